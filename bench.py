@@ -2,16 +2,19 @@
 """
 bench.py -- fixed-point iterations/sec of the wealth-consumption-ratio operator on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload gcy20|gcy16|ssy15] [--no-cpu]
+    python bench.py --gpus N --steps K --warmup W [--workload gcy20|gcy16|ssy15] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-secondary]]
 
 A "step" is one successive-approximation iteration: one application of the Koopmans
 operator T (expectation passes + fused Epstein-Zin aggregator) with the sup-norm
 residual max|Tw - w| fused into the last kernel -- the body of the reference's hot loop
 (code/solvers.py:34-36).  Inputs are resident in HBM when the timed region starts.
 Default workload: GCY (20,)*6 fp64 (BASELINE.json configs[3] grid; the grid the
-north_star roofline/CPU targets are quoted on), synthetic w = 400 + 500*U(0,1).
+north_star roofline/CPU targets are quoted on), synthetic w = 400 + 500*U(0,1), seeded.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`, ...).  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
+--full adds the objects below, each measured after the timed steps:
   roofline     dominant kernel: algorithmic bytes per launch / mean launch duration, measured with HIP events on
                the library's stream in a second loop of the same steps right behind the timed one (the timed loop
                itself runs without the two hipEventRecord per launch); also the in-run rate of a
@@ -179,6 +182,112 @@ def newton_roofline(op, w_host, N, krylov_f32, inner=1e-6):
     return out
 
 
+DUMP_MAX_POINTS = 1 << 22      # 32 MB of float64: grids above it are dumped as a sample (the dump stays under 64 MB)
+
+
+def dump_outputs(dirname, tw, resid):
+    """--dump-outputs: what the last timed step returned to its caller, as float64 .npy files -- `Tw.npy`, the
+    grid T w in its shape, and `residual.npy`, the fused sup-norm step max|T w - w| (one value).  A grid of more than
+    DUMP_MAX_POINTS points is written as `Tw_sample.npy` instead: the flat grid cut into DUMP_MAX_POINTS equal runs,
+    one point from each at an offset drawn from a fixed seed, so that two builds dump the same points."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    flat = tw.reshape(-1)
+    n = flat.numel()
+    if n <= DUMP_MAX_POINTS:
+        np.save(os.path.join(dirname, "Tw.npy"), tw.cpu().numpy())
+    else:
+        run = n // DUMP_MAX_POINTS
+        idx = np.arange(DUMP_MAX_POINTS, dtype=np.int64) * run + np.random.default_rng(2024).integers(0, run, DUMP_MAX_POINTS)
+        np.save(os.path.join(dirname, "Tw_sample.npy"), flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy())
+    np.save(os.path.join(dirname, "residual.npy"), resid.cpu().numpy())
+
+
+def roofline_figures(op, step, stream, w_dev, N, shapes, args, dt, plan_now):
+    """--full: per-kernel durations, the dominant kernel against the HBM peak and the copy ceiling, the fp64 pipe.
+    Runs after the timed loop and its outputs (it steps the operator again and reuses the timed loop's buffers)."""
+    import torch
+    # per-kernel durations: the same steps once more with HIP events around every launch (on the launch stream)
+    op.set_profiling(True)
+    for i in range(8):            # (creates the event pool)
+        step(i)
+    torch.cuda.synchronize()
+    op.reset_counters()
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        step(args.warmup + i)
+    torch.cuda.synchronize()
+    dt_prof = time.perf_counter() - t0
+    counters = op.counters()
+    op.set_profiling(False)
+    # this box's copy ceiling, in the same run: the library's own streaming copy of the grid (read N + write N doubles;
+    # 16 bytes per lane, eight loads in flight per lane, non-temporal loads and stores -- the fastest copy form
+    # tools/probes/kernel_bench.hip found, profiles/round4_kernel_bench.txt), timed with HIP events on the launch
+    # stream; torch's copy_ (what rounds 1-3 printed here) beside it
+    def timed_copies(fn, reps=100):
+        for _ in range(60):              # (the clock ramps for a few milliseconds after the host-side pause before this block)
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(reps):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return reps * 16.0 * N / (e0.elapsed_time(e1) * 1e-3) / 1e9
+    scratch = torch.empty(shapes, dtype=torch.float64, device="cuda")
+    torch_copy_gbs = timed_copies(lambda: scratch.copy_(w_dev))
+    copy_gbs = timed_copies(lambda: op.stream_copy_dev(w_dev.data_ptr(), scratch.data_ptr(), N))
+    torch_copy_gbs = max(torch_copy_gbs, timed_copies(lambda: scratch.copy_(w_dev)))
+    del scratch
+
+    dom = max(counters, key=lambda c: c["total_ms"])
+    avg_ms = dom["total_ms"] / max(dom["launches"], 1)
+    achieved = dom["alg_bytes"] / (avg_ms * 1e-3) / 1e9
+    # HBM bytes per launch cannot be counted from inside this process (PMC counters need rocprofv3): the figure
+    # is taken from the committed PMC passes of this same command (profiles/: (2*FETCH_SIZE + WRITE_SIZE)*1024,
+    # gfx950 correction of MI355X_MICROARCH.md) and only if that profile was taken on the plan that ran here
+    traffic, traffic_source = None, "no committed PMC profile of this workload"
+    try:
+        pfile = os.path.join("profiles", f"round4_{args.workload}_pmc.json")
+        pmc = json.load(open(os.path.join(ROOT, pfile)))
+        if pmc.get("plan") != plan_now:
+            traffic_source = f"{pfile} was taken on a different kernel plan: dropped"
+        else:
+            traffic = pmc["kernels"][pmc["launch_order"][counters.index(dom)]]["hbm_traffic_bytes"]
+            traffic_source = f"{pfile} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, same plan)"
+    except (OSError, KeyError, ValueError, IndexError):
+        pass
+    kernels = [{"name": c["name"], "launches": c["launches"],
+                "avg_ms": c["total_ms"] / max(c["launches"], 1),
+                "alg_GB": c["alg_bytes"] / 1e9,
+                "GBps": c["alg_bytes"] / (c["total_ms"] / max(c["launches"], 1) * 1e-3) / 1e9,
+                "frac_hbm": c["alg_bytes"] / (c["total_ms"] / max(c["launches"], 1) * 1e-3) / 1e9 / HBM_PEAK_GBS}
+               for c in counters]
+    return {
+        "roofline": {"bound": "hbm", "kernel": dom["name"], "achieved": achieved, "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                     "traffic_source": traffic_source,
+                     "avg_launch_ms": avg_ms, "alg_bytes_per_launch": dom["alg_bytes"],
+                     "events_from": f"a second loop of the same {args.steps} steps with HIP events around every launch "
+                                    f"({dt_prof / args.steps * 1e3:.4f} ms per step against {dt / args.steps * 1e3:.4f} without)",
+                     "copy_ceiling_GBps": copy_gbs, "frac_of_copy_ceiling": achieved / copy_gbs,
+                     "copy_ceiling_kind": "sdfs_stream_copy_dev: 16 B per lane, eight loads in flight per lane, non-temporal; "
+                                          "HIP events on the launch stream, 100 copies of the grid",
+                     "torch_copy_GBps": torch_copy_gbs, "guide_copy_GBps": 6290.0,
+                     "step_alg_bytes": sum(c["alg_bytes"] for c in counters),
+                     "step_frac": sum(c["alg_bytes"] for c in counters) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
+                     "step_frac_of_copy_ceiling": sum(c["alg_bytes"] for c in counters) / (dt / args.steps) / 1e9 / copy_gbs},
+        # secondary bound (DESIGN.md 4.1): an fp64 MFMA holds its SIMD for its full 64 / 20 cycles and every VALU
+        # instruction of the same SIMD shares that issue slot, so a pass costs MFMA + VALU issue cycles; the
+        # nominal fp64 peak is 78.6 TFLOP/s.  Algorithmic flops = contraction MACs x 2 plus the two powers of
+        # the operator at the 31 fp64 instructions (~50 flops) the kernels spend on each.
+        "fp64_pipe": {"peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                      "achieved": (sum(c["alg_flops"] for c in counters) + 2 * 50.0 * N) / (dt / args.steps) / 1e12,
+                      "contraction_only": sum(c["alg_flops"] for c in counters) / (dt / args.steps) / 1e12},
+        "kernels": kernels,
+    }
+
+
 def spawn_ranks(n, backend):
     """`python bench.py --gpus N` without a launcher: run torch.distributed.run as a child (one rank per GPU,
     rendezvous on 127.0.0.1) with this command line; rank 0 of the child prints the JSON line."""
@@ -206,9 +315,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)     # idle period run ~5 % slower (clock ramp)
     ap.add_argument("--workload", default="gcy20", choices=sorted(WORKLOADS))
     ap.add_argument("--allow-knobs", action="store_true", help="run although SDFS_* kernel-plan variables are set")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, CPU baseline and secondary runs (off: the headline step only)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out the secondary runs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     # the library's test knobs change the kernels that run (SDFS_PLAN=classic is the round-1 path): a measurement must not
     # pick one up by accident
@@ -220,6 +334,8 @@ def main():
     backend = os.environ.get("SDFS_BENCH_BACKEND", "nccl")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("SDFS_BENCH_SHARDED", "0") == "1"):
+        raise SystemExit("bench.py: --dump-outputs is supported on the single-GPU path only")
     if args.gpus > 1 and "RANK" not in os.environ:
         # not under a launcher: start one rank per GPU ourselves, as a CHILD process and before anything in
         # this process touches the GPU (device_count() does not initialise it), and pass its exit code on
@@ -267,7 +383,7 @@ def main():
         from sdfs_via_autodiff_amd.distributed import bench_sharded
         line = bench_sharded(S, model, shapes, params, arrays, args, rank, local_rank, world)
         if rank == 0:
-            if not args.no_cpu:
+            if args.full and not args.no_cpu:
                 # same bounded CPU sample as at N = 1 (rank 0's host cores; the other ranks wait at the barrier)
                 w_host = 400 + 500 * np.random.default_rng(0).random(shapes)
                 line["cpu_baseline"] = cpu_baseline(model, shapes, params, arrays, w_host)
@@ -303,63 +419,9 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     last_resid = float(resid.item())
-    # per-kernel durations: the same steps once more with HIP events around every launch (on the launch stream)
-    op.set_profiling(True)
-    for i in range(8):            # (creates the event pool)
-        step(i)
-    torch.cuda.synchronize()
-    op.reset_counters()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        step(args.warmup + i)
-    torch.cuda.synchronize()
-    dt_prof = time.perf_counter() - t0
-    counters = op.counters()
-    op.set_profiling(False)
-    # this box's copy ceiling, in the same run: the library's own streaming copy of the grid (read N + write N doubles;
-    # 16 bytes per lane, eight loads in flight per lane, non-temporal loads and stores -- the fastest copy form
-    # tools/probes/kernel_bench.hip found, profiles/round4_kernel_bench.txt), timed with HIP events on the launch
-    # stream; torch's copy_ (what rounds 1-3 printed here) beside it
-    def timed_copies(fn, reps=100):
-        for _ in range(60):              # (the clock ramps for a few milliseconds after the host-side pause before this block)
-            fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(reps):
-            fn()
-        e1.record(stream)
-        e1.synchronize()
-        return reps * 16.0 * N / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    scratch = torch.empty(shapes, dtype=torch.float64, device="cuda")
-    torch_copy_gbs = timed_copies(lambda: scratch.copy_(bufs[0]))
-    copy_gbs = timed_copies(lambda: op.stream_copy_dev(bufs[0].data_ptr(), scratch.data_ptr(), N))
-    torch_copy_gbs = max(torch_copy_gbs, timed_copies(lambda: scratch.copy_(bufs[0])))
-    del scratch
-
-    dom = max(counters, key=lambda c: c["total_ms"])
-    avg_ms = dom["total_ms"] / max(dom["launches"], 1)
-    achieved = dom["alg_bytes"] / (avg_ms * 1e-3) / 1e9
-    # HBM bytes per launch cannot be counted from inside this process (PMC counters need rocprofv3): the figure
-    # is taken from the committed PMC passes of this same command (profiles/: (2*FETCH_SIZE + WRITE_SIZE)*1024,
-    # gfx950 correction of MI355X_MICROARCH.md) and only if that profile was taken on the plan that ran here
-    traffic, traffic_source = None, "no committed PMC profile of this workload"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bufs[(args.warmup + args.steps) & 1], resid)
     plan_now = op.describe_plan().strip().split("\n")
-    try:
-        pfile = os.path.join("profiles", f"round4_{args.workload}_pmc.json")
-        pmc = json.load(open(os.path.join(ROOT, pfile)))
-        if pmc.get("plan") != plan_now:
-            traffic_source = f"{pfile} was taken on a different kernel plan: dropped"
-        else:
-            traffic = pmc["kernels"][pmc["launch_order"][counters.index(dom)]]["hbm_traffic_bytes"]
-            traffic_source = f"{pfile} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, same plan)"
-    except (OSError, KeyError, ValueError, IndexError):
-        pass
-    kernels = [{"name": c["name"], "launches": c["launches"],
-                "avg_ms": c["total_ms"] / max(c["launches"], 1),
-                "alg_GB": c["alg_bytes"] / 1e9,
-                "GBps": c["alg_bytes"] / (c["total_ms"] / max(c["launches"], 1) * 1e-3) / 1e9,
-                "frac_hbm": c["alg_bytes"] / (c["total_ms"] / max(c["launches"], 1) * 1e-3) / 1e9 / HBM_PEAK_GBS}
-               for c in counters]
     line = {
         "metric": "fixed-point iterations/sec",
         "value": args.steps / dt,
@@ -371,34 +433,15 @@ def main():
         "config": {"workload": f"{model.upper()} {'x'.join(map(str, shapes))} grid, successive-approximation "
                                f"step (T apply + fused sup-norm residual), default calibration, Rouwenhorst",
                    "grid_points": N, "spinup_steps": SPINUP, "plan": plan_now, "env_knobs": knobs},
-        "roofline": {"bound": "hbm", "kernel": dom["name"], "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "traffic_source": traffic_source,
-                     "avg_launch_ms": avg_ms, "alg_bytes_per_launch": dom["alg_bytes"],
-                     "events_from": f"a second loop of the same {args.steps} steps with HIP events around every launch "
-                                    f"({dt_prof / args.steps * 1e3:.4f} ms per step against {dt / args.steps * 1e3:.4f} without)",
-                     "copy_ceiling_GBps": copy_gbs, "frac_of_copy_ceiling": achieved / copy_gbs,
-                     "copy_ceiling_kind": "sdfs_stream_copy_dev: 16 B per lane, eight loads in flight per lane, non-temporal; "
-                                          "HIP events on the launch stream, 100 copies of the grid",
-                     "torch_copy_GBps": torch_copy_gbs, "guide_copy_GBps": 6290.0,
-                     "step_alg_bytes": sum(c["alg_bytes"] for c in counters),
-                     "step_frac": sum(c["alg_bytes"] for c in counters) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                     "step_frac_of_copy_ceiling": sum(c["alg_bytes"] for c in counters) / (dt / args.steps) / 1e9 / copy_gbs},
-        # secondary bound: an fp64 MFMA holds its SIMD for its full 64 / 20 cycles and every VALU
-        # instruction of the same SIMD shares that issue slot, so a pass costs MFMA + VALU issue cycles; the
-        # nominal fp64 peak is 78.6 TFLOP/s.  Algorithmic flops = contraction MACs x 2 plus the two powers of
-        # the operator at the 31 fp64 instructions (~50 flops) the kernels spend on each.
-        "fp64_pipe": {"peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                      "achieved": (sum(c["alg_flops"] for c in counters) + 2 * 50.0 * N) / (dt / args.steps) / 1e12,
-                      "contraction_only": sum(c["alg_flops"] for c in counters) / (dt / args.steps) / 1e12},
-        "kernels": kernels,
         "ideal_single_pass_frac": 16.0 * N / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
         "last_residual": last_resid,
     }
-    if not args.no_cpu:
+    if args.full:
+        line.update(roofline_figures(op, step, stream, bufs[0], N, shapes, args, dt, plan_now))
+    if args.full and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(model, shapes, params, arrays, w_host)
         line["gpu_over_cpu"] = line["value"] / line["cpu_baseline"]["value"]
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         sec = {}
         if args.workload == "gcy20":
             # time-to-converge (sup-norm 1e-8) of the bench grid itself, device-resident Newton-Krylov

@@ -1048,52 +1048,57 @@ def bench_sharded(S, model, shapes, params, arrays, args, rank, local_rank, worl
     dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     dt = float(dt.item())
     n_exch = op.n_exchanges - x0
-    # per-kernel durations of rank 0's stages: a second, shorter loop with HIP events around every launch (the timed
-    # loop above runs without them), both orientations of the mirror schedule
-    backends = [b for b in (op.backend, op.backend_m if mirror else None) if b is not None]
-    for b in backends:
-        b.set_profiling(True)
-    for _ in range(4):
-        w = step(w)
-    torch.cuda.synchronize()
-    for b in backends:
-        b.reset_counters()
-    for _ in range(min(args.steps, 40)):
-        w = step(w)
-    torch.cuda.synchronize()
-    counters = [c for b in backends for c in b.counters()]
-    for b in backends:
-        b.set_profiling(False)
     N = int(np.prod(shapes))
-    dom = max(counters, key=lambda c: c["total_ms"])
-    avg_ms = dom["total_ms"] / max(dom["launches"], 1)
-    achieved = dom["alg_bytes"] / (avg_ms * 1e-3) / 1e9
-    # the same step with fp32 intermediates between the stages (successive_approx_sharded(t_f32=True): half the bytes per
-    # exchange while the iteration is far from its tolerance); reported beside the fp64 step, never as `value`
-    t32 = None
-    if mirror and all(hasattr(b, "set_t_f32") for b in backends):
-        ref = torch.tensor([float(w.max()), -float(w.min())], dtype=torch.float64, device="cuda")
-        op.allreduce_max(ref)
-        hi, lo = float(ref[0].item()), -float(ref[1].item())
-        if lo > 0.0 and all(b.set_t_f32(True, float(np.sqrt(hi * lo))) for b in backends):
-            try:
-                for _ in range(max(args.warmup, 2)):
-                    w = step(w)
-                dist.barrier()
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(args.steps):
-                    w = step(w)
-                torch.cuda.synchronize()
-                dist.barrier()
-                d32 = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device="cuda")
-                dist.all_reduce(d32, op=dist.ReduceOp.MAX)
-                t32 = {"ms_per_step": float(d32.item()) / args.steps * 1e3,
-                       "bytes_per_peer_link_per_exchange": 4.0 * N / world / world,
-                       "note": "opt-in (t_f32): fp32 intermediates between the stages, fp64 iterate and residual"}
-            finally:
-                for b in backends:
-                    b.set_t_f32(False)
+    roofline = t32 = None
+    if args.full:
+        # per-kernel durations of rank 0's stages: a second, shorter loop with HIP events around every launch (the timed
+        # loop above runs without them), both orientations of the mirror schedule
+        backends = [b for b in (op.backend, op.backend_m if mirror else None) if b is not None]
+        for b in backends:
+            b.set_profiling(True)
+        for _ in range(4):
+            w = step(w)
+        torch.cuda.synchronize()
+        for b in backends:
+            b.reset_counters()
+        for _ in range(min(args.steps, 40)):
+            w = step(w)
+        torch.cuda.synchronize()
+        counters = [c for b in backends for c in b.counters()]
+        for b in backends:
+            b.set_profiling(False)
+        dom = max(counters, key=lambda c: c["total_ms"])
+        avg_ms = dom["total_ms"] / max(dom["launches"], 1)
+        achieved = dom["alg_bytes"] / (avg_ms * 1e-3) / 1e9
+        roofline = {"bound": "hbm", "kernel": dom["name"], "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                    "frac": achieved / 8000.0, "traffic": None,
+                    "traffic_source": "PMC counters need rocprofv3; no committed profile of the sharded stage kernels",
+                    "avg_launch_ms": avg_ms, "alg_bytes_per_launch": dom["alg_bytes"], "note": "rank 0's local shard"}
+        # the same step with fp32 intermediates between the stages (successive_approx_sharded(t_f32=True): half the bytes per
+        # exchange while the iteration is far from its tolerance); reported beside the fp64 step, never as `value`
+        if mirror and all(hasattr(b, "set_t_f32") for b in backends):
+            ref = torch.tensor([float(w.max()), -float(w.min())], dtype=torch.float64, device="cuda")
+            op.allreduce_max(ref)
+            hi, lo = float(ref[0].item()), -float(ref[1].item())
+            if lo > 0.0 and all(b.set_t_f32(True, float(np.sqrt(hi * lo))) for b in backends):
+                try:
+                    for _ in range(max(args.warmup, 2)):
+                        w = step(w)
+                    dist.barrier()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(args.steps):
+                        w = step(w)
+                    torch.cuda.synchronize()
+                    dist.barrier()
+                    d32 = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device="cuda")
+                    dist.all_reduce(d32, op=dist.ReduceOp.MAX)
+                    t32 = {"ms_per_step": float(d32.item()) / args.steps * 1e3,
+                           "bytes_per_peer_link_per_exchange": 4.0 * N / world / world,
+                           "note": "opt-in (t_f32): fp32 intermediates between the stages, fp64 iterate and residual"}
+                finally:
+                    for b in backends:
+                        b.set_t_f32(False)
     return {
         "metric": "fixed-point iterations/sec",
         "value": args.steps / dt,
@@ -1113,10 +1118,7 @@ def bench_sharded(S, model, shapes, params, arrays, args, rank, local_rank, worl
                                   else "REHEARSAL (not a multi-GPU measurement): ranks share a device or exchange through the host",
                    "shard_sizes": op.a_sizes,
                    "plan_rank0": op.backend.describe_plan().strip().split("\n")},
-        "roofline": {"bound": "hbm", "kernel": dom["name"], "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                     "frac": achieved / 8000.0, "traffic": None,
-                     "traffic_source": "PMC counters need rocprofv3; no committed profile of the sharded stage kernels",
-                     "avg_launch_ms": avg_ms, "alg_bytes_per_launch": dom["alg_bytes"], "note": "rank 0's local shard"},
+        "roofline": roofline,
         "exchange": {"per_iteration": n_exch / max(args.steps, 1),
                      "bytes_sent_per_rank_per_exchange": 8.0 * N / world * (world - 1) / world,
                      "bytes_per_peer_link_per_exchange": 8.0 * N / world / world},

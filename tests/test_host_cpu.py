@@ -400,3 +400,36 @@ def test_bench_gpus_flag_never_falls_back_to_one_gpu():
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node=4" in cmd
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-4:] == ["--gpus", "4", "--steps", "3"]
     assert captured["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_bench_dump_outputs_whole_grid_or_fixed_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: a grid of up to DUMP_MAX_POINTS points is written whole, a larger one as the same
+    seeded sample on every call (one point from each equal run of the flat grid); float64, residual beside it."""
+    import sys
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_POINTS", 64)
+    res = torch.tensor([0.5], dtype=torch.float64)
+    small = torch.from_numpy(np.random.default_rng(3).random((4, 4, 4)))
+    bench.dump_outputs(str(tmp_path / "small"), small, res)
+    assert sorted(os.listdir(tmp_path / "small")) == ["Tw.npy", "residual.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "Tw.npy"), small.numpy())
+    assert np.array_equal(np.load(tmp_path / "small" / "residual.npy"), [0.5])
+    big = torch.from_numpy(np.random.default_rng(4).random((10, 10, 10)))
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), big, res)
+    assert sorted(os.listdir(tmp_path / "big1")) == ["Tw_sample.npy", "residual.npy"]
+    s = np.load(tmp_path / "big1" / "Tw_sample.npy")
+    assert s.dtype == np.float64 and s.shape == (64,)
+    assert np.array_equal(s, np.load(tmp_path / "big2" / "Tw_sample.npy"))
+    flat, run = big.numpy().ravel(), 1000 // 64
+    assert all(s[k] in flat[k * run:(k + 1) * run] for k in range(64))
+
+
+def test_bench_rejects_steps_below_one():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and '"metric"' not in r.stdout
