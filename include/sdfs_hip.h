@@ -178,6 +178,31 @@ int sdfs_apply_jvp_dev(sdfs_handle* h, const double* v_dev, double* out_dev, int
 int sdfs_apply_vjp(sdfs_handle* h, const double* w_host, const double* u_host, double* out_host);
 int sdfs_apply_vjp_dev(sdfs_handle* h, const double* u_dev, double* out_dev, int minus_identity);
 
+/* Parameter sensitivities of the fixed point w* = T(w*; p) (the open item of the reference paper's conclusion: the fixed point
+ * "can potentially [be differentiated] with respect to the parameters").  A direction of (params, arrays) -- the reference's
+ * own terms, as in sdfs_create -- is (dparams, darrays): `dparams` has the handle's nparams entries, `darrays` its narrays
+ * HOST pointers of the same sizes as the arrays (NULL, or darrays == NULL: a zero tangent); e.g. what jax.jvp of the
+ * reference's discretize_ssy / discretize_gcy returns.
+ *
+ * out = dT(w)[dparams, darrays], the tangent of T at a fixed w (device pointers, N doubles each; out distinct from Tw):
+ *   (T w - 1) (dbeta/beta - (dtheta/theta) ln((T w - 1)/beta) + (dln a2 + dln a3)/theta) + (1/theta) J(w) [w .* (dtheta ln w + dln a1)]
+ * with theta = (1-gamma)/(1-1/psi) and the log-tangents of the scale tables a1 = exp(theta h_lambda), a2 = exp((1/2)((1-gamma)
+ * sigma_c)^2), a3 = exp((1-gamma)(mu_c + z)).  Linearises at w (one linearising application of T, T w into Tw_dev when not
+ * NULL) and leaves that linearisation cached for sdfs_apply_jvp_dev / sdfs_solve_linear_dev.  The J.v term is skipped for
+ * directions with dtheta = 0 and dln a1 = 0.  SDFS_ERR_UNSUPPORTED: a non-zero tangent of a transition array (SSY arrays
+ * 1, 3, 5, 7; GCY 1, 3, 5, 8, 11, 14 -- the persistence parameters move those), or a continuous, dense or sharded handle. */
+int sdfs_param_tangent_dev(sdfs_handle* h, const double* w_dev, const double* dparams, const double* const* darrays,
+                           double* out_dev, double* Tw_dev);
+/* x = (I - J)^{-1} rhs, or (I - J^T)^{-1} rhs when `transpose` != 0, at the cached linearisation (sdfs_linearize_dev or
+ * sdfs_param_tangent_dev): forward sensitivities dw* / dp = (I - J(w*))^{-1} dT/dp, adjoints lambda = (I - J(w*)^T)^{-1} g.
+ * BiCGSTAB on the device (x0 = 0, stop when |r|_2 <= max(opts.inner_rtol |rhs|_2, opts.inner_atol), at most
+ * opts.inner_max_iter iterations, 0 -> 10 N; opts NULL = defaults), fp64 only: opts.krylov_f32 != 0 is SDFS_ERR_ARG.
+ * `transpose` is SDFS_ERR_UNSUPPORTED where sdfs_apply_vjp_dev is.  n_iter (iterations; two products each) and
+ * final_rel_resid (|r|_2 / |rhs|_2 of the recursion) may be NULL.  A breakdown or a solve that stops above the tolerance
+ * returns SDFS_ERR_NUMERIC, with x and the residual where it stopped. */
+int sdfs_solve_linear_dev(sdfs_handle* h, int transpose, const sdfs_opts* opts, const double* rhs_dev, double* x_dev,
+                          int64_t* n_iter, double* final_rel_resid);
+
 /* max|T(w) - w| of the most recent apply that computed it. */
 int sdfs_residual(sdfs_handle* h, double* sup_norm);
 

@@ -24,6 +24,8 @@ from .continuous import (ContinuousOperator, build_grid, T_fun_factory, wc_ratio
                          lin_interp, vals_to_coords, construct_wstar_callable, save_wstar, load_wstar)
 from .single_index import (DenseOperator, compute_H_single_index, discretize_single_index, single_index_T,
                            single_to_multi, multi_to_single)
+from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_ratio_sensitivities,
+                          wc_ratio_gradient)
 from ._lib import SdfsError, LIB_PATH
 
 __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize_gcy",
@@ -36,4 +38,5 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "lin_interp", "vals_to_coords", "construct_wstar_callable", "save_wstar", "load_wstar",
            "DenseOperator", "compute_H_single_index", "discretize_single_index", "single_index_T",
            "single_to_multi", "multi_to_single",
+           "discretize_ssy_tangent", "discretize_gcy_tangent", "wc_ratio_sensitivities", "wc_ratio_gradient",
            "SdfsError", "LIB_PATH"]

@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("SDFS_LIB_NAME", "libsdfs_hip.so")
 
 SDFS_MODEL_SSY, SDFS_MODEL_GCY = 0, 1
 SDFS_ALGO_SA, SDFS_ALGO_NEWTON, SDFS_ALGO_ANDERSON = 0, 1, 2
+SDFS_ERR_ARG = -1
 SDFS_ERR_UNSUPPORTED = -3
 SDFS_ERR_NUMERIC = -4
 SDFS_MAX_KERNELS = 16
@@ -68,6 +69,8 @@ SYMBOLS = {
     "sdfs_apply_jvp_dev": (C.c_int, [_P, _P, _P, C.c_int]),
     "sdfs_apply_vjp": (C.c_int, [_P, _P, _P, _P]),
     "sdfs_apply_vjp_dev": (C.c_int, [_P, _P, _P, C.c_int]),
+    "sdfs_param_tangent_dev": (C.c_int, [_P, _P, _D, C.POINTER(_D), _P, _P]),
+    "sdfs_solve_linear_dev": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _P, _I64, _D]),
     "sdfs_residual": (C.c_int, [_P, _D]),
     "sdfs_solve": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _I64, _I64, _D]),
     "sdfs_solve_dev": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _I64, _I64, _D]),

@@ -29,6 +29,7 @@
 #include "dense_kernel.hpp"
 #include "vec_kernels.hpp"
 #include "krylov_kernels.hpp"
+#include "sens_kernels.hpp"
 
 using namespace sdfs;
 
@@ -173,6 +174,21 @@ struct sdfs_handle {
   int axis_a = -1, axis_b = -1;
 
   double* a3 = nullptr;              // current-state scale table, kept only when the z tensor is slice-identical
+
+  // parameter tangent (sdfs_param_tangent_dev): what setup_model built the scale tables a1 / a2 / a3 from
+  struct {
+    int ip_beta = 0, ip_gamma = 0, ip_psi = 0, ip_mu_c = 0;   // indices into params
+    int ia_hlam = 0, ia_sigc = 0, ia_z = 0;                   // indices into arrays
+    std::vector<int> trans;                                   // indices of the transition arrays
+    std::vector<long long> sizes;                             // element count of every array
+    double gamma = 0, psi = 0, mu_c = 0;
+    std::vector<double> hlam, sigc, z;                        // h_lambda, sigma_c, z states (z in the a3 layout)
+    int ax_a1 = 0, ax_a2 = 0;                                 // axes a1 (next state) and a2 (current state) are indexed by
+    int a3s[MAXD] = {0, 0, 0, 0, 0, 0};                       // strides of the a3 table along each axis
+    std::vector<double> dla3_host;                            // staging of the dln a3 table (kept alive across the async copy)
+    double* dla3 = nullptr;                                   // device copy
+    double* v = nullptr;                                      // J.v direction of the tangent
+  } sens;
 
   // Newton-Krylov with fp32 Krylov vectors / J.v streams (opts.krylov_f32); set while such a solve runs
   bool krylov_f32 = false;
@@ -1803,8 +1819,12 @@ int solve_sa(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int
 // b in kry[6]; solution in kry[5].  One host sync per iteration (reads rr).
 // T = storage type of the Krylov vectors: double, or float under opts.krylov_f32 (the vectors then
 // occupy the first half of the same allocations and the J.v kernels read / write fp32, see run_plan)
+// mode = the matvec: MODE_JVP solves (J - I) x = b, MODE_VJP (fp64 only) solves (J^T - I) x = b.  The fused forms below
+// (dot products in the last J.v pass, the merged small-grid loop, the slice_jfused updates, the captured graph) are
+// J.v-only: the transposed solve runs the plain iteration.
 template <typename T>
-int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs) {
+int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mode = MODE_JVP) {
+  const bool vjp = mode == MODE_VJP;
   T *r = (T*)h->kry[0], *rhat = (T*)h->kry[1], *p = (T*)h->kry[2], *q = (T*)h->kry[3], *t = (T*)h->kry[4],
     *x = (T*)h->kry[5];
   const double* b = h->kry[6];
@@ -1830,7 +1850,7 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs) {
   const long long maxit = o.inner_max_iter > 0 ? o.inner_max_iter : 10 * n;
   // <t, s> and <t, t> come out of the last J.v pass when its tiles fit the partial-sum buffer
   const long long last_tiles = jvp_last_tiles(h);
-  const bool fused_dots = last_tiles > 0 && 2 * last_tiles <= (long long)MAX_PARTIAL_BLOCKS * AND_MAX_M &&
+  const bool fused_dots = !vjp && last_tiles > 0 && 2 * last_tiles <= (long long)MAX_PARTIAL_BLOCKS * AND_MAX_M &&
                           (h->plan[0].passes.size() > 1 || (h->fast.ok && (!h->krylov_f32 || h->fast.f32_ok))) && h->knobs.no_dot_fusion == 0 &&
                           !h->krylov_bf16;      // (the fused sums would see the J.v output before its rounding)
   // small grids are launch-bound: the finishing kernels merge into the vector kernels behind them (vec_kernels.hpp),
@@ -1840,7 +1860,7 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs) {
   double* const pss = h->partial + PR;          // <s, s>
   double* const pt = h->partial + 2 * PR;       // <t, s>, <t, t>
   double* const prr = h->partial + 4 * PR;      // <r, r>, <rhat, r>
-  const bool merged = n <= (1LL << 22) && (!fused_dots || last_tiles <= MAX_PARTIAL_BLOCKS) && h->knobs.no_bicg_merge == 0;
+  const bool merged = !vjp && n <= (1LL << 22) && (!fused_dots || last_tiles <= MAX_PARTIAL_BLOCKS) && h->knobs.no_bicg_merge == 0;
   auto iteration_merged = [&]() -> int {
     int rc2;
     { ProfScope ps(h, cvec);
@@ -1868,13 +1888,13 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs) {
     int rc2;
     { ProfScope ps(h, cvec);
       hipLaunchKernelGGL(k_bicg_update_p<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)r, p, (const T*)q, n, h->sc, (const unsigned long long*)gate); }
-    if ((rc2 = run_plan(h, h->plan[0], MODE_JVP, true, true, (const double*)p, (double*)q, (const double*)p, nullptr, gate, 0.0, 1))) return rc2;
+    if ((rc2 = run_plan(h, h->plan[0], mode, true, true, (const double*)p, (double*)q, (const double*)p, nullptr, gate, 0.0, 1))) return rc2;
     { ProfScope ps(h, cvec);
       hipLaunchKernelGGL(k_dot<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)rhat, (const T*)q, n, h->partial, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_alpha_finish, dim3(1), dim3(VEC_BLOCK), 0, st, h->partial, g, h->sc, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_s<T>, dim3(g), dim3(VEC_BLOCK), 0, st, r, (const T*)q, n, h->sc, h->partial, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_s_finish, dim3(1), dim3(VEC_BLOCK), 0, st, h->partial, g, h->sc, (const unsigned long long*)gate); }
-    if ((rc2 = run_plan(h, h->plan[0], MODE_JVP, true, true, (const double*)r, (double*)t, (const double*)r, nullptr, gate, 0.0, 1,
+    if ((rc2 = run_plan(h, h->plan[0], mode, true, true, (const double*)r, (double*)t, (const double*)r, nullptr, gate, 0.0, 1,
                         fused_dots ? h->partial : nullptr))) return rc2;
     { ProfScope ps(h, cvec);
       if (!fused_dots) hipLaunchKernelGGL(k_dot2<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)t, (const T*)r, n, h->partial, (const unsigned long long*)gate);
@@ -1893,7 +1913,7 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs) {
 #else
   const bool jf32 = std::is_same<T, float>::value && h->krylov_f32 && h->krylov_mfma32 && !h->krylov_bf16 && h->fast.f32_ok;
 #endif
-  bool jfuse = ((std::is_same<T, double>::value && !h->krylov_f32) || jf32) && !merged && h->fast.ok && !h->fast.small && !h->fast.pad &&
+  bool jfuse = !vjp && ((std::is_same<T, double>::value && !h->krylov_f32) || jf32) && !merged && h->fast.ok && !h->fast.small && !h->fast.pad &&
                h->fast.passes.size() >= 2 && !P0->line && !P0->pad && PL->line && PL->ld.lrest % LINE_R == 0 && h->knobs.no_dot_fusion == 0;
   // workgroups of the last pass (one partial sum each per inner product), wave tiles of the first
   const long long jf_last = jfuse ? (jf32 ? PL->ld.ntiles * LINE_R / line32_row_floats(PL->n, PL->ld.lrest) : PL->ld.ntiles) : 0;
@@ -1949,7 +1969,7 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs) {
   // breakdown / convergence test for long.
   const int chunk = (int)std::min<long long>(maxit, n <= (1LL << 22) ? 8 : 1);
   const int gslot = std::is_same<T, float>::value ? 1 : 0;
-  const bool graph = o.use_graph && !h->profiling && st != nullptr && chunk > 1 && !std::is_same<T, bf16r>::value;
+  const bool graph = !vjp && o.use_graph && !h->profiling && st != nullptr && chunk > 1 && !std::is_same<T, bf16r>::value;
   if (graph && (h->bicg_graph[gslot] == nullptr || h->bicg_graph_chunk[gslot] != chunk)) {
     if (h->bicg_graph[gslot]) { hipGraphExecDestroy(h->bicg_graph[gslot]); h->bicg_graph[gslot] = nullptr; }
     hipGraph_t gr = nullptr;
@@ -2501,6 +2521,9 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
       h->ax[a].Q = q; h->ax[a].qcount = (long long)qf[a].size() / ((long long)h->shape[a] * h->shape[a]);
       strncpy(h->ax[a].name, nm[a], sizeof h->ax[a].name - 1);
     }
+    h->sens.ip_beta = 0; h->sens.ip_gamma = 1; h->sens.ip_psi = 2; h->sens.ip_mu_c = 3;
+    h->sens.ia_hlam = 0; h->sens.ia_sigc = 8; h->sens.ia_z = 6; h->sens.trans = {1, 3, 5, 7};
+    h->sens.ax_a1 = 0; h->sens.ax_a2 = 1; h->sens.a3s[2] = nj; h->sens.a3s[3] = 1;
     if (z_same) {
       if ((rc = upload(h, &h->a3, a3.data(), a3.size()))) return rc;
       h->a3_host = a3;
@@ -2546,6 +2569,10 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
       h->ax[a].Q = q; h->ax[a].qcount = (long long)qf[a].size() / ((long long)h->shape[a] * h->shape[a]);
       strncpy(h->ax[a].name, nm[a], sizeof h->ax[a].name - 1);
     }
+    h->sens.ip_beta = 0; h->sens.ip_gamma = 2; h->sens.ip_psi = 1; h->sens.ip_mu_c = 5;
+    h->sens.ia_hlam = 13; h->sens.ia_sigc = 9; h->sens.ia_z = 0; h->sens.trans = {1, 3, 5, 8, 11, 14};
+    h->sens.ax_a1 = 5; h->sens.ax_a2 = 3;
+    h->sens.a3s[0] = 1; h->sens.a3s[4] = (int)na; h->sens.a3s[2] = (int)(ne * na); h->sens.a3s[1] = (int)(nc * ne * na);
     if (z_same) {
       if ((rc = upload(h, &h->a3, a3.data(), a3.size()))) return rc;
       h->a3_host = a3;
@@ -2561,6 +2588,59 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
   }
   if (!(h->theta == h->theta) || h->theta == 0.0 || !std::isfinite(h->theta))
     return fail(h, SDFS_ERR_ARG, "theta = (1-gamma)/(1-1/psi) is not finite / zero");
+  {
+    auto& S = h->sens;
+    S.gamma = params[S.ip_gamma]; S.psi = params[S.ip_psi]; S.mu_c = params[S.ip_mu_c];
+    S.sizes.assign(sizes, sizes + narrays);
+    S.hlam.assign(arrays[S.ia_hlam], arrays[S.ia_hlam] + sizes[S.ia_hlam]);
+    S.sigc.assign(arrays[S.ia_sigc], arrays[S.ia_sigc] + sizes[S.ia_sigc]);
+    S.z.assign(arrays[S.ia_z], arrays[S.ia_z] + sizes[S.ia_z]);
+  }
+  return 0;
+}
+
+// Log-tangents of the scale tables setup_model builds, along one direction (dparams, darrays) of (params, arrays):
+//   theta = (1 - gamma) / (1 - 1/psi),  a1 = exp(theta h_lam),  a2 = exp((1/2) ((1 - gamma) sigma_c)^2),
+//   a3 = exp((1 - gamma) (mu_c + z)),
+// so  dln a1 = dtheta h_lam + theta dh_lam,  dln a2 = (1 - gamma) sigma_c ((1 - gamma) dsigma_c - dgamma sigma_c),
+//     dln a3 = (1 - gamma) (dmu_c + dz) - dgamma (mu_c + z).
+// dln a3 lands in h->sens.dla3_host.  A non-zero tangent of a transition array is SDFS_ERR_UNSUPPORTED: the expectation
+// with a differentiated matrix is not among the kernels.  *need_jv: the J.v term is present (dtheta or dln a1 non-zero).
+int sens_tables(sdfs_handle* h, const double* dparams, const double* const* darrays, double* dtheta, double* dbeta,
+                SensTab& dla1, SensTab& dla2, bool* need_jv, bool* any_a3) {
+  auto& S = h->sens;
+  auto darr = [&](int i) -> const double* { return darrays ? darrays[i] : nullptr; };
+  for (int i : S.trans) {
+    const double* d = darr(i);
+    if (!d) continue;
+    for (long long k = 0; k < S.sizes[i]; ++k)
+      if (d[k] != 0.0) return fail(h, SDFS_ERR_UNSUPPORTED, "arrays[%d] is a transition array: its tangent must be zero "
+                                   "(persistence parameters are not supported)", i);
+  }
+  const double g = S.gamma, psi = S.psi, th = h->theta;
+  const double dg = dparams[S.ip_gamma], dpsi = dparams[S.ip_psi], dmu = dparams[S.ip_mu_c];
+  // dtheta/dgamma = -1 / (1 - 1/psi),  dtheta/dpsi = -theta / (psi (psi - 1))
+  *dtheta = -dg / (1.0 - 1.0 / psi) - dpsi * th / (psi * (psi - 1.0));
+  *dbeta = dparams[S.ip_beta];
+  const double* dhl = darr(S.ia_hlam);
+  const double* dsc = darr(S.ia_sigc);
+  const double* dz = darr(S.ia_z);
+  bool a1nz = false;
+  for (int i = 0; i < SENS_MAXN; ++i) { dla1.t[i] = 0.0; dla2.t[i] = 0.0; }
+  for (size_t l = 0; l < S.hlam.size(); ++l) {
+    dla1.t[l] = *dtheta * S.hlam[l] + (dhl ? th * dhl[l] : 0.0);
+    a1nz |= dla1.t[l] != 0.0;
+  }
+  for (size_t k = 0; k < S.sigc.size(); ++k)
+    dla2.t[k] = (1.0 - g) * S.sigc[k] * ((1.0 - g) * (dsc ? dsc[k] : 0.0) - dg * S.sigc[k]);
+  *any_a3 = dg != 0.0 || dmu != 0.0;
+  if (dz) for (size_t i = 0; i < S.z.size() && !*any_a3; ++i) *any_a3 = dz[i] != 0.0;
+  if (*any_a3) {
+    S.dla3_host.resize(S.z.size());
+    for (size_t i = 0; i < S.z.size(); ++i)
+      S.dla3_host[i] = (1.0 - g) * (dmu + (dz ? dz[i] : 0.0)) - dg * (S.mu_c + S.z[i]);
+  }
+  *need_jv = *dtheta != 0.0 || a1nz;
   return 0;
 }
 
@@ -3114,6 +3194,96 @@ int sdfs_apply_vjp(sdfs_handle* h, const double* w_host, const double* u_host, d
   if ((rc = sdfs_apply_vjp_dev(h, h->hostio2, h->hostio3, 0))) return rc;
   HIPCHK(h, hipMemcpyAsync(out_host, h->hostio3, nb, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int sdfs_param_tangent_dev(sdfs_handle* h, const double* w, const double* dparams, const double* const* darrays,
+                           double* out, double* Tw) {
+  int rc = check(h); if (rc) return rc;
+  if (!w || !out || !dparams) return fail(h, SDFS_ERR_ARG, "NULL argument");
+  if (h->cont || h->dense || h->sharded)
+    return fail(h, SDFS_ERR_UNSUPPORTED, "parameter tangents exist for unsharded discretised (multi-index) handles only");
+  double dtheta = 0.0, dbeta = 0.0;
+  SensTab dla1, dla2;
+  bool need_jv = false, any_a3 = false;
+  if ((rc = sens_tables(h, dparams, darrays, &dtheta, &dbeta, dla1, dla2, &need_jv, &any_a3))) return rc;
+  if (!Tw) { if ((rc = ensure_buf(h, &h->hostio3))) return rc; Tw = h->hostio3; }
+  if (need_jv && (rc = ensure_buf(h, &h->sens.v))) return rc;
+  if (any_a3) {
+    if (!h->sens.dla3 && (rc = dev_alloc(h, &h->sens.dla3, h->sens.z.size()))) return rc;
+    // (the previous call's epilogue may still read the table; its staging copy may still be in flight)
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->sens.dla3, h->sens.dla3_host.data(), sizeof(double) * h->sens.z.size(),
+                             hipMemcpyHostToDevice, h->stream));
+  }
+  // linearise at w (T w, and the cache of c1 / c2 the J.v below and a later sdfs_solve_linear_dev use)
+  if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, w, Tw, w, nullptr, nullptr, 0.0, 0))) return rc;
+  SensGeom g;
+  memset(&g, 0, sizeof g);
+  g.n = h->N; g.ndim = h->ndim;
+  for (int a = 0; a < h->ndim; ++a) { g.ext[a] = h->shape[a]; g.a3s[a] = h->sens.a3s[a]; }
+  const int grid = (int)std::min<long long>((h->N + SENS_BLOCK - 1) / SENS_BLOCK, (long long)h->num_cus * 16);
+  const double n8 = 8.0 * (double)h->N;
+  if (need_jv) {
+    g.ax_tab = h->sens.ax_a1;
+    { const int cid = h->profiling ? counter_id(h, "sens:prologue", 2 * n8, 0) : -1;
+      ProfScope ps(h, cid);
+      hipLaunchKernelGGL(k_sens_prologue, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, g, dla1, dtheta, w, h->sens.v);
+      HIPCHK(h, hipGetLastError()); }
+    if ((rc = run_plan(h, h->plan[0], MODE_JVP, true, true, h->sens.v, out, h->sens.v, nullptr, nullptr, 0.0, 0))) return rc;
+  }
+  g.ax_tab = h->sens.ax_a2;
+  {
+    const int cid = h->profiling ? counter_id(h, need_jv ? "sens:epilogue" : "sens:epilogue_nojv", (need_jv ? 3 : 2) * n8, 0) : -1;
+    ProfScope ps(h, cid);
+    hipLaunchKernelGGL(k_sens_epilogue, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, g, dla2, dbeta / h->beta, dtheta / h->theta,
+                       1.0 / h->beta, 1.0 / h->theta, (const double*)Tw, need_jv ? (const double*)out : nullptr,
+                       any_a3 ? (const double*)h->sens.dla3 : nullptr, out);
+    HIPCHK(h, hipGetLastError());
+  }
+  return 0;
+}
+
+int sdfs_solve_linear_dev(sdfs_handle* h, int transpose, const sdfs_opts* opts, const double* rhs, double* x,
+                          int64_t* n_iter, double* final_rel_resid) {
+  int rc = check(h); if (rc) return rc;
+  if (!rhs || !x) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
+  if (h->sharded) return fail(h, SDFS_ERR_UNSUPPORTED, "sharded handle: no single-handle linear solve");
+  if (!h->c1 || !h->c2) return fail(h, SDFS_ERR_ARG, "sdfs_solve_linear_dev before a linearisation (sdfs_linearize_dev, "
+                                    "sdfs_param_tangent_dev)");
+  if (transpose) {                         // where sdfs_apply_vjp_dev is unsupported (run_plan, MODE_VJP)
+    if (h->cont || h->dense) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product exists for the discretised operator only");
+    for (int a = 0; a < h->ndim; ++a)
+      if (!h->ax[a].Qt) return fail(h, SDFS_ERR_UNSUPPORTED, "the transposed solve needs unconditional transition tensors "
+                                    "(axis %s is conditional)", h->ax[a].name);
+  }
+  sdfs_opts o;
+  if (opts) o = *opts; else sdfs_default_opts(&o);
+  if (o.krylov_f32 != 0) return fail(h, SDFS_ERR_ARG, "sdfs_solve_linear_dev is fp64 only (opts.krylov_f32 = %d)", o.krylov_f32);
+  if ((rc = ensure_scalars(h))) return rc;
+  while (h->kry.size() < 7) { double* p = nullptr; if ((rc = dev_alloc(h, &p, (size_t)h->N))) return rc; h->kry.push_back(p); }
+  const long long n = h->N;
+  const int grid = (int)std::min<long long>((n + SENS_BLOCK - 1) / SENS_BLOCK, (long long)h->num_cus * 16);
+  // the loop solves (J - I) y = b: b = -rhs gives y = (I - J)^{-1} rhs
+  hipLaunchKernelGGL(k_sens_neg, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, rhs, h->kry[6], n);
+  HIPCHK(h, hipGetLastError());
+  const bool f32 = h->krylov_f32;
+  h->krylov_f32 = false;
+  int64_t mv = 0;
+  rc = bicgstab_dev_t<double>(h, o, &mv, transpose ? MODE_VJP : MODE_JVP);
+  h->krylov_f32 = f32;
+  if (rc) return rc;
+  HIPCHK(h, hipMemcpyAsync(x, h->kry[5], sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the loop's last read of the scalars preceded this copy)
+  const double rr = h->sc_host[SC_RR], bb = h->sc_host[SC_BB], a2 = h->sc_host[SC_ATOL2];
+  const long long its = (long long)h->sc_host[SC_ITERS];
+  const double rel = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+  if (n_iter) *n_iter = its;
+  if (final_rel_resid) *final_rel_resid = rel;
+  if (!(rr <= a2))
+    return fail(h, SDFS_ERR_NUMERIC, "%s BiCGSTAB stopped at relative residual %.3e after %lld iterations (%s)",
+                transpose ? "transposed" : "plain", rel, its,
+                h->sc_host[SC_BREAK] != 0.0 ? "breakdown" : (std::isfinite(rr) ? "not converged" : "non-finite residual"));
   return 0;
 }
 

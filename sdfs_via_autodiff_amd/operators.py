@@ -149,6 +149,76 @@ class KoopmansOperator:
     def vjp_dev(self, u_ptr, out_ptr, minus_identity=False):
         check(lib.sdfs_apply_vjp_dev(self._h, u_ptr, out_ptr, int(minus_identity)), self._h)
 
+    def _darrays(self, darrays):
+        """ctypes array of the narrays host pointers of a direction (None -> NULL), sizes checked against the arrays."""
+        if darrays is None:
+            return None, None
+        if len(darrays) != len(self._arrays):
+            raise ValueError(f"darrays has {len(darrays)} entries, the operator has {len(self._arrays)} arrays")
+        keep = []
+        for i, (d, a) in enumerate(zip(darrays, self._arrays)):
+            if d is None:
+                keep.append(None)
+                continue
+            d = _as_f64(d)
+            if d.size != a.size:
+                raise ValueError(f"darrays[{i}] has {d.size} elements, arrays[{i}] has {a.size}")
+            keep.append(d)
+        ptrs = (C.POINTER(C.c_double) * len(keep))(
+            *[d.ctypes.data_as(C.POINTER(C.c_double)) if d is not None else None for d in keep])
+        return ptrs, keep
+
+    def _dparams(self, dparams):
+        dparams = tuple(float(x) for x in dparams)
+        if len(dparams) != len(self.params):
+            raise ValueError(f"dparams has {len(dparams)} entries, the operator has {len(self.params)} parameters")
+        return (C.c_double * len(dparams))(*dparams)
+
+    def param_tangent_dev(self, w_ptr, dparams, darrays, out_ptr, Tw_ptr=None):
+        """out = dT(w)[dparams, darrays] on device pointers (sdfs_param_tangent_dev); linearises at w."""
+        dp = self._dparams(dparams)
+        ptrs, keep = self._darrays(darrays)
+        check(lib.sdfs_param_tangent_dev(self._h, w_ptr, dp, ptrs, out_ptr, Tw_ptr), self._h)
+        del keep
+
+    def solve_linear_dev(self, rhs_ptr, x_ptr, transpose=False, rtol=1e-10, atol=0.0, max_iter=0):
+        """x = (I - J)^{-1} rhs (transpose: (I - J^T)^{-1} rhs) at the cached linearisation (sdfs_solve_linear_dev).
+        Returns (iterations, relative residual)."""
+        o = _lib.default_opts()
+        o.inner_rtol, o.inner_atol, o.inner_max_iter = float(rtol), float(atol), int(max_iter)
+        it, rel = C.c_int64(), C.c_double()
+        check(lib.sdfs_solve_linear_dev(self._h, int(bool(transpose)), C.byref(o), rhs_ptr, x_ptr, C.byref(it),
+                                        C.byref(rel)), self._h)
+        return it.value, rel.value
+
+    def _to_dev(self, *arrays):
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = [torch.from_numpy(a).to(dev) for a in arrays]
+        torch.cuda.current_stream(dev).synchronize()       # (the library runs on its own stream)
+        return out
+
+    def param_tangent(self, w, dparams, darrays):
+        """dT(w)[dparams, darrays]: the tangent of T at a fixed w along one direction of (params, arrays), host
+        ndarrays in and out (``sensitivity.discretize_ssy_tangent`` / ``discretize_gcy_tangent`` make directions)."""
+        import torch
+        (wd,) = self._to_dev(self._host_in(w))
+        out = torch.empty_like(wd)
+        self.param_tangent_dev(wd.data_ptr(), dparams, darrays, out.data_ptr())
+        self.synchronize()
+        return out.cpu().numpy()
+
+    def solve_linear(self, w, rhs, transpose=False, rtol=1e-10, atol=0.0, max_iter=0):
+        """(I - J(w))^{-1} rhs, or (I - J(w)^T)^{-1} rhs with ``transpose``; host ndarrays in and out.  Raises
+        SdfsError if BiCGSTAB breaks down or stops above max(rtol |rhs|_2, atol)."""
+        import torch
+        wd, bd = self._to_dev(self._host_in(w), self._host_in(rhs, "rhs"))
+        x = torch.empty_like(wd)
+        self.linearize_dev(wd.data_ptr(), x.data_ptr())
+        self.solve_linear_dev(bd.data_ptr(), x.data_ptr(), transpose, rtol, atol, max_iter)
+        self.synchronize()
+        return x.cpu().numpy()
+
     def synchronize(self):
         check(lib.sdfs_synchronize(self._h), self._h)
 
