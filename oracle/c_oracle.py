@@ -55,7 +55,7 @@ def num_threads():
 
 
 class COperator:
-    """T(w) and jvp(w, v) through the C oracle, for model in {"ssy", "gcy"}."""
+    """T(w), jvp(w, v) and vjp(w, u) through the C oracle, for model in {"ssy", "gcy"}."""
 
     def __init__(self, model, shapes, params, arrays):
         self.shapes = tuple(int(s) for s in shapes)
@@ -118,3 +118,7 @@ class COperator:
 
     def jvp(self, w, v):
         return self._run(1, w, v)
+
+    def vjp(self, w, u):
+        """dT(w)^T[u] (mode 2: the adjoint contractions in the reverse axis order)."""
+        return self._run(2, w, u)

@@ -14,7 +14,8 @@ fastest in memory.  Conditional tensors (reference layout):
         Qhz[c,C] Qhc[d,D] Qhzpi[e,E] Qhl[f,F] a1[F] w[A,B,C,D,E,F]^theta )^(1/theta)
 
 Factorised order must respect the conditioning: (h_z, h_c, h_zpi, h_lam) any order,
-then z_pi (needs current h_zpi), then z (needs current z_pi, h_z, h_zpi).
+then z_pi (needs current h_zpi), then z (needs current z_pi, h_z, h_zpi).  ``vjp_gcy`` is the transpose of
+``jvp_gcy``: the adjoint contractions in the reverse order (z first, then z_pi, then the four unconditional axes).
 """
 import numpy as np
 
@@ -122,6 +123,19 @@ def expect_gcy(x, arrays_Q):
     return y
 
 
+def expect_gcy_T(y, arrays_Q):
+    """H0^T y: the adjoint of ``expect_gcy``, every contraction summed over its slice's row (current-state) index and
+    the axes in the reverse order -- z while z_pi, h_z and h_zpi are still current indices, then z_pi while h_zpi is."""
+    zQ, zpQ, Qhz, Qhc, Qhzp, Qhl = arrays_Q
+    x = np.einsum("bceaA,abcdef->Abcdef", zQ, y)
+    x = np.einsum("ebB,Abcdef->ABcdef", zpQ, x)
+    x = np.einsum("cC,ABcdef->ABCdef", Qhz, x)
+    x = np.einsum("dD,ABCdef->ABCDef", Qhc, x)
+    x = np.einsum("eE,ABCDef->ABCDEf", Qhzp, x)
+    x = np.einsum("fF,ABCDEf->ABCDEF", Qhl, x)
+    return x
+
+
 def kfactor_gcy(a2, a3):
     """K[a,b,c,d,e,f] = a2[d] * a3[b,c,e,a] broadcast over f."""
     a3t = np.transpose(a3, (3, 0, 1, 2))                    # [a, b, c, e]
@@ -145,3 +159,15 @@ def jvp_gcy(w, v, shapes, params, arrays):
     S = expect_gcy(a1 * w ** theta, Qs)
     dS = expect_gcy(a1 * w ** (theta - 1) * v, Qs)
     return beta * (K * S) ** (1 / theta - 1) * K * dS
+
+
+def vjp_gcy(w, u, shapes, params, arrays):
+    """dT(w)^T[u] = a1 w^(theta-1) * H0^T( beta (K S)^(1/theta - 1) K * u ),  S = H0(a1 w^theta)."""
+    beta, theta, a1, a2, a3, zQ, zpQ, Qhz, Qhc, Qhzp, Qhl = _pieces(params, arrays)
+    w = np.asarray(w, dtype=np.float64)
+    u = np.asarray(u, dtype=np.float64)
+    Qs = (zQ, zpQ, Qhz, Qhc, Qhzp, Qhl)
+    K = kfactor_gcy(a2, a3)
+    S = expect_gcy(a1 * w ** theta, Qs)
+    y = beta * (K * S) ** (1 / theta - 1) * K * u
+    return a1 * w ** (theta - 1) * expect_gcy_T(y, Qs)

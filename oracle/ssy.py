@@ -15,7 +15,8 @@ State order (h_lam, h_c, h_z, z) = indices (l, k, i, j), z fastest in memory.
 ``T_ssy_factorised`` evaluates the same sum axis by axis (legal order: h_z before
 z because zQ is conditioned on the *current* h_z index).  ``jvp_ssy`` is the
 analytic directional derivative; the reference documents the same Jacobian in
-dense form at code/ssy/discrete/temp_ssy.py:204-216.
+dense form at code/ssy/discrete/temp_ssy.py:204-216.  ``vjp_ssy`` is its transpose, dT(w)^T[u], written
+from the same definition (the adjoint of each axis's contraction, in the reverse order).
 """
 import numpy as np
 
@@ -96,6 +97,18 @@ def expect_ssy(x, arrays_Q):
     return y
 
 
+def expect_ssy_T(y, arrays_Q):
+    """H0^T y: the adjoint of ``expect_ssy``.  Each axis's contraction is transposed -- the sum runs over the row
+    (current-state) index of every slice -- and the axes are taken in the reverse of ``expect_ssy``'s order, so the
+    conditioning index of zQ is still the current h_z index when z is contracted."""
+    Ql, Qc, Qz, zQ = arrays_Q
+    x = np.einsum("lL,lkij->Lkij", Ql, y)      # h_lam
+    x = np.einsum("kK,Lkij->LKij", Qc, x)      # h_c
+    x = np.einsum("ijJ,LKij->LKiJ", zQ, x)     # z, conditioned on current h_z
+    x = np.einsum("iI,LKiJ->LKIJ", Qz, x)      # h_z last
+    return x
+
+
 def T_ssy_factorised(w, shapes, params, arrays):
     beta, theta, a1, a2, a3, Ql, Qc, Qz, zQ = _pieces(params, arrays)
     w = np.asarray(w, dtype=np.float64)
@@ -115,3 +128,15 @@ def jvp_ssy(w, v, shapes, params, arrays):
     S = expect_ssy(A1 * w ** theta, (Ql, Qc, Qz, zQ))
     dS = expect_ssy(A1 * w ** (theta - 1) * v, (Ql, Qc, Qz, zQ))
     return beta * (K * S) ** (1 / theta - 1) * K * dS
+
+
+def vjp_ssy(w, u, shapes, params, arrays):
+    """dT(w)^T[u] = a1 w^(theta-1) * H0^T( beta (K S)^(1/theta - 1) K * u ),  S = H0(a1 w^theta)."""
+    beta, theta, a1, a2, a3, Ql, Qc, Qz, zQ = _pieces(params, arrays)
+    w = np.asarray(w, dtype=np.float64)
+    u = np.asarray(u, dtype=np.float64)
+    A1 = a1[:, None, None, None]
+    K = a2[None, :, None, None] * a3[None, None, :, :]
+    S = expect_ssy(A1 * w ** theta, (Ql, Qc, Qz, zQ))
+    y = beta * (K * S) ** (1 / theta - 1) * K * u
+    return A1 * w ** (theta - 1) * expect_ssy_T(y, (Ql, Qc, Qz, zQ))
