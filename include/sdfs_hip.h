@@ -203,6 +203,34 @@ int sdfs_param_tangent_dev(sdfs_handle* h, const double* w_dev, const double* dp
 int sdfs_solve_linear_dev(sdfs_handle* h, int transpose, const sdfs_opts* opts, const double* rhs_dev, double* x_dev,
                           int64_t* n_iter, double* final_rel_resid);
 
+/* Asset pricing with the SDF M' = beta^theta exp(theta g_lam' - gamma g_c') (w(X') / (w(X) - 1))^(theta-1) at w.  For a power
+ * p in {0, 1, 2} of the SDF and exponents (kappa_lam, kappa_c) the tilted expectation is
+ *   K f (x) = [beta^theta (Tw(x) - 1)^(1-theta)]^p E_x[exp(kappa_lam g_lam' + kappa_c g_c') w(X')^(p (theta-1)) f(X')]
+ *           = d2 .* H'(d1 .* f),   d1 = c1^p e_lam,  d2 = c2^p e_c e_z
+ * with (c1, c2) the linearisation at w: (1, theta, 1 - gamma) is J(w) bit for bit; (1, theta, -gamma) gives E_x[M] = K 1,
+ * (2, 2 theta, -2 gamma) E_x[M^2], (1, theta, kappa - gamma) the price operator of a claim on G_c^kappa, (0, 0, kappa)
+ * the physical E_x[G_c^kappa f].  Discretised unsharded handles only (SDFS_ERR_UNSUPPORTED otherwise); fp64 whatever
+ * fp32 solve options the handle has run with.
+ *
+ * sdfs_set_tilt_dev linearises at w (fp64; replaces the cached linearisation, as sdfs_param_tangent_dev does; w may be
+ * NULL when sdf_power = 0, and then nothing is linearised) and forms d1, d2.  The later calls use them and leave the
+ * cached linearisation untouched; before a set_tilt they are SDFS_ERR_ARG, as is sdf_power outside {0, 1, 2}. */
+int sdfs_set_tilt_dev(sdfs_handle* h, const double* w_dev, int sdf_power, double kappa_lam, double kappa_c);
+/* out = K f (device pointers, N doubles each, distinct). */
+int sdfs_apply_tilted_dev(sdfs_handle* h, const double* f_dev, double* out_dev);
+/* x = (I - K)^{-1} rhs by the device BiCGSTAB (the stopping rule and opts of sdfs_solve_linear_dev; opts.krylov_f32 is
+ * ignored: fp64).  SDFS_ERR_NUMERIC for a breakdown or a solve that stops above the tolerance. */
+int sdfs_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const double* rhs_dev, double* x_dev,
+                          int64_t* n_iter, double* final_rel_resid);
+/* P_0 = 1, P_n = K P_{n-1} for n = 1 ... n_max on the device, no host synchronisation per horizon.  Row n-1 of out_host
+ * (n_max x 4) = <g, P_n>, <g, -log P_n> / n, min and max of P_n / P_{n-1} over the grid (the Collatz-Wielandt bracket of
+ * the spectral radius of K), with product-form weights g(x) = prod_a weight_axes[a][x_a] (HOST pointers, shapes[a]
+ * doubles each; weight_axes NULL, or an entry NULL: uniform 1 / shapes[a]).  P_n is copied to save_dev[j] (device, N
+ * doubles) at the horizons save_at[j] (strictly rising within 1 ... n_max).  The sums are finished in a fixed order: two
+ * runs give identical bits.  SDFS_ERR_NUMERIC (results written) if some P_n is not strictly positive. */
+int sdfs_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* const* weight_axes, int64_t n_save,
+                             const int64_t* save_at, double* const* save_dev, double* out_host);
+
 /* max|T(w) - w| of the most recent apply that computed it. */
 int sdfs_residual(sdfs_handle* h, double* sup_norm);
 

@@ -30,6 +30,7 @@
 #include "vec_kernels.hpp"
 #include "krylov_kernels.hpp"
 #include "sens_kernels.hpp"
+#include "price_kernels.hpp"
 
 using namespace sdfs;
 
@@ -189,6 +190,18 @@ struct sdfs_handle {
     double* dla3 = nullptr;                                   // device copy
     double* v = nullptr;                                      // J.v direction of the tangent
   } sens;
+
+  // tilted expectation K (sdfs_set_tilt_dev): its scalings d1 / d2 stand in for c1 / c2 in the J.v kernels; they never
+  // replace the cached linearisation, and Newton's fused forms and the captured graphs never see them
+  struct {
+    int power = -1;                                           // -1: no tilt set
+    double* d1 = nullptr; double* d2 = nullptr;               // next-state / current-state scalings
+    std::vector<double> ez_host;                              // staging of the e_z table (kept alive across the async copy)
+    double* ez = nullptr;                                     // device copy
+    double* pa = nullptr; double* pb = nullptr;               // P_n ping-pong of the horizon loop
+    double* part = nullptr;                                   // per-workgroup partials of one horizon
+    double* res = nullptr; long long res_cap = 0;             // PRICE_NSUM doubles per horizon
+  } price;
 
   // Newton-Krylov with fp32 Krylov vectors / J.v streams (opts.krylov_f32); set while such a solve runs
   bool krylov_f32 = false;
@@ -1221,9 +1234,12 @@ int round_stream_bf16(sdfs_handle* h, void* p, const unsigned long long* gate) {
 // stage 0 holds the first pass, stage 1 the last); nloc = grid points of the block
 int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, bool has_last, int mode, const double* in, double* out,
                   const double* old, unsigned long long* resid, const unsigned long long* gate, double gate_tol, int minus_identity,
-                  double* dotp) {
+                  double* dotp, const double* lc1 = nullptr, const double* lc2 = nullptr) {
   const bool vjp = mode == MODE_VJP;       // the J.v launches with transposed matrices and c1 / c2 swapped (fp64)
   if (vjp) mode = MODE_JVP;
+  // J.v scalings: the cached linearisation, or the caller's (lc1, lc2: the tilted expectation's d1 / d2)
+  const double* const C1 = lc1 ? lc1 : h->c1;
+  const double* const C2 = lc2 ? lc2 : h->c2;
   int rc = ensure_tmp(h);
   if (rc) return rc;
   if (mode != MODE_T) { rc = ensure_lin(h); if (rc) return rc; }
@@ -1256,7 +1272,7 @@ int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, 
         io.zero = (mode != MODE_JVP) ? resid : nullptr;
         int sm = S_TFIRST;
         if (mode == MODE_T_LIN) { sm = S_TFIRST_LIN; io.aux_out = h->c1; bytes += n8; }
-        else if (mode == MODE_JVP) { sm = S_JFIRST; io.aux_in = vjp ? h->c2 : h->c1; bytes += n8; }
+        else if (mode == MODE_JVP) { sm = S_JFIRST; io.aux_in = vjp ? C2 : C1; bytes += n8; }
         if (h->profiling) { char nm[48]; snprintf(nm, sizeof nm, "%s:%s", tag, P.label.c_str()); cid = counter_id(h, nm, bytes, P.flops); }
         const long long ntile = (d.nslices + pad_slice_g(P.nt) - 1) / pad_slice_g(P.nt);
         ProfScope ps(h, cid);
@@ -1269,7 +1285,7 @@ int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, 
         if (last) {
           if (mode == MODE_T) { lm = L_TLAST; io.old = old; io.resid = resid; if (resid) bytes += n8; }
           else if (mode == MODE_T_LIN) { lm = L_TLAST_LIN; io.old = old; io.resid = resid; io.aux_out = h->c2; bytes += n8; if (resid) bytes += n8; }
-          else { lm = L_JLAST; io.aux_in = vjp ? h->c1 : h->c2; io.old = old; bytes += n8; if (minus_identity) { bytes += n8; io.dotp = dotp; } }
+          else { lm = L_JLAST; io.aux_in = vjp ? C1 : C2; io.old = old; bytes += n8; if (minus_identity) { bytes += n8; io.dotp = dotp; } }
         }
         if (h->profiling) { char nm[48]; snprintf(nm, sizeof nm, "%s:%s", tag, P.label.c_str()); cid = counter_id(h, nm, bytes, P.flops); }
         ProfScope ps(h, cid);
@@ -1287,12 +1303,12 @@ int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, 
         io.zero = (mode != MODE_JVP) ? resid : nullptr;
         if (mode == MODE_T) sm = SM_FIRST_T;
         else if (mode == MODE_T_LIN) { sm = SM_FIRST_TLIN; io.aux_out = h->c1; bytes += n8; }
-        else { sm = SM_FIRST_J; io.aux_in = vjp ? h->c2 : h->c1; bytes += n8; }
+        else { sm = SM_FIRST_J; io.aux_in = vjp ? C2 : C1; bytes += n8; }
       } else if (last) {
         if (mode == MODE_T) { sm = SM_LAST_T; io.old = old; io.resid = resid; if (resid) bytes += n8; }
         else if (mode == MODE_T_LIN) { sm = SM_LAST_TLIN; io.old = old; io.resid = resid; io.aux_out = h->c2; bytes += n8; if (resid) bytes += n8; }
         else {
-          sm = SM_LAST_J; io.aux_in = vjp ? h->c1 : h->c2; io.old = old; bytes += n8;
+          sm = SM_LAST_J; io.aux_in = vjp ? C1 : C2; io.old = old; bytes += n8;
           if (minus_identity) { bytes += n8; io.dotp = dotp; }
           if (dotp && h->jvp_dot_with) { io.dot_with = h->jvp_dot_with; bytes += n8; }
         }
@@ -1311,11 +1327,12 @@ int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, 
       int sm = S_TFIRST;
       if (t32) { sm = S_TFIRST32; bytes -= 0.5 * n8; }
       if (mode == MODE_T_LIN) { sm = S_TFIRST_LIN; io.aux_out = h->c1; bytes += n8; }
-      else if (mode == MODE_JVP) { sm = S_JFIRST; io.aux_in = vjp ? h->c2 : h->c1; bytes += n8; }
+      else if (mode == MODE_JVP) { sm = S_JFIRST; io.aux_in = vjp ? C2 : C1; bytes += n8; }
       SliceDesc sd = P.sd;
       if (vjp) { sd.Qf = h->ax[P.ax1].Qt; sd.Qe = h->ax[P.ax0].Qt; }
       if (h->sharded) sd.t32_ref = h->t32_ref;
       if (mode == MODE_JVP && !vjp && !f32 && h->jf.active && h->jf.kind >= 0) {
+        if (lc1) return fail(h, SDFS_ERR_ARG, "the fused BiCGSTAB first pass reads the cached linearisation only");
         // BiCGSTAB's p / s update on the registers of this pass (krylov_kernels.hpp)
         jfused_fn jfn = slice_jfused_variant(P.n, h->jf.kind);
         if (!jfn) return fail(h, SDFS_ERR_UNSUPPORTED, "no fused first pass for this extent");
@@ -1375,7 +1392,7 @@ int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, 
       if (last) {
         if (mode == MODE_T) { lm = L_TLAST; io.old = old; io.resid = resid; if (resid) bytes += n8; }
         else if (mode == MODE_T_LIN) { lm = L_TLAST_LIN; io.old = old; io.resid = resid; io.aux_out = h->c2; bytes += n8; if (resid) bytes += n8; }
-        else { lm = L_JLAST; io.aux_in = vjp ? h->c1 : h->c2; io.old = old; bytes += n8; if (minus_identity) { bytes += n8; io.dotp = dotp; } }
+        else { lm = L_JLAST; io.aux_in = vjp ? C1 : C2; io.old = old; bytes += n8; if (minus_identity) { bytes += n8; io.dotp = dotp; } }
       }
       const bool lf32 = f32 && (mode == MODE_JVP || lm == L_TLAST_LIN);
       line_fn fn = lf32 ? line_variant(P.n, lm, false, true, true) : line_variant(P.n, lm, P.persist, P.ld.lrest % LINE_R == 0);
@@ -1465,7 +1482,8 @@ long long jvp_last_tiles(sdfs_handle* h) {
 
 int run_plan(sdfs_handle* h, Plan& plan, int mode, bool has_first, bool has_last,
              const double* in, double* out, const double* old, unsigned long long* resid,
-             const unsigned long long* gate, double gate_tol, int minus_identity, double* dotp = nullptr) {
+             const unsigned long long* gate, double gate_tol, int minus_identity, double* dotp = nullptr,
+             const double* lc1 = nullptr, const double* lc2 = nullptr) {
   if (mode == MODE_VJP) {
     if (h->cont || h->dense) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product exists for the discretised operator only");
     for (int a = 0; a < h->ndim; ++a)
@@ -1477,13 +1495,15 @@ int run_plan(sdfs_handle* h, Plan& plan, int mode, bool has_first, bool has_last
   // the pair plan serves the whole-grid operator; its fp32-storage forms need whole 16-element chunks in
   // every line pass, otherwise fp32 Krylov storage (and its linearisation) stays on the generic kernels
   if (h->fast.ok && &plan == &h->plan[0] && has_first && has_last && !(h->krylov_f32 && mode != MODE_T && !h->fast.f32_ok))
-    return run_fast_plan(h, h->fast, h->N, true, true, mode, in, out, old, resid, gate, gate_tol, minus_identity, dotp);
+    return run_fast_plan(h, h->fast, h->N, true, true, mode, in, out, old, resid, gate, gate_tol, minus_identity, dotp, lc1, lc2);
   // sharded stages on the pair plan's kernels (fp64 streams)
   if (h->sharded && (&plan == &h->plan[0] || &plan == &h->plan[1]) && h->sfast[&plan - h->plan].ok && mode != MODE_VJP &&
       !(h->krylov_f32 && mode != MODE_T) && has_first == (&plan == &h->plan[0]) && has_last == (&plan == &h->plan[1]))
     return run_fast_plan(h, h->sfast[&plan - h->plan], plan.nloc, has_first, has_last, mode, in, out, old, resid, gate, gate_tol, minus_identity, dotp);
   const bool vjp = mode == MODE_VJP;       // the J.v launches with transposed matrices and c1 / c2 swapped
   if (vjp) mode = MODE_JVP;
+  const double* const C1 = lc1 ? lc1 : h->c1;   // (lc1, lc2: the caller's J.v scalings, see run_fast_plan)
+  const double* const C2 = lc2 ? lc2 : h->c2;
   int rc = ensure_tmp(h);
   if (rc) return rc;
   if (mode != MODE_T) { rc = ensure_lin(h); if (rc) return rc; }
@@ -1502,7 +1522,7 @@ int run_plan(sdfs_handle* h, Plan& plan, int mode, bool has_first, bool has_last
     if (first) {
       if (mode == MODE_T) pro = PRO_POW;
       else if (mode == MODE_T_LIN) { pro = PRO_POW_LIN; io.aux_out = h->c1; bytes += n8; }
-      else { pro = PRO_MUL; io.aux_in = vjp ? h->c2 : h->c1; bytes += n8; }
+      else { pro = PRO_MUL; io.aux_in = vjp ? C2 : C1; bytes += n8; }
     }
     if (last) {
       if (mode == MODE_T) { epi = EPI_CES; io.old = old; io.resid = resid; if (resid) bytes += n8; }
@@ -1515,7 +1535,7 @@ int run_plan(sdfs_handle* h, Plan& plan, int mode, bool has_first, bool has_last
       } else {
         epi = EPI_MUL; bytes += n8;
         if (first) return fail(h, SDFS_ERR_UNSUPPORTED, "single-pass JVP not supported");
-        io.aux_in = vjp ? h->c1 : h->c2; io.old = old; if (minus_identity) bytes += n8;
+        io.aux_in = vjp ? C1 : C2; io.old = old; if (minus_identity) bytes += n8;
         if (minus_identity) io.dotp = dotp;
       }
     }
@@ -1821,10 +1841,13 @@ int solve_sa(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int
 // occupy the first half of the same allocations and the J.v kernels read / write fp32, see run_plan)
 // mode = the matvec: MODE_JVP solves (J - I) x = b, MODE_VJP (fp64 only) solves (J^T - I) x = b.  The fused forms below
 // (dot products in the last J.v pass, the merged small-grid loop, the slice_jfused updates, the captured graph) are
-// J.v-only: the transposed solve runs the plain iteration.
+// J.v-only: the transposed solve runs the plain iteration.  lc1 / lc2 (fp64 MODE_JVP only): the J.v scalings to use in
+// place of the cached c1 / c2 (the tilted expectation, sdfs_solve_tilted_dev); they too run the plain iteration.
 template <typename T>
-int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mode = MODE_JVP) {
+int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mode = MODE_JVP,
+                   const double* lc1 = nullptr, const double* lc2 = nullptr) {
   const bool vjp = mode == MODE_VJP;
+  const bool plain = vjp || lc1 != nullptr;     // only the plain iteration takes explicit scalings
   T *r = (T*)h->kry[0], *rhat = (T*)h->kry[1], *p = (T*)h->kry[2], *q = (T*)h->kry[3], *t = (T*)h->kry[4],
     *x = (T*)h->kry[5];
   const double* b = h->kry[6];
@@ -1850,7 +1873,7 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
   const long long maxit = o.inner_max_iter > 0 ? o.inner_max_iter : 10 * n;
   // <t, s> and <t, t> come out of the last J.v pass when its tiles fit the partial-sum buffer
   const long long last_tiles = jvp_last_tiles(h);
-  const bool fused_dots = !vjp && last_tiles > 0 && 2 * last_tiles <= (long long)MAX_PARTIAL_BLOCKS * AND_MAX_M &&
+  const bool fused_dots = !plain && last_tiles > 0 && 2 * last_tiles <= (long long)MAX_PARTIAL_BLOCKS * AND_MAX_M &&
                           (h->plan[0].passes.size() > 1 || (h->fast.ok && (!h->krylov_f32 || h->fast.f32_ok))) && h->knobs.no_dot_fusion == 0 &&
                           !h->krylov_bf16;      // (the fused sums would see the J.v output before its rounding)
   // small grids are launch-bound: the finishing kernels merge into the vector kernels behind them (vec_kernels.hpp),
@@ -1860,7 +1883,7 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
   double* const pss = h->partial + PR;          // <s, s>
   double* const pt = h->partial + 2 * PR;       // <t, s>, <t, t>
   double* const prr = h->partial + 4 * PR;      // <r, r>, <rhat, r>
-  const bool merged = !vjp && n <= (1LL << 22) && (!fused_dots || last_tiles <= MAX_PARTIAL_BLOCKS) && h->knobs.no_bicg_merge == 0;
+  const bool merged = !plain && n <= (1LL << 22) && (!fused_dots || last_tiles <= MAX_PARTIAL_BLOCKS) && h->knobs.no_bicg_merge == 0;
   auto iteration_merged = [&]() -> int {
     int rc2;
     { ProfScope ps(h, cvec);
@@ -1888,14 +1911,15 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
     int rc2;
     { ProfScope ps(h, cvec);
       hipLaunchKernelGGL(k_bicg_update_p<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)r, p, (const T*)q, n, h->sc, (const unsigned long long*)gate); }
-    if ((rc2 = run_plan(h, h->plan[0], mode, true, true, (const double*)p, (double*)q, (const double*)p, nullptr, gate, 0.0, 1))) return rc2;
+    if ((rc2 = run_plan(h, h->plan[0], mode, true, true, (const double*)p, (double*)q, (const double*)p, nullptr, gate, 0.0, 1,
+                        nullptr, lc1, lc2))) return rc2;
     { ProfScope ps(h, cvec);
       hipLaunchKernelGGL(k_dot<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)rhat, (const T*)q, n, h->partial, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_alpha_finish, dim3(1), dim3(VEC_BLOCK), 0, st, h->partial, g, h->sc, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_s<T>, dim3(g), dim3(VEC_BLOCK), 0, st, r, (const T*)q, n, h->sc, h->partial, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_s_finish, dim3(1), dim3(VEC_BLOCK), 0, st, h->partial, g, h->sc, (const unsigned long long*)gate); }
     if ((rc2 = run_plan(h, h->plan[0], mode, true, true, (const double*)r, (double*)t, (const double*)r, nullptr, gate, 0.0, 1,
-                        fused_dots ? h->partial : nullptr))) return rc2;
+                        fused_dots ? h->partial : nullptr, lc1, lc2))) return rc2;
     { ProfScope ps(h, cvec);
       if (!fused_dots) hipLaunchKernelGGL(k_dot2<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)t, (const T*)r, n, h->partial, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_omega_finish, dim3(1), dim3(VEC_BLOCK), 0, st, h->partial, fused_dots ? (int)last_tiles : g, h->sc, (const unsigned long long*)gate);
@@ -1913,7 +1937,7 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
 #else
   const bool jf32 = std::is_same<T, float>::value && h->krylov_f32 && h->krylov_mfma32 && !h->krylov_bf16 && h->fast.f32_ok;
 #endif
-  bool jfuse = !vjp && ((std::is_same<T, double>::value && !h->krylov_f32) || jf32) && !merged && h->fast.ok && !h->fast.small && !h->fast.pad &&
+  bool jfuse = !plain && ((std::is_same<T, double>::value && !h->krylov_f32) || jf32) && !merged && h->fast.ok && !h->fast.small && !h->fast.pad &&
                h->fast.passes.size() >= 2 && !P0->line && !P0->pad && PL->line && PL->ld.lrest % LINE_R == 0 && h->knobs.no_dot_fusion == 0;
   // workgroups of the last pass (one partial sum each per inner product), wave tiles of the first
   const long long jf_last = jfuse ? (jf32 ? PL->ld.ntiles * LINE_R / line32_row_floats(PL->n, PL->ld.lrest) : PL->ld.ntiles) : 0;
@@ -1969,7 +1993,7 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
   // breakdown / convergence test for long.
   const int chunk = (int)std::min<long long>(maxit, n <= (1LL << 22) ? 8 : 1);
   const int gslot = std::is_same<T, float>::value ? 1 : 0;
-  const bool graph = !vjp && o.use_graph && !h->profiling && st != nullptr && chunk > 1 && !std::is_same<T, bf16r>::value;
+  const bool graph = !plain && o.use_graph && !h->profiling && st != nullptr && chunk > 1 && !std::is_same<T, bf16r>::value;
   if (graph && (h->bicg_graph[gslot] == nullptr || h->bicg_graph_chunk[gslot] != chunk)) {
     if (h->bicg_graph[gslot]) { hipGraphExecDestroy(h->bicg_graph[gslot]); h->bicg_graph[gslot] = nullptr; }
     hipGraph_t gr = nullptr;
@@ -3066,6 +3090,7 @@ void sdfs_destroy(sdfs_handle* h) {
   if (h->and_err_host) { hipHostFree(h->and_err_host); hipHostFree(h->and_kind_host); }
   for (int i = 0; i < 2; ++i) if (h->bicg_graph[i]) hipGraphExecDestroy(h->bicg_graph[i]);
   for (double* p : h->dev_allocs) hipFree(p);
+  if (h->price.res) hipFree(h->price.res);
   for (void* p : h->misc_allocs) hipFree(p);
   if (h->slots) hipFree(h->slots);
   if (h->slots_host) hipHostFree(h->slots_host);
@@ -3244,6 +3269,40 @@ int sdfs_param_tangent_dev(sdfs_handle* h, const double* w, const double* dparam
   return 0;
 }
 
+namespace {
+// x = (I - A)^{-1} rhs with the fp64 device BiCGSTAB, A = J (MODE_JVP), J^T (MODE_VJP) or, with (lc1, lc2), the J.v
+// kernels on those scalings.  Runs on fp64 storage whatever fp32 settings the handle carries, and restores them.
+int linear_solve(sdfs_handle* h, const sdfs_opts& o, int mode, const double* rhs, double* x, int64_t* n_iter,
+                 double* final_rel_resid, const double* lc1, const double* lc2, const char* what) {
+  int rc;
+  if ((rc = ensure_scalars(h))) return rc;
+  while (h->kry.size() < 7) { double* p = nullptr; if ((rc = dev_alloc(h, &p, (size_t)h->N))) return rc; h->kry.push_back(p); }
+  const long long n = h->N;
+  const int grid = (int)std::min<long long>((n + SENS_BLOCK - 1) / SENS_BLOCK, (long long)h->num_cus * 16);
+  // the loop solves (A - I) y = b: b = -rhs gives y = (I - A)^{-1} rhs
+  hipLaunchKernelGGL(k_sens_neg, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, rhs, h->kry[6], n);
+  HIPCHK(h, hipGetLastError());
+  const bool f32 = h->krylov_f32;
+  h->krylov_f32 = false;
+  int64_t mv = 0;
+  rc = bicgstab_dev_t<double>(h, o, &mv, mode, lc1, lc2);
+  h->krylov_f32 = f32;
+  if (rc) return rc;
+  HIPCHK(h, hipMemcpyAsync(x, h->kry[5], sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the loop's last read of the scalars preceded this copy)
+  const double rr = h->sc_host[SC_RR], bb = h->sc_host[SC_BB], a2 = h->sc_host[SC_ATOL2];
+  const long long its = (long long)h->sc_host[SC_ITERS];
+  const double rel = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+  if (n_iter) *n_iter = its;
+  if (final_rel_resid) *final_rel_resid = rel;
+  if (!(rr <= a2))
+    return fail(h, SDFS_ERR_NUMERIC, "%s BiCGSTAB stopped at relative residual %.3e after %lld iterations (%s)",
+                what, rel, its,
+                h->sc_host[SC_BREAK] != 0.0 ? "breakdown" : (std::isfinite(rr) ? "not converged" : "non-finite residual"));
+  return 0;
+}
+}  // namespace
+
 int sdfs_solve_linear_dev(sdfs_handle* h, int transpose, const sdfs_opts* opts, const double* rhs, double* x,
                           int64_t* n_iter, double* final_rel_resid) {
   int rc = check(h); if (rc) return rc;
@@ -3260,30 +3319,191 @@ int sdfs_solve_linear_dev(sdfs_handle* h, int transpose, const sdfs_opts* opts, 
   sdfs_opts o;
   if (opts) o = *opts; else sdfs_default_opts(&o);
   if (o.krylov_f32 != 0) return fail(h, SDFS_ERR_ARG, "sdfs_solve_linear_dev is fp64 only (opts.krylov_f32 = %d)", o.krylov_f32);
-  if ((rc = ensure_scalars(h))) return rc;
-  while (h->kry.size() < 7) { double* p = nullptr; if ((rc = dev_alloc(h, &p, (size_t)h->N))) return rc; h->kry.push_back(p); }
-  const long long n = h->N;
-  const int grid = (int)std::min<long long>((n + SENS_BLOCK - 1) / SENS_BLOCK, (long long)h->num_cus * 16);
-  // the loop solves (J - I) y = b: b = -rhs gives y = (I - J)^{-1} rhs
-  hipLaunchKernelGGL(k_sens_neg, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, rhs, h->kry[6], n);
+  return linear_solve(h, o, transpose ? MODE_VJP : MODE_JVP, rhs, x, n_iter, final_rel_resid, nullptr, nullptr,
+                      transpose ? "transposed" : "plain");
+}
+
+namespace {
+PriceGeom price_geom(const sdfs_handle* h) {
+  PriceGeom g;
+  memset(&g, 0, sizeof g);
+  g.n = h->N; g.ndim = h->ndim;
+  for (int a = 0; a < h->ndim; ++a) { g.ext[a] = price_div((unsigned)h->shape[a]); g.a3s[a] = h->sens.a3s[a]; }
+  g.ax_lam = h->sens.ax_a1; g.ax_c = h->sens.ax_a2;
+  return g;
+}
+
+// Pricing is fp64 end to end: the fp32 settings a handle may carry are off while a pricing call runs, then restored.
+struct Fp64Scope {
+  sdfs_handle* h;
+  bool kf32, kbf16, kmfma, t32;
+  explicit Fp64Scope(sdfs_handle* hh) : h(hh), kf32(hh->krylov_f32), kbf16(hh->krylov_bf16), kmfma(hh->krylov_mfma32), t32(hh->t32_active) {
+    h->krylov_f32 = h->krylov_bf16 = h->krylov_mfma32 = h->t32_active = false;
+  }
+  ~Fp64Scope() { h->krylov_f32 = kf32; h->krylov_bf16 = kbf16; h->krylov_mfma32 = kmfma; h->t32_active = t32; }
+};
+
+int price_handle_ok(sdfs_handle* h, const char* fn, bool need_tilt) {
+  if (h->cont || h->dense || h->sharded)
+    return fail(h, SDFS_ERR_UNSUPPORTED, "%s: pricing exists for unsharded discretised (multi-index) handles only", fn);
+  if (need_tilt && h->price.power < 0) return fail(h, SDFS_ERR_ARG, "%s before sdfs_set_tilt_dev", fn);
+  return 0;
+}
+
+int price_grid(const sdfs_handle* h) {
+  return (int)std::max<long long>(1, std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK,
+                                                         std::min<long long>((long long)h->num_cus * 8, PRICE_MAX_BLOCKS)));
+}
+}  // namespace
+
+int sdfs_set_tilt_dev(sdfs_handle* h, const double* w, int sdf_power, double kappa_lam, double kappa_c) {
+  int rc = check(h); if (rc) return rc;
+  if ((rc = price_handle_ok(h, "sdfs_set_tilt_dev", false))) return rc;
+  if (sdf_power < 0 || sdf_power > 2) return fail(h, SDFS_ERR_ARG, "sdf_power = %d: 0, 1 or 2", sdf_power);
+  if (sdf_power > 0 && !w) return fail(h, SDFS_ERR_ARG, "sdf_power = %d needs the linearisation point w", sdf_power);
+  if (!std::isfinite(kappa_lam) || !std::isfinite(kappa_c)) return fail(h, SDFS_ERR_ARG, "non-finite tilt exponent");
+  auto& S = h->sens;
+  auto& Pr = h->price;
+  Pr.power = -1;                           // (until the scalings below are in place)
+  // e_lam = exp((kappa_lam - theta) h_lam), e_c = exp((1/2)(kappa_c^2 - (1-gamma)^2) sigma_c^2),
+  // e_z = exp((kappa_c - (1-gamma)) (mu_c + z)); every exponent is exactly 0 at (kappa_lam, kappa_c) = (theta, 1 - gamma).
+  // Where a3 is a table the aggregator applies (h->a3), the J.v passes leave it out and the cached c2 carries it
+  // (c2 = beta u / S with S unscaled): e_z then also replaces c2^p's a3^p by the a3 of H', exponent kappa_c - p (1-gamma).
+  const double og = 1.0 - S.gamma;
+  const double xl = kappa_lam - h->theta, xc = 0.5 * (kappa_c * kappa_c - og * og);
+  const double xz = h->a3 ? kappa_c - sdf_power * og : kappa_c - og;
+  SensTab el, ec;
+  for (int i = 0; i < SENS_MAXN; ++i) { el.t[i] = 1.0; ec.t[i] = 1.0; }
+  for (size_t l = 0; l < S.hlam.size(); ++l) el.t[l] = std::exp(xl * S.hlam[l]);
+  for (size_t k = 0; k < S.sigc.size(); ++k) ec.t[k] = std::exp(xc * S.sigc[k] * S.sigc[k]);
+  if ((rc = ensure_buf(h, &Pr.d1)) || (rc = ensure_buf(h, &Pr.d2))) return rc;
+  if (xz != 0.0) {
+    if (!Pr.ez && (rc = dev_alloc(h, &Pr.ez, S.z.size()))) return rc;
+    // (the previous call's scaling pass may still read the table; its staging copy may still be in flight)
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    Pr.ez_host.resize(S.z.size());
+    for (size_t i = 0; i < S.z.size(); ++i) Pr.ez_host[i] = std::exp(xz * (S.mu_c + S.z[i]));
+    HIPCHK(h, hipMemcpyAsync(Pr.ez, Pr.ez_host.data(), sizeof(double) * S.z.size(), hipMemcpyHostToDevice, h->stream));
+  }
+  Fp64Scope f64(h);
+  if (w) {
+    // linearise at w in fp64: c1 = w^(theta-1), c2 = beta^theta (Tw - 1)^(1-theta) (replaces the cached linearisation)
+    if ((rc = ensure_buf(h, &h->hostio3))) return rc;
+    if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, w, h->hostio3, w, nullptr, nullptr, 0.0, 0))) return rc;
+  }
+  const PriceGeom g = price_geom(h);
+  const int grid = (int)std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK, (long long)h->num_cus * 16);
+  const double* ez = xz != 0.0 ? (const double*)Pr.ez : nullptr;
+  const double n8 = 8.0 * (double)h->N;
+  const int cid = h->profiling ? counter_id(h, sdf_power == 0 ? "price:tilt0" : (sdf_power == 1 ? "price:tilt1" : "price:tilt2"),
+                                            (sdf_power == 0 ? 2 : 4) * n8, 0) : -1;
+  {
+    ProfScope ps(h, cid);
+    if (sdf_power == 0)
+      hipLaunchKernelGGL(k_tilt_scalings<0>, dim3(grid), dim3(PRICE_BLOCK), 0, h->stream, g, el, ec, ez, (const double*)nullptr,
+                         (const double*)nullptr, Pr.d1, Pr.d2);
+    else if (sdf_power == 1)
+      hipLaunchKernelGGL(k_tilt_scalings<1>, dim3(grid), dim3(PRICE_BLOCK), 0, h->stream, g, el, ec, ez, (const double*)h->c1,
+                         (const double*)h->c2, Pr.d1, Pr.d2);
+    else
+      hipLaunchKernelGGL(k_tilt_scalings<2>, dim3(grid), dim3(PRICE_BLOCK), 0, h->stream, g, el, ec, ez, (const double*)h->c1,
+                         (const double*)h->c2, Pr.d1, Pr.d2);
+    HIPCHK(h, hipGetLastError());
+  }
+  Pr.power = sdf_power;
+  return 0;
+}
+
+int sdfs_apply_tilted_dev(sdfs_handle* h, const double* f, double* out) {
+  int rc = check(h); if (rc) return rc;
+  if ((rc = price_handle_ok(h, "sdfs_apply_tilted_dev", true))) return rc;
+  if (!f || !out) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
+  Fp64Scope f64(h);
+  return run_plan(h, h->plan[0], MODE_JVP, true, true, f, out, f, nullptr, nullptr, 0.0, 0, nullptr, h->price.d1, h->price.d2);
+}
+
+int sdfs_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const double* rhs, double* x, int64_t* n_iter,
+                          double* final_rel_resid) {
+  int rc = check(h); if (rc) return rc;
+  if ((rc = price_handle_ok(h, "sdfs_solve_tilted_dev", true))) return rc;
+  if (!rhs || !x) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
+  sdfs_opts o;
+  if (opts) o = *opts; else sdfs_default_opts(&o);
+  o.krylov_f32 = 0;                        // (fp64 whatever the options say)
+  Fp64Scope f64(h);
+  return linear_solve(h, o, MODE_JVP, rhs, x, n_iter, final_rel_resid, h->price.d1, h->price.d2, "tilted");
+}
+
+int sdfs_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* const* weight_axes, int64_t n_save,
+                             const int64_t* save_at, double* const* save_dev, double* out_host) {
+  int rc = check(h); if (rc) return rc;
+  if ((rc = price_handle_ok(h, "sdfs_tilted_horizons_dev", true))) return rc;
+  if (n_max < 1 || n_max > (1LL << 24)) return fail(h, SDFS_ERR_ARG, "n_max = %lld: 1 ... 2^24 horizons", (long long)n_max);
+  if (!out_host) return fail(h, SDFS_ERR_ARG, "NULL out_host");
+  if (n_save < 0 || (n_save > 0 && (!save_at || !save_dev))) return fail(h, SDFS_ERR_ARG, "bad save list");
+  for (int64_t j = 0; j < n_save; ++j) {
+    if (save_at[j] < 1 || save_at[j] > n_max || (j > 0 && save_at[j] <= save_at[j - 1]))
+      return fail(h, SDFS_ERR_ARG, "save_at must rise strictly within 1 ... n_max (save_at[%lld] = %lld)", (long long)j,
+                  (long long)save_at[j]);
+    if (!save_dev[j]) return fail(h, SDFS_ERR_ARG, "save_dev[%lld] is NULL", (long long)j);
+  }
+  PriceWeights wt;
+  for (int a = 0; a < SENS_MAXD; ++a) for (int k = 0; k < SENS_MAXN; ++k) wt.t[a][k] = 0.0;
+  for (int a = 0; a < h->ndim; ++a)
+    for (int k = 0; k < h->shape[a]; ++k) {
+      const double v = weight_axes && weight_axes[a] ? weight_axes[a][k] : 1.0 / h->shape[a];
+      if (!std::isfinite(v)) return fail(h, SDFS_ERR_ARG, "weight_axes[%d][%d] is not finite", a, k);
+      wt.t[a][k] = v;
+    }
+  auto& Pr = h->price;
+  if ((rc = ensure_buf(h, &Pr.pa)) || (rc = ensure_buf(h, &Pr.pb))) return rc;
+  if (!Pr.part && (rc = dev_alloc(h, &Pr.part, (size_t)PRICE_MAX_BLOCKS * PRICE_NSUM))) return rc;
+  if (Pr.res_cap < n_max) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (Pr.res) { hipFree(Pr.res); Pr.res = nullptr; Pr.res_cap = 0; }
+    HIPCHK(h, hipMalloc((void**)&Pr.res, sizeof(double) * PRICE_NSUM * (size_t)n_max));
+    Pr.res_cap = n_max;
+  }
+  Fp64Scope f64(h);
+  const PriceGeom g = price_geom(h);
+  const int rgrid = price_grid(h);
+  const int fgrid = (int)std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK, (long long)h->num_cus * 16);
+  const int cid = h->profiling ? counter_id(h, "price:horizon_reduce", 16.0 * (double)h->N, 0) : -1;
+  hipLaunchKernelGGL(k_price_fill, dim3(fgrid), dim3(PRICE_BLOCK), 0, h->stream, Pr.pa, (long long)h->N, 1.0);
   HIPCHK(h, hipGetLastError());
-  const bool f32 = h->krylov_f32;
-  h->krylov_f32 = false;
-  int64_t mv = 0;
-  rc = bicgstab_dev_t<double>(h, o, &mv, transpose ? MODE_VJP : MODE_JVP);
-  h->krylov_f32 = f32;
-  if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(x, h->kry[5], sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));          // (the loop's last read of the scalars preceded this copy)
-  const double rr = h->sc_host[SC_RR], bb = h->sc_host[SC_BB], a2 = h->sc_host[SC_ATOL2];
-  const long long its = (long long)h->sc_host[SC_ITERS];
-  const double rel = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
-  if (n_iter) *n_iter = its;
-  if (final_rel_resid) *final_rel_resid = rel;
-  if (!(rr <= a2))
-    return fail(h, SDFS_ERR_NUMERIC, "%s BiCGSTAB stopped at relative residual %.3e after %lld iterations (%s)",
-                transpose ? "transposed" : "plain", rel, its,
-                h->sc_host[SC_BREAK] != 0.0 ? "breakdown" : (std::isfinite(rr) ? "not converged" : "non-finite residual"));
+  double* prev = Pr.pa;
+  double* cur = Pr.pb;
+  int64_t js = 0;
+  for (int64_t n = 1; n <= n_max; ++n) {
+    if ((rc = run_plan(h, h->plan[0], MODE_JVP, true, true, prev, cur, prev, nullptr, nullptr, 0.0, 0, nullptr, Pr.d1, Pr.d2))) return rc;
+    {
+      ProfScope ps(h, cid);
+      hipLaunchKernelGGL(k_horizon_reduce, dim3(rgrid), dim3(PRICE_BLOCK), 0, h->stream, g, wt, (const double*)cur,
+                         (const double*)prev, Pr.part);
+    }
+    hipLaunchKernelGGL(k_horizon_finish, dim3(1), dim3(64), 0, h->stream, (const double*)Pr.part, rgrid, Pr.res + PRICE_NSUM * (n - 1));
+    HIPCHK(h, hipGetLastError());
+    if (js < n_save && save_at[js] == n) {
+      HIPCHK(h, hipMemcpyAsync(save_dev[js], cur, sizeof(double) * (size_t)h->N, hipMemcpyDeviceToDevice, h->stream));
+      ++js;
+    }
+    std::swap(prev, cur);
+  }
+  std::vector<double> res((size_t)PRICE_NSUM * n_max);
+  HIPCHK(h, hipMemcpyAsync(res.data(), Pr.res, sizeof(double) * res.size(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  long long first_bad = 0;
+  for (int64_t n = 1; n <= n_max; ++n) {
+    const double* r = res.data() + PRICE_NSUM * (n - 1);
+    out_host[4 * (n - 1) + 0] = r[0];
+    out_host[4 * (n - 1) + 1] = r[1] / (double)n;
+    out_host[4 * (n - 1) + 2] = r[2];
+    out_host[4 * (n - 1) + 3] = r[3];
+    if (r[4] != 0.0 && first_bad == 0) first_bad = n;
+  }
+  if (first_bad)
+    return fail(h, SDFS_ERR_NUMERIC, "P_n is not strictly positive (or NaN) at %.0f grid points at horizon %lld",
+                res[PRICE_NSUM * (first_bad - 1) + 4], first_bad);
   return 0;
 }
 

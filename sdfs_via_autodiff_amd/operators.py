@@ -191,6 +191,51 @@ class KoopmansOperator:
                                         C.byref(rel)), self._h)
         return it.value, rel.value
 
+    # -- asset pricing: the tilted expectation K (pricing.py) ------------------------------------------------------
+    def set_tilt_dev(self, w_ptr, sdf_power, kappa_lam, kappa_c):
+        """Form K = K(sdf_power, kappa_lam, kappa_c) linearised at w (sdfs_set_tilt_dev; w_ptr may be None for
+        sdf_power 0).  Replaces the cached linearisation with the one at w."""
+        check(lib.sdfs_set_tilt_dev(self._h, w_ptr, int(sdf_power), float(kappa_lam), float(kappa_c)), self._h)
+
+    def apply_tilted_dev(self, f_ptr, out_ptr):
+        """out = K f on device pointers (sdfs_apply_tilted_dev)."""
+        check(lib.sdfs_apply_tilted_dev(self._h, f_ptr, out_ptr), self._h)
+
+    def solve_tilted_dev(self, rhs_ptr, x_ptr, rtol=1e-10, atol=0.0, max_iter=0):
+        """x = (I - K)^{-1} rhs (sdfs_solve_tilted_dev).  Returns (iterations, relative residual)."""
+        o = _lib.default_opts()
+        o.inner_rtol, o.inner_atol, o.inner_max_iter = float(rtol), float(atol), int(max_iter)
+        it, rel = C.c_int64(), C.c_double()
+        check(lib.sdfs_solve_tilted_dev(self._h, C.byref(o), rhs_ptr, x_ptr, C.byref(it), C.byref(rel)), self._h)
+        return it.value, rel.value
+
+    def tilted_horizons_dev(self, n_max, weight_axes=None, save_at=(), save_ptrs=()):
+        """P_n = K P_{n-1}, P_0 = 1, for n = 1 ... n_max on the device (sdfs_tilted_horizons_dev).  weight_axes: one
+        host vector per axis (product-form weights; None = uniform).  P_n lands in save_ptrs[j] at n = save_at[j].
+        Returns an (n_max, 4) array: <g, P_n>, <g, -log P_n> / n, min and max of P_n / P_{n-1}."""
+        n_max = int(n_max)
+        save_at = [int(n) for n in save_at]
+        if len(save_ptrs) != len(save_at):
+            raise ValueError(f"{len(save_at)} save horizons but {len(save_ptrs)} save pointers")
+        keep, wp = [], None
+        if weight_axes is not None:
+            if len(weight_axes) != len(self.shapes):
+                raise ValueError(f"weight_axes has {len(weight_axes)} entries, the grid has {len(self.shapes)} axes")
+            for a, (g, n) in enumerate(zip(weight_axes, self.shapes)):
+                g = _as_f64(g).ravel()
+                if g.size != n:
+                    raise ValueError(f"weight_axes[{a}] has {g.size} entries, axis {a} has {n} states")
+                keep.append(g)
+            wp = (C.POINTER(C.c_double) * len(keep))(*[g.ctypes.data_as(C.POINTER(C.c_double)) for g in keep])
+        ns = len(save_at)
+        sat = (C.c_int64 * max(ns, 1))(*save_at)
+        sp = (C.c_void_p * max(ns, 1))(*[int(p) for p in save_ptrs])
+        out = np.empty((max(n_max, 1), 4))
+        check(lib.sdfs_tilted_horizons_dev(self._h, n_max, wp, ns, sat, sp,
+                                           out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        del keep
+        return out
+
     def _to_dev(self, *arrays):
         import torch
         dev = torch.device("cuda", self.device)
