@@ -348,6 +348,16 @@ int sdfs_debug_pow(const double* x_host, double y, double* out_host, int64_t n, 
  * 1/theta in the last; csrc/pass_kernel.hpp, powy): degree 6 = the form inside the operator kernels (|y| * 1.04e-17
  * polynomial error on x^y), degree 7 = accurate for any |y| <= 64, degree 0 = sdfs_debug_pow. */
 int sdfs_debug_powy(const double* x_host, double y, double* out_host, int64_t n, int degree, int device_id);
+/* Test hook: one J.v product in the reduced-precision storage of Newton's inner solve.  Sets the handle's storage flags
+ * as sdfs_solve does for opts.krylov_f32 = `krylov_f32` (0: fp64, 1: fp32, 2: bf16-rounded fp32, 3: fp32 with the pair
+ * plan's fp32-MFMA kernels), linearises at w_dev in that storage (c1 / c2 as scaled floats), runs one J.v application
+ * (out = J v, or J v - v when `minus_identity`) and restores the flags.  v_dev and out_dev hold N floats when `krylov_f32`
+ * != 0 and N doubles when it is 0.  A reduced-precision call leaves c1 / c2 as floats and marks the cached linearisation
+ * invalid: sdfs_apply_jvp_dev, sdfs_apply_vjp_dev and sdfs_solve_linear_dev then return SDFS_ERR_ARG until the next
+ * sdfs_linearize_dev or sdfs_param_tangent_dev.  SDFS_ERR_UNSUPPORTED for a non-zero `krylov_f32` on continuous, dense or
+ * sharded handles (sdfs_solve ignores the option there). */
+int sdfs_debug_jvp_storage_dev(sdfs_handle* h, int krylov_f32, const double* w_dev, const void* v_dev, void* out_dev,
+                               int minus_identity);
 
 /* Measurement aid (bench.py's `copy_ceiling_GBps`; no counterpart in the reference): dst[0..n) = src[0..n) by the library's
  * own streaming copy -- one launch on the handle's stream, 16 bytes per lane, eight loads in flight per lane, non-temporal

@@ -99,6 +99,7 @@ SYMBOLS = {
     "sdfs_stream_copy_dev": (C.c_int, [_P, _P, _P, C.c_int64]),
     "sdfs_debug_pow": (C.c_int, [_P, C.c_double, _P, C.c_int64, C.c_int]),
     "sdfs_debug_powy": (C.c_int, [_P, C.c_double, _P, C.c_int64, C.c_int, C.c_int]),
+    "sdfs_debug_jvp_storage_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int]),
 }
 
 

@@ -212,6 +212,8 @@ struct sdfs_handle {
   bool krylov_mfma32 = false;        // ... with the J.v passes of the pair plan on an fp32 LDS tile and fp32 MFMA (opts.krylov_f32 = 3: f32_kernels.hpp)
   bool krylov_bf16 = false;          // ... with every store of those fp32 containers rounded to bfloat16 (opts.krylov_f32 = 2: bf16r, vec_kernels.hpp)
   double lin_ref = 0.0;              // sharded handles: reference value of the fp32 linearisation scale (sdfs_set_krylov_f32)
+  bool lin_stale = false;            // c1 / c2 hold the scaled floats of sdfs_debug_jvp_storage_dev: no fp64 J.v until the next
+                                     // sdfs_linearize_dev / sdfs_param_tangent_dev
 
   // continuous-state operator (sdfs_create_continuous): no plan, one kernel per application
   bool cont = false;
@@ -3171,14 +3173,16 @@ int sdfs_linearize_dev(sdfs_handle* h, const double* w, double* Tw) {
   if (h->sharded) return fail(h, SDFS_ERR_ARG, "sharded handle: use sdfs_apply_stage_dev");
   double* out = Tw;
   if (!out) { if ((rc = ensure_buf(h, &h->hostio3))) return rc; out = h->hostio3; }
-  return run_plan(h, h->plan[0], MODE_T_LIN, true, true, w, out, w, nullptr, nullptr, 0.0, 0);
+  if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, w, out, w, nullptr, nullptr, 0.0, 0))) return rc;
+  h->lin_stale = false;
+  return 0;
 }
 
 int sdfs_apply_jvp_dev(sdfs_handle* h, const double* v, double* out, int minus_identity) {
   int rc = check(h); if (rc) return rc;
   if (!v || !out) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
   if (h->sharded) return fail(h, SDFS_ERR_ARG, "sharded handle: use sdfs_apply_stage_dev");
-  if (!h->c1 || !h->c2) return fail(h, SDFS_ERR_ARG, "sdfs_apply_jvp_dev before sdfs_linearize_dev");
+  if (!h->c1 || !h->c2 || h->lin_stale) return fail(h, SDFS_ERR_ARG, "sdfs_apply_jvp_dev before sdfs_linearize_dev");
   return run_plan(h, h->plan[0], MODE_JVP, true, true, v, out, v, nullptr, nullptr, 0.0, minus_identity);
 }
 
@@ -3200,7 +3204,7 @@ int sdfs_apply_vjp_dev(sdfs_handle* h, const double* u, double* out, int minus_i
   int rc = check(h); if (rc) return rc;
   if (!u || !out) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
   if (h->sharded) return fail(h, SDFS_ERR_ARG, "sharded handle: no vector-Jacobian product");
-  if (!h->c1 || !h->c2) return fail(h, SDFS_ERR_ARG, "sdfs_apply_vjp_dev before sdfs_linearize_dev");
+  if (!h->c1 || !h->c2 || h->lin_stale) return fail(h, SDFS_ERR_ARG, "sdfs_apply_vjp_dev before sdfs_linearize_dev");
   const bool f32 = h->krylov_f32;
   h->krylov_f32 = false;
   rc = run_plan(h, h->plan[0], MODE_VJP, true, true, u, out, u, nullptr, nullptr, 0.0, minus_identity);
@@ -3243,6 +3247,7 @@ int sdfs_param_tangent_dev(sdfs_handle* h, const double* w, const double* dparam
   }
   // linearise at w (T w, and the cache of c1 / c2 the J.v below and a later sdfs_solve_linear_dev use)
   if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, w, Tw, w, nullptr, nullptr, 0.0, 0))) return rc;
+  h->lin_stale = false;
   SensGeom g;
   memset(&g, 0, sizeof g);
   g.n = h->N; g.ndim = h->ndim;
@@ -3308,7 +3313,7 @@ int sdfs_solve_linear_dev(sdfs_handle* h, int transpose, const sdfs_opts* opts, 
   int rc = check(h); if (rc) return rc;
   if (!rhs || !x) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
   if (h->sharded) return fail(h, SDFS_ERR_UNSUPPORTED, "sharded handle: no single-handle linear solve");
-  if (!h->c1 || !h->c2) return fail(h, SDFS_ERR_ARG, "sdfs_solve_linear_dev before a linearisation (sdfs_linearize_dev, "
+  if (!h->c1 || !h->c2 || h->lin_stale) return fail(h, SDFS_ERR_ARG, "sdfs_solve_linear_dev before a linearisation (sdfs_linearize_dev, "
                                     "sdfs_param_tangent_dev)");
   if (transpose) {                         // where sdfs_apply_vjp_dev is unsupported (run_plan, MODE_VJP)
     if (h->cont || h->dense) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product exists for the discretised operator only");
@@ -3390,6 +3395,7 @@ int sdfs_set_tilt_dev(sdfs_handle* h, const double* w, int sdf_power, double kap
     // linearise at w in fp64: c1 = w^(theta-1), c2 = beta^theta (Tw - 1)^(1-theta) (replaces the cached linearisation)
     if ((rc = ensure_buf(h, &h->hostio3))) return rc;
     if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, w, h->hostio3, w, nullptr, nullptr, 0.0, 0))) return rc;
+    h->lin_stale = false;
   }
   const PriceGeom g = price_geom(h);
   const int grid = (int)std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK, (long long)h->num_cus * 16);
@@ -3869,6 +3875,28 @@ int sdfs_debug_powy(const double* x_host, double y, double* out_host, int64_t n,
   return e == hipSuccess ? 0 : fail(nullptr, SDFS_ERR_HIP, "debug_pow: %s", hipGetErrorString(e));
 }
 
+int sdfs_debug_jvp_storage_dev(sdfs_handle* h, int krylov_f32, const double* w_dev, const void* v_dev, void* out_dev,
+                               int minus_identity) {
+  int rc = check(h); if (rc) return rc;
+  if (!w_dev || !v_dev || !out_dev) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
+  if (krylov_f32 < 0 || krylov_f32 > 3) return fail(h, SDFS_ERR_ARG, "krylov_f32 = %d: 0, 1, 2 or 3", krylov_f32);
+  if (krylov_f32 != 0 && (h->cont || h->dense || h->sharded))
+    return fail(h, SDFS_ERR_UNSUPPORTED, "reduced-precision J.v storage exists for unsharded discretised handles only");
+  if (h->sharded) return fail(h, SDFS_ERR_ARG, "sharded handle: use sdfs_apply_stage_dev");
+  if ((rc = ensure_buf(h, &h->hostio3))) return rc;
+  Fp64Scope keep(h);                       // (restores the handle's own flags on every exit path)
+  // the storage flags exactly as solve_newton sets them for opts.krylov_f32
+  h->krylov_f32 = krylov_f32 != 0;
+  h->krylov_bf16 = krylov_f32 == 2;
+  h->krylov_mfma32 = krylov_f32 == 3;
+  // from here on c1 / c2 may hold scaled floats: an fp64 J.v must relinearise first
+  if (krylov_f32 != 0) h->lin_stale = true;
+  if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, w_dev, h->hostio3, w_dev, nullptr, nullptr, 0.0, 0))) return rc;
+  if (krylov_f32 == 0) h->lin_stale = false;
+  return run_plan(h, h->plan[0], MODE_JVP, true, true, (const double*)v_dev, (double*)out_dev, (const double*)v_dev, nullptr,
+                  nullptr, 0.0, minus_identity);
+}
+
 int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
   if (!h || !buf || cap < 1) return SDFS_ERR_ARG;
   std::string s;
@@ -3913,6 +3941,25 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
     }
     if (h->fast.small && anderson_fused_ok(h, 10))
       s += "small-grid plan, Anderson: passes in reverse order, push on the last pass, control step + update of x on the first\n";
+    // the fp32 J.v forms of each pass (opts.krylov_f32 = 1 / 2: fp32 streams on the fp64 tile; 3: the fp32-MFMA kernel
+    // run_fast_plan picks, with its row width and, for a middle pass, whether it runs persistent)
+    for (size_t i = 0; i < h->fast.passes.size() && h->fast.f32_ok && !h->fast.small && !h->fast.pad; ++i) {
+      const FastPass& P = h->fast.passes[i];
+      const bool last = i + 1 == h->fast.passes.size();
+      if (!P.line) {
+        snprintf(line, sizeof line, "pair plan pass %zu fp32: %s mfma32 %s\n", i, P.label.c_str(), slice32_variant(P.n) ? "slice32" : "none");
+      } else {
+        const int r32 = line32_row_floats(P.n, P.ld.lrest);
+        const long long grid = P.ld.ntiles * LINE_R / r32;
+        const bool persist = !last && (P.stream & 1) && grid >= 8 * TK_SUB && h->knobs.no_f32_stream == 0 &&
+                             line32_stream_mid_variant(P.n, r32) != nullptr;
+        snprintf(line, sizeof line, "pair plan pass %zu fp32: %s mfma32 %s row %d floats %s\n", i, P.label.c_str(),
+                 line32_variant(P.n, last ? L_JLAST : L_MID, r32) ? "line32" : "none", r32,
+                 last ? "last pass" : persist ? "persistent middle pass" : "one tile per workgroup");
+      }
+      s += line;
+    }
+    if (!h->fast.f32_ok || h->fast.small || h->fast.pad) s += "pair plan fp32: none (fp32 Krylov storage on the generic plan)\n";
     s += "generic plan (fp32 Krylov storage, sharded stages):\n";
   }
   if (h->sharded && h->sfast[0].ok) {

@@ -93,7 +93,7 @@ class KoopmansOperator:
         self._finalizer()
 
     def describe_plan(self):
-        buf = C.create_string_buffer(4096)
+        buf = C.create_string_buffer(16384)
         check(lib.sdfs_describe_plan(self._h, buf, len(buf)), self._h)
         return buf.value.decode()
 
@@ -148,6 +148,12 @@ class KoopmansOperator:
 
     def vjp_dev(self, u_ptr, out_ptr, minus_identity=False):
         check(lib.sdfs_apply_vjp_dev(self._h, u_ptr, out_ptr, int(minus_identity)), self._h)
+
+    def debug_jvp_storage_dev(self, krylov_f32, w_ptr, v_ptr, out_ptr, minus_identity=False):
+        """Test hook (sdfs_debug_jvp_storage_dev): linearise at w and apply J once in the storage of Newton's inner solve
+        for opts.krylov_f32 = ``krylov_f32``; v and out are N floats for a non-zero storage, N doubles for 0.  Afterwards
+        the cached linearisation is invalid for the fp64 device forms until the next ``linearize_dev``."""
+        check(lib.sdfs_debug_jvp_storage_dev(self._h, int(krylov_f32), w_ptr, v_ptr, out_ptr, int(minus_identity)), self._h)
 
     def _darrays(self, darrays):
         """ctypes array of the narrays host pointers of a direction (None -> NULL), sizes checked against the arrays."""
