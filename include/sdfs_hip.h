@@ -231,6 +231,38 @@ int sdfs_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const double* r
 int sdfs_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* const* weight_axes, int64_t n_save,
                              const int64_t* save_at, double* const* save_dev, double* out_host);
 
+/* Simulated paths of the discretised chain at w* (unsharded multi-index handles only, else
+ * SDFS_ERR_UNSUPPORTED; fp64 whatever the handle's fp32 settings).  The chain must factorise: axis a moves by one
+ * n_a x n_a matrix, whose cumulative rows the caller passes (the last entry of each row set to 2).  Step t of path p
+ * draws Philox4x32-10 words with counter (t, p, b, 0), b = 0, 1, and key (seed & 0xffffffff, seed >> 32). */
+typedef struct sdfs_sim_desc {
+  uint64_t seed;
+  int64_t path_offset;      /* number of the first path; path_offset + n_paths <= 2^32 */
+  int64_t n_paths;
+  int64_t burn_in;          /* B >= 0 */
+  int64_t n_periods;        /* T >= 2, B + T < 2^32 */
+  int32_t has_kappa;        /* the records carry ln v and ln(1 + v) of a claim on G_c^kappa: the series rd, xd, pd */
+  int32_t start_fixed;      /* 1: x_0 = start[]; 0: x_0 drawn from the stationary marginals (cdf0) */
+  double kappa;
+  int32_t start[6];
+  int32_t lookahead;        /* record loads in flight per lane: 1, 2 or 4 (0: the default) */
+  int32_t search;           /* inverse-CDF search: 1 linear, 2 binary (0: the default) */
+  const double* cdf;        /* HOST: per axis in grid order, its n_a x n_a cumulative rows (row-major), concatenated */
+  const double* cdf0;       /* HOST: per axis, its n_a cumulative stationary weights, concatenated (NULL with start_fixed) */
+} sdfs_sim_desc;
+/* One 64-byte record per state into records_dev (N x 8 doubles): {ln w, ln(w - 1), -ln E_x[M], mu_c + z(x), w, ln v,
+ * ln(1 + v), 0}, with E_x[M] = K(1, theta, -gamma) 1 formed by sdfs_set_tilt_dev(w, 1, theta, -gamma) and
+ * sdfs_apply_tilted_dev (so the cached linearisation and the tilt are those of that call afterwards).  v_dev (N doubles)
+ * may be NULL: the two fields are then 0. */
+int sdfs_sim_records_dev(sdfs_handle* h, const double* w_dev, const double* v_dev, double* records_dev);
+/* desc->n_paths paths of desc->n_periods recorded steps after desc->burn_in, one lane per path, from the records of
+ * sdfs_sim_records_dev.  stats_dev: (3 nser + 1) x n_paths doubles, structure of arrays: mean, std, ac1 of series
+ * k at rows 3k ... 3k+2, the slope last; series dc, m, rf, rc, xc, wc (nser = 6), and rd, xd, pd with a claim (nser = 9).
+ * idx_dev (n_paths x (T+1) x ndim bytes: x_B ... x_{B+T}) and series_dev (nser x n_paths x T doubles) are both NULL or
+ * both set; set, they run with the default lookahead and search.  No host synchronisation; two runs give identical bits. */
+int sdfs_sim_paths_dev(sdfs_handle* h, const double* records_dev, const sdfs_sim_desc* desc, double* stats_dev,
+                       uint8_t* idx_dev, double* series_dev);
+
 /* max|T(w) - w| of the most recent apply that computed it. */
 int sdfs_residual(sdfs_handle* h, double* sup_norm);
 

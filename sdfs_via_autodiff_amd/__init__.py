@@ -27,6 +27,7 @@ from .single_index import (DenseOperator, compute_H_single_index, discretize_sin
 from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_ratio_sensitivities,
                           wc_ratio_gradient)
 from .pricing import stationary_weights, sdf_moments, term_structure, claim_prices
+from .simulation import simulate
 from ._lib import SdfsError, LIB_PATH
 
 __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize_gcy",
@@ -40,5 +41,5 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "DenseOperator", "compute_H_single_index", "discretize_single_index", "single_index_T",
            "single_to_multi", "multi_to_single",
            "discretize_ssy_tangent", "discretize_gcy_tangent", "wc_ratio_sensitivities", "wc_ratio_gradient",
-           "stationary_weights", "sdf_moments", "term_structure", "claim_prices",
+           "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate",
            "SdfsError", "LIB_PATH"]

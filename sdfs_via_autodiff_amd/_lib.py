@@ -37,6 +37,14 @@ class sdfs_kernel_counter(C.Structure):
                 ("alg_bytes", C.c_double), ("alg_flops", C.c_double)]
 
 
+class sdfs_sim_desc(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("path_offset", C.c_int64), ("n_paths", C.c_int64),
+                ("burn_in", C.c_int64), ("n_periods", C.c_int64),
+                ("has_kappa", C.c_int32), ("start_fixed", C.c_int32), ("kappa", C.c_double),
+                ("start", C.c_int32 * 6), ("lookahead", C.c_int32), ("search", C.c_int32),
+                ("cdf", C.POINTER(C.c_double)), ("cdf0", C.POINTER(C.c_double))]
+
+
 class sdfs_counters(C.Structure):
     _fields_ = [("nkernels", C.c_int32), ("reserved", C.c_int32),
                 ("k", sdfs_kernel_counter * SDFS_MAX_KERNELS)]
@@ -75,6 +83,8 @@ SYMBOLS = {
     "sdfs_apply_tilted_dev": (C.c_int, [_P, _P, _P]),
     "sdfs_solve_tilted_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _P, _I64, _D]),
     "sdfs_tilted_horizons_dev": (C.c_int, [_P, C.c_int64, C.POINTER(_D), C.c_int64, C.POINTER(C.c_int64), C.POINTER(_P), _D]),
+    "sdfs_sim_records_dev": (C.c_int, [_P, _P, _P, _P]),
+    "sdfs_sim_paths_dev": (C.c_int, [_P, _P, C.POINTER(sdfs_sim_desc), _P, _P, _P]),
     "sdfs_residual": (C.c_int, [_P, _D]),
     "sdfs_solve": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _I64, _I64, _D]),
     "sdfs_solve_dev": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _I64, _I64, _D]),

@@ -31,6 +31,7 @@
 #include "krylov_kernels.hpp"
 #include "sens_kernels.hpp"
 #include "price_kernels.hpp"
+#include "sim_kernels.hpp"
 
 using namespace sdfs;
 
@@ -202,6 +203,14 @@ struct sdfs_handle {
     double* part = nullptr;                                   // per-workgroup partials of one horizon
     double* res = nullptr; long long res_cap = 0;             // PRICE_NSUM doubles per horizon
   } price;
+
+  // simulated paths (sdfs_sim_records_dev / sdfs_sim_paths_dev)
+  struct {
+    double* one = nullptr; double* em = nullptr;              // E_x[M] = K(1, theta, -gamma) 1
+    double* zt = nullptr;                                     // mu_c + z in the a3 layout
+    double* tab = nullptr;                                    // k_sim_paths' LDS table (SIM_TAB_MAX doubles)
+    std::vector<double> tab_host;                             // its staging (kept alive across the async copy)
+  } sim;
 
   // Newton-Krylov with fp32 Krylov vectors / J.v streams (opts.krylov_f32); set while such a solve runs
   bool krylov_f32 = false;
@@ -3510,6 +3519,150 @@ int sdfs_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* const*
   if (first_bad)
     return fail(h, SDFS_ERR_NUMERIC, "P_n is not strictly positive (or NaN) at %.0f grid points at horizon %lld",
                 res[PRICE_NSUM * (first_bad - 1) + 4], first_bad);
+  return 0;
+}
+
+// -- simulated paths (sim_kernels.hpp) -------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+constexpr int SIM_K_DEFAULT = 2;             // record loads in flight per lane (tools/simulation_times.py A/B)
+constexpr bool SIM_LIN_DEFAULT = false;      // inverse-CDF search: binary (false) or linear (true)
+
+int sim_handle_ok(sdfs_handle* h, const char* fn) {
+  if (h->cont || h->dense || h->sharded)
+    return fail(h, SDFS_ERR_UNSUPPORTED, "%s: simulation exists for unsharded discretised (multi-index) handles only", fn);
+  return 0;
+}
+
+template <int ND, bool KAP, bool LIN, int K>
+void sim_launch(sdfs_handle* h, dim3 grid, size_t lds, const SimArgs& a, const double* tab, const double* rec,
+                double* stats, unsigned char* idx, double* ser) {
+  if constexpr (LIN == SIM_LIN_DEFAULT && K == SIM_K_DEFAULT) {
+    if (idx) {
+      hipLaunchKernelGGL((k_sim_paths<ND, KAP, LIN, K, true>), grid, dim3(SIM_BLOCK), lds, h->stream, a, tab, rec, stats, idx, ser);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_sim_paths<ND, KAP, LIN, K, false>), grid, dim3(SIM_BLOCK), lds, h->stream, a, tab, rec, stats, idx, ser);
+}
+
+template <int ND, bool KAP>
+void sim_dispatch(sdfs_handle* h, int k, bool lin, dim3 grid, size_t lds, const SimArgs& a, const double* tab,
+                  const double* rec, double* stats, unsigned char* idx, double* ser) {
+  if (lin) {
+    if (k == 1) sim_launch<ND, KAP, true, 1>(h, grid, lds, a, tab, rec, stats, idx, ser);
+    else if (k == 2) sim_launch<ND, KAP, true, 2>(h, grid, lds, a, tab, rec, stats, idx, ser);
+    else sim_launch<ND, KAP, true, 4>(h, grid, lds, a, tab, rec, stats, idx, ser);
+  } else {
+    if (k == 1) sim_launch<ND, KAP, false, 1>(h, grid, lds, a, tab, rec, stats, idx, ser);
+    else if (k == 2) sim_launch<ND, KAP, false, 2>(h, grid, lds, a, tab, rec, stats, idx, ser);
+    else sim_launch<ND, KAP, false, 4>(h, grid, lds, a, tab, rec, stats, idx, ser);
+  }
+}
+}  // namespace
+}  // extern "C++"
+
+int sdfs_sim_records_dev(sdfs_handle* h, const double* w, const double* v, double* rec) {
+  int rc = check(h); if (rc) return rc;
+  if ((rc = sim_handle_ok(h, "sdfs_sim_records_dev"))) return rc;
+  if (!w || !rec) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
+  auto& Sm = h->sim;
+  const auto& S = h->sens;
+  if ((rc = ensure_buf(h, &Sm.one)) || (rc = ensure_buf(h, &Sm.em))) return rc;
+  if (!Sm.zt) {
+    std::vector<double> zt(S.z.size());
+    for (size_t i = 0; i < zt.size(); ++i) zt[i] = S.mu_c + S.z[i];
+    if ((rc = upload(h, &Sm.zt, zt.data(), zt.size()))) return rc;
+  }
+  const int fgrid = (int)std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK, (long long)h->num_cus * 16);
+  hipLaunchKernelGGL(k_price_fill, dim3(fgrid), dim3(PRICE_BLOCK), 0, h->stream, Sm.one, (long long)h->N, 1.0);
+  HIPCHK(h, hipGetLastError());
+  // E_x[M] = K(1, theta, -gamma) 1: the product sdf_moments forms, bit for bit
+  if ((rc = sdfs_set_tilt_dev(h, w, 1, h->theta, -S.gamma))) return rc;
+  if ((rc = sdfs_apply_tilted_dev(h, Sm.one, Sm.em))) return rc;
+  const int cid = h->profiling ? counter_id(h, "sim:records", (double)h->N * (16.0 + (v ? 8.0 : 0.0) + 8.0 * SIM_REC), 0) : -1;
+  {
+    ProfScope ps(h, cid);
+    hipLaunchKernelGGL(k_sim_records, dim3(fgrid), dim3(PRICE_BLOCK), 0, h->stream, price_geom(h), (const double*)Sm.zt, w,
+                       (const double*)Sm.em, v, rec);
+    HIPCHK(h, hipGetLastError());
+  }
+  return 0;
+}
+
+int sdfs_sim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_sim_desc* d, double* stats, uint8_t* idx, double* ser) {
+  int rc = check(h); if (rc) return rc;
+  if ((rc = sim_handle_ok(h, "sdfs_sim_paths_dev"))) return rc;
+  if (!rec || !d || !stats) return fail(h, SDFS_ERR_ARG, "NULL records, desc or stats");
+  if (!idx != !ser) return fail(h, SDFS_ERR_ARG, "idx and series are stored together: both NULL or neither");
+  if (d->n_paths < 1 || d->path_offset < 0 || d->path_offset + d->n_paths > (1LL << 32))
+    return fail(h, SDFS_ERR_ARG, "paths %lld ... %lld: numbers lie in 0 ... 2^32 - 1", (long long)d->path_offset,
+                (long long)(d->path_offset + d->n_paths - 1));
+  if (d->n_periods < 2 || d->burn_in < 0 || d->burn_in + d->n_periods >= (1LL << 32))
+    return fail(h, SDFS_ERR_ARG, "burn_in = %lld, n_periods = %lld: T >= 2 and B + T < 2^32", (long long)d->burn_in,
+                (long long)d->n_periods);
+  if (d->has_kappa && !std::isfinite(d->kappa)) return fail(h, SDFS_ERR_ARG, "kappa is not finite");
+  if (!d->cdf || (!d->start_fixed && !d->cdf0)) return fail(h, SDFS_ERR_ARG, "NULL cumulative transition table");
+  const int k = d->lookahead ? d->lookahead : SIM_K_DEFAULT;
+  if (k != 1 && k != 2 && k != 4) return fail(h, SDFS_ERR_ARG, "lookahead = %d: 1, 2 or 4", d->lookahead);
+  if (d->search < 0 || d->search > 2) return fail(h, SDFS_ERR_ARG, "search = %d: 0, 1 (linear) or 2 (binary)", d->search);
+  const bool lin = d->search ? d->search == 1 : SIM_LIN_DEFAULT;
+  if (idx && (k != SIM_K_DEFAULT || lin != SIM_LIN_DEFAULT))
+    return fail(h, SDFS_ERR_ARG, "stored paths run with the default lookahead and search");
+  const auto& S = h->sens;
+  SimArgs a{};
+  auto& tb = h->sim.tab_host;
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // (the previous call's staging copy may still be in flight)
+  tb.clear();
+  size_t ci = 0, c0 = 0;
+  for (int ax = 0; ax < h->ndim; ++ax) {
+    const int n = h->shape[ax];
+    a.n[ax] = n;
+    a.cdf_off[ax] = (int)tb.size();
+    tb.insert(tb.end(), d->cdf + ci, d->cdf + ci + (size_t)n * n);
+    ci += (size_t)n * n;
+    if (d->start_fixed && (d->start[ax] < 0 || d->start[ax] >= n))
+      return fail(h, SDFS_ERR_ARG, "start[%d] = %d: a state index of axis %d lies in 0 ... %d", ax, d->start[ax], ax, n - 1);
+    a.start[ax] = d->start_fixed ? d->start[ax] : 0;
+  }
+  for (int ax = 0; ax < h->ndim; ++ax) {
+    const int n = h->shape[ax];
+    a.cdf0_off[ax] = (int)tb.size();
+    if (d->start_fixed) tb.insert(tb.end(), (size_t)n, 2.0);
+    else tb.insert(tb.end(), d->cdf0 + c0, d->cdf0 + c0 + n);
+    c0 += n;
+  }
+  long long st = 1;
+  for (int ax = h->ndim - 1; ax >= 0; --ax) { a.stride[ax] = (int)st; st *= h->shape[ax]; }
+  a.ax_lam = S.ax_a1; a.ax_c = S.ax_a2;
+  a.hl_off = (int)tb.size(); tb.insert(tb.end(), S.hlam.begin(), S.hlam.end());
+  a.sc_off = (int)tb.size(); tb.insert(tb.end(), S.sigc.begin(), S.sigc.end());
+  a.lds_n = (int)tb.size();
+  if (a.lds_n > SIM_TAB_MAX) return fail(h, SDFS_ERR_ARG, "LDS table of %d doubles", a.lds_n);
+  a.start_fixed = d->start_fixed ? 1 : 0;
+  a.key0 = (unsigned)(d->seed & 0xffffffffu); a.key1 = (unsigned)(d->seed >> 32);
+  a.path0 = (unsigned long long)d->path_offset;
+  a.n_paths = d->n_paths;
+  a.burn_in = (unsigned)d->burn_in; a.n_periods = (unsigned)d->n_periods;
+  a.theta = h->theta; a.theta_ln_beta = h->theta * std::log(h->beta); a.gamma = S.gamma; a.kappa = d->has_kappa ? d->kappa : 0.0;
+  if (!h->sim.tab && (rc = dev_alloc(h, &h->sim.tab, SIM_TAB_MAX))) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->sim.tab, tb.data(), sizeof(double) * tb.size(), hipMemcpyHostToDevice, h->stream));
+  const dim3 grid((unsigned)((d->n_paths + SIM_BLOCK - 1) / SIM_BLOCK));
+  const size_t lds = sizeof(double) * (size_t)a.lds_n;
+  const double steps = (double)d->n_paths * (double)(d->burn_in + d->n_periods);
+  const int cid = h->profiling ? counter_id(h, "sim:paths", 8.0 * SIM_REC * (double)d->n_paths * (double)(d->n_periods + 1), steps) : -1;
+  {
+    ProfScope ps(h, cid);
+    const double* tab = h->sim.tab;
+    if (h->ndim == 4) {
+      if (d->has_kappa) sim_dispatch<4, true>(h, k, lin, grid, lds, a, tab, rec, stats, idx, ser);
+      else sim_dispatch<4, false>(h, k, lin, grid, lds, a, tab, rec, stats, idx, ser);
+    } else {
+      if (d->has_kappa) sim_dispatch<6, true>(h, k, lin, grid, lds, a, tab, rec, stats, idx, ser);
+      else sim_dispatch<6, false>(h, k, lin, grid, lds, a, tab, rec, stats, idx, ser);
+    }
+    HIPCHK(h, hipGetLastError());
+  }
   return 0;
 }
 

@@ -242,6 +242,33 @@ class KoopmansOperator:
         del keep
         return out
 
+    # -- simulated paths (simulation.py) -------------------------------------------------------------------------------
+    def sim_records_dev(self, w_ptr, v_ptr, rec_ptr):
+        """One 64-byte record per state into rec_ptr (N x 8 doubles; sdfs_sim_records_dev).  v_ptr: the claim's
+        price–dividend ratio, or None.  Leaves the tilt K(1, θ, −γ) at w set."""
+        check(lib.sdfs_sim_records_dev(self._h, w_ptr, v_ptr, rec_ptr), self._h)
+
+    def sim_paths_dev(self, rec_ptr, cdf, cdf0, seed, path_offset, n_paths, burn_in, n_periods, kappa=None,
+                      start=None, stats_ptr=None, idx_ptr=None, series_ptr=None, lookahead=0, search=0):
+        """Paths of the chain from the records (sdfs_sim_paths_dev).  cdf: the per-axis cumulative rows, concatenated;
+        cdf0: the per-axis cumulative stationary marginals (ignored with a fixed ``start``)."""
+        cdf = _as_f64(cdf).ravel()
+        cdf0 = _as_f64(cdf0).ravel() if cdf0 is not None else None
+        d = _lib.sdfs_sim_desc()
+        d.seed, d.path_offset, d.n_paths = int(seed), int(path_offset), int(n_paths)
+        d.burn_in, d.n_periods = int(burn_in), int(n_periods)
+        d.has_kappa = int(kappa is not None)
+        d.kappa = float(kappa) if kappa is not None else 0.0
+        d.start_fixed = int(start is not None)
+        if start is not None:
+            for a, s in enumerate(start):
+                d.start[a] = int(s)
+        d.lookahead, d.search = int(lookahead), int(search)
+        d.cdf = cdf.ctypes.data_as(C.POINTER(C.c_double))
+        d.cdf0 = cdf0.ctypes.data_as(C.POINTER(C.c_double)) if cdf0 is not None else None
+        check(lib.sdfs_sim_paths_dev(self._h, rec_ptr, C.byref(d), stats_ptr, idx_ptr, series_ptr), self._h)
+        del cdf, cdf0
+
     def _to_dev(self, *arrays):
         import torch
         dev = torch.device("cuda", self.device)

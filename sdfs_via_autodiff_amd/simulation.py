@@ -1,0 +1,166 @@
+"""
+Simulated paths of the discretised chain at the fixed point w*: the SDF, returns and their sample moments.
+
+What a long-run-risk model is compared with are moments of simulated series of data length, across many samples.  Each
+path starts at x_0 (drawn from the stationary distribution, or a given state), runs B burn-in steps, then records T
+transitions x_{t−1} → x_t with a standard normal ξ_t (t = B+1 … B+T):
+
+    dc_t = μ_c + z(x_{t−1}) + σ_c(x_{t−1}) ξ_t                                  log consumption growth
+    m_t  = θ ln β + θ h_λ(x_t) − γ dc_t + (θ−1)(ln w(x_t) − ln(w(x_{t−1}) − 1))   log SDF
+    rf_t = −ln E_{x_{t−1}}[M]                                                   log risk-free rate
+    rc_t = dc_t + ln w(x_t) − ln(w(x_{t−1}) − 1),  xc_t = rc_t − rf_t,  wc_t = w(x_t)
+    with κ (a claim on G_c^κ, v its price–dividend ratio):
+    rd_t = κ dc_t + ln(1 + v(x_t)) − ln v(x_{t−1}),  xd_t = rd_t − rf_t,  pd_t = ln v(x_t)
+
+Random numbers are Philox4x32-10 with counter (t, p, b, 0) for step t of path p, so every index can be reproduced
+(tests/sim_oracle.py is the numpy twin).  The grid work (records) and the paths (one lane each) run in libsdfs_hip.so
+(sdfs_sim_records_dev, sdfs_sim_paths_dev), fp64.  DESIGN §4.8.
+"""
+import math
+
+import numpy as np
+
+from .pricing import _AXIS_Q, _shapes, _check_grid, _kappa, stationary_weights, claim_prices
+from .sensitivity import _kind, _operator, _device_grid
+
+SERIES = ("dc", "m", "rf", "rc", "xc", "wc")
+SERIES_KAPPA = SERIES + ("rd", "xd", "pd")
+STATS = ("mean", "std", "ac1")
+MAX_RETURNED = 1 << 25            # path-steps of returned series
+REC_BYTES = 64                    # per state
+
+
+def cdf_tables(model, shapes, arrays=None):
+    """(cdf, cdf0): per axis the cumulative rows of its transition matrix and the cumulative stationary marginal, np.cumsum
+    in fp64 with the last entry of every row set to 2.0.  ValueError (of ``stationary_weights``) when the chain does not
+    factorise."""
+    kind, shapes = _shapes(model, shapes)
+    arr = _kind(model)[2](model, shapes) if arrays is None else arrays
+    pis = stationary_weights(model, shapes, arr)
+    cdf, cdf0 = [], []
+    for qi, n, pi in zip(_AXIS_Q[kind], shapes, pis):
+        Q = np.asarray(arr[qi], dtype=np.float64).reshape(-1, n, n)[0]
+        c = np.cumsum(Q, axis=1)
+        c[:, -1] = 2.0
+        c0 = np.cumsum(pi)
+        c0[-1] = 2.0
+        cdf.append(c)
+        cdf0.append(c0)
+    return cdf, cdf0
+
+
+def _count(x, name, lo, hi):
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not lo <= int(x) <= hi:
+        raise ValueError(f"{name} must be an integer in {lo} ... {hi}, got {x!r}")
+    return int(x)
+
+
+def _summary(a):
+    a = np.asarray(a, dtype=np.float64)
+    ok = a[np.isfinite(a)]
+    if ok.size == 0:
+        nan = float("nan")
+        return {"mean": nan, "median": nan, "p05": nan, "p95": nan}
+    return {"mean": float(ok.mean()), "median": float(np.median(ok)), "p05": float(np.percentile(ok, 5)),
+            "p95": float(np.percentile(ok, 95))}
+
+
+def simulate(model, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, path_offset=0, start="stationary",
+             kappa=None, rtol=1e-10, return_paths=False):
+    """Simulate ``n_paths`` paths (numbered path_offset … path_offset + n_paths − 1) of ``n_periods`` recorded steps
+    after ``burn_in`` steps of the discretised chain of (model, shapes) at the fixed point ``w_star``.
+
+    start: "stationary" (x_0 from the product of the stationary marginals) or one state index per axis.  kappa: None,
+    or the leverage of a claim on G_c^κ whose price–dividend ratio v = claim_prices(...)["pd"] (at ``rtol``) adds the
+    series rd, xd, pd.  Returns {"series": names, "per_path": {name: {"mean", "std", "ac1"}, "slope"} (host arrays of
+    shape (n_paths,)), "summary": the NaN-ignoring cross-path mean, median, 5 % and 95 % of each, "pooled": {name:
+    {"mean", "se"}} over all path-steps (se from the per-path means)}, and with ``return_paths`` "paths" = {"index":
+    (P, T+1, d) uint8 for t = B … B+T, name: (P, T) float64}.  ``slope``: OLS slope of xd_t on pd_{t−1} (xc_t on
+    ln(w(x_{t−1}) − 1) without κ).  A path's result depends only on its number, the seed and the model."""
+    import torch
+    kind, shapes = _shapes(model, shapes)
+    _check_grid(w_star, shapes, "w_star")
+    P = _count(n_paths, "n_paths", 1, 1 << 32)
+    T = _count(n_periods, "n_periods", 2, (1 << 32) - 1)
+    B = _count(burn_in, "burn_in", 0, (1 << 32) - 1)
+    off = _count(path_offset, "path_offset", 0, (1 << 32) - 1)
+    sd = _count(seed, "seed", 0, (1 << 64) - 1)
+    if off + P > 1 << 32:
+        raise ValueError(f"path_offset + n_paths = {off + P} > 2^32: path numbers are 32-bit")
+    if B + T >= 1 << 32:
+        raise ValueError(f"burn_in + n_periods = {B + T} >= 2^32: step numbers are 32-bit")
+    k = None if kappa is None else _kappa(kappa)
+    rtol = float(rtol)
+    if not (rtol > 0.0 and math.isfinite(rtol)):
+        raise ValueError(f"rtol must be positive, got {rtol!r}")
+    if return_paths and P * T > MAX_RETURNED:
+        raise ValueError(f"return_paths: n_paths * n_periods = {P * T} > 2^25 path-steps")
+    if isinstance(start, str):
+        if start != "stationary":
+            raise ValueError(f"start must be 'stationary' or one state index per axis, got {start!r}")
+        fixed = None
+    else:
+        fixed = tuple(start)
+        if len(fixed) != len(shapes):
+            raise ValueError(f"start needs one state index per axis ({len(shapes)}), got {len(fixed)}")
+        for a, (s, n) in enumerate(zip(fixed, shapes)):
+            if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < n:
+                raise ValueError(f"start[{a}] = {s!r}: a state index of axis {a} lies in 0 ... {n - 1}")
+        fixed = tuple(int(s) for s in fixed)
+    if isinstance(w_star, torch.Tensor):
+        w_ok = bool(torch.all(w_star > 1.0))
+    else:
+        w_ok = bool(np.all(np.asarray(w_star, dtype=np.float64) > 1.0))
+    if not w_ok:
+        raise ValueError("w_star must exceed 1 at every grid point (the log return needs ln(w - 1))")
+    arr = _kind(model)[2](model, shapes)
+    cdf, cdf0 = cdf_tables(model, shapes, arr)          # (ValueError when the chain does not factorise)
+    names = SERIES_KAPPA if k is not None else SERIES
+    ns = len(names)
+    N = int(np.prod(shapes))
+    need = N * REC_BYTES + (3 * ns + 1) * P * 8
+    if return_paths:
+        need += P * T * ns * 8 + P * (T + 1) * len(shapes)
+    free = torch.cuda.mem_get_info(torch.cuda.current_device())[0]
+    if need > free:
+        raise ValueError(f"the per-state records and outputs need {need / 2**30:.2f} GiB, {free / 2**30:.2f} GiB of "
+                         "device memory is free")
+
+    op, _ = _operator(model, shapes)
+    w = _device_grid(op, w_star, "w_star")
+    v = None
+    if k is not None:
+        v = _device_grid(op, claim_prices(model, shapes, w_star, k, rtol=rtol)["pd"], "pd")
+    dev = w.device
+    rec = torch.empty((N, 8), dtype=torch.float64, device=dev)
+    op.sim_records_dev(w.data_ptr(), v.data_ptr() if v is not None else None, rec.data_ptr())
+    stats = torch.empty((3 * ns + 1, P), dtype=torch.float64, device=dev)
+    idx = ser = None
+    if return_paths:
+        idx = torch.empty((P, T + 1, len(shapes)), dtype=torch.uint8, device=dev)
+        ser = torch.empty((ns, P, T), dtype=torch.float64, device=dev)
+    op.sim_paths_dev(rec.data_ptr(), np.concatenate([c.ravel() for c in cdf]),
+                     None if fixed is not None else np.concatenate(cdf0), sd, off, P, B, T, kappa=k, start=fixed,
+                     stats_ptr=stats.data_ptr(), idx_ptr=idx.data_ptr() if idx is not None else None,
+                     series_ptr=ser.data_ptr() if ser is not None else None)
+    st = stats.cpu().numpy()
+    per_path = {nm: {s: st[3 * i + j] for j, s in enumerate(STATS)} for i, nm in enumerate(names)}
+    per_path["slope"] = st[3 * ns]
+    summary = {nm: {s: _summary(per_path[nm][s]) for s in STATS} for nm in names}
+    summary["slope"] = _summary(per_path["slope"])
+    pooled = {}
+    for nm in names:
+        m = per_path[nm]["mean"]
+        pooled[nm] = {"mean": float(m.mean()), "se": float(m.std(ddof=1) / math.sqrt(P)) if P > 1 else float("nan")}
+    out = {"series": names, "per_path": per_path, "summary": summary, "pooled": pooled}
+    if return_paths:
+        s = ser.cpu().numpy()
+        paths = {"index": idx.cpu().numpy()}
+        for i, nm in enumerate(names):
+            paths[nm] = s[i]
+        out["paths"] = paths
+    del rec
+    return out
+
+
+__all__ = ["simulate", "cdf_tables"]
