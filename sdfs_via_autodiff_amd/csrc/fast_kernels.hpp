@@ -1547,24 +1547,17 @@ template <int N> inline line_fn line_variant_f32(int mode) {
     default: return nullptr;
   }
 }
-template <int N> inline line_fn line_variant_pf(int mode, bool persist, bool fullc, bool f32) {
-  if (f32) return (fullc && !persist) ? line_variant_f32<N>(mode) : nullptr;
-#ifdef SDFS_DIAG
-  // round 2's persistent form (SDFS_LINE_PERSIST; superseded by stream_kernels.hpp): diagnostic builds only -- the shipped
-  // library neither reads the knob nor carries these forty instantiations
-  if (persist) return fullc ? line_variant_n<N, true, true>(mode) : line_variant_n<N, true, false>(mode);
-#else
-  if (persist) return nullptr;
-#endif
+template <int N> inline line_fn line_variant_f(int mode, bool fullc, bool f32) {
+  if (f32) return fullc ? line_variant_f32<N>(mode) : nullptr;
   return fullc ? line_variant_n<N, false, true>(mode) : line_variant_n<N, false, false>(mode);
 }
 // fullc: lrest % 16 == 0 (no partial chunk anywhere in the pass); f32: fp32 storage of the J.v streams / of c2
-inline line_fn line_variant(int n, int mode, bool persist, bool fullc, bool f32 = false) {
+inline line_fn line_variant(int n, int mode, bool fullc, bool f32 = false) {
   switch (n) {
-    case 16: return line_variant_pf<16>(mode, persist, fullc, f32);
-    case 20: return line_variant_pf<20>(mode, persist, fullc, f32);
-    case 24: return line_variant_pf<24>(mode, persist, fullc, f32);
-    case 32: return line_variant_pf<32>(mode, persist, fullc, f32);
+    case 16: return line_variant_f<16>(mode, fullc, f32);
+    case 20: return line_variant_f<20>(mode, fullc, f32);
+    case 24: return line_variant_f<24>(mode, fullc, f32);
+    case 32: return line_variant_f<32>(mode, fullc, f32);
     default: return nullptr;
   }
 }

@@ -68,7 +68,7 @@ struct PassDesc {
   // lets the planner treat that axis as unconditional (longer contiguous runs in the last pass)
   const double* a3;
   long long ntiles;
-  int ablate;                  // -DSDFS_DIAG builds only (SDFS_ABLATE): 1 = skip the powers, 2 = skip the contractions
+  int ablate;                  // unused (always 0; kept so that the kernels' argument layout stays put)
   long long ref_off;           // grid offset of the mid-grid point (reference of the fp32 c1 / c2 scaling)
   double lin_ref;              // > 0: use this value as the reference instead (sharded handles: every rank and
                                // both stages must derive the same power of two, sdfs_set_krylov_f32)
@@ -674,13 +674,6 @@ __device__ __forceinline__ void contract_step(double* __restrict__ lds, const Pa
 #undef SDFS_CC
 }
 
-// timing diagnostics (skip the powers / the contractions: results are WRONG) exist only in -DSDFS_DIAG builds
-#ifdef SDFS_DIAG
-#define SDFS_ABL(P, bit) (((P).ablate & (bit)) != 0)
-#else
-#define SDFS_ABL(P, bit) false
-#endif
-
 #ifdef SDFS_STAMP
 #define STAMP(slot)                                                                        \
   do {                                                                                     \
@@ -850,7 +843,7 @@ pass_kernel(const PassDesc P, const PassIO io) {
 
   // ---- prologue x = a1 w^theta, in place in LDS (each thread revisits its own units).
   //      Uniform trip count: pow_fast needs every lane of the wave active.
-  if (POWP && !SDFS_ABL(P, 1)) {
+  if (POWP) {
     Walker wk;
     wk.init(tid, B, m1, m2u);
 #pragma unroll 1
@@ -881,15 +874,15 @@ pass_kernel(const PassDesc P, const PassIO io) {
   STAMP(4);
 
   // ---- contractions ------------------------------------------------------------------
-  if (P.nsteps > 0 && !SDFS_ABL(P, 2)) { contract_step(lds, P, 0, lane, wave, nwaves); STAMP(5); __syncthreads(); }
+  if (P.nsteps > 0) { contract_step(lds, P, 0, lane, wave, nwaves); STAMP(5); __syncthreads(); }
   STAMP(6);
-  if (P.nsteps > 1 && !SDFS_ABL(P, 2)) { contract_step(lds, P, 1, lane, wave, nwaves); STAMP(7); __syncthreads(); }
+  if (P.nsteps > 1) { contract_step(lds, P, 1, lane, wave, nwaves); STAMP(7); __syncthreads(); }
   STAMP(8);
-  if (P.nsteps > 2 && !SDFS_ABL(P, 2)) { contract_step(lds, P, 2, lane, wave, nwaves); STAMP(9); __syncthreads(); }
+  if (P.nsteps > 2) { contract_step(lds, P, 2, lane, wave, nwaves); STAMP(9); __syncthreads(); }
   STAMP(10);
 
   // ---- aggregator Tw = 1 + beta (K S)^(1/theta), in place in LDS (rolled, uniform) ------
-  if (CES && !SDFS_ABL(P, 1)) {
+  if (CES) {
     Walker wk;
     wk.init(tid, B, m1, m2u);
 #pragma unroll 1

@@ -84,7 +84,6 @@ struct EventPair { hipEvent_t a, b; int counter; };
 // "pair plan" (fast_kernels.hpp): one slice pass over the two fastest axes, then one line pass per slower pair
 struct FastPass {
   bool line = false;
-  bool persist = false;        // line pass: persistent workgroups with look-ahead into the next tile
   int stream = 0;              // line pass: stream_kernels.hpp's forms -- bit 0: as a middle pass (T and J.v, fp64), bit 1: as T's last pass
   int n = 0;
   int ax0 = -1, ax1 = -1;      // the contracted pair (ax0 slower)
@@ -108,31 +107,23 @@ struct FastPlan {
   std::vector<FastPass> passes;
 };
 
-// Diagnostic knobs (tools/README.md): read ONCE, when a handle is created -- never on a launch path
+// Run-time knobs (tools/README.md): read ONCE, when a handle is created -- never on a launch path
 struct Knobs {
-  int tile_budget = 0, filler_chunk = -1, force_waves = 0, no_occ_blocks = 0, no_pad = 0, no_vec2 = 0, no_vec4 = 0;
-  int no_dot_fusion = 0, no_slice_merge = 0, cont_no_tensor = 0, cont_lds_cap = 4000;
+  int no_slice_merge = 0;      // SDFS_NO_SLICE_MERGE: 1 = slice-identical conditional tensors stay conditional
   int no_and_push_fusion = 0;  // SDFS_NO_AND_PUSH_FUSION: 1 = Anderson on large grids keeps the push as a kernel of its own
   int no_f32_stream = 0;       // SDFS_NO_F32_STREAM: 1 = the fp32-MFMA middle pass keeps one tile per workgroup
-  int line_persist = 0;        // SDFS_LINE_PERSIST bit 0: middle line passes persistent, bit 1: last line pass persistent
-                               // (round 2's look-ahead form; measured equal to one tile per workgroup at GCY 20^6: off by default)
   int line_stream = 3;         // SDFS_LINE_STREAM: stream_kernels.hpp forms of the fp64 line passes; bit 0: middle pass, bit 1: T's
                                // last pass (both: on the extents they were measured on, n = 20), bit 2: on every extent
-  int pair_order = 1;          // SDFS_PAIR_ORDER: 1 = line passes slowest pair first (the last pass then walks the faster pair), 0 = fastest first
   int plan = 0;                // SDFS_PLAN: 0 = automatic, 1 = "classic" (generic tiles only), 2 = "pair" (pair plan whenever legal)
   int small_plan = 1;          // SDFS_SMALL_PLAN: 0 = never use the small-grid pair plan
   int small_r = 0;             // SDFS_SMALL_R: force the run length of its line passes (1 or 4)
   int small_wpt = 0;           // SDFS_SMALL_WPT: force its waves per tile (1 or 4)
   int pad_plan = 1;            // SDFS_PAD_PLAN: 0 = the grids between the plans keep the generic tiles; 2 = the padded plan also for
                                // shapes that mix extents above and below 16 (measured: no gain)
-  int small_xcd = 1;           // SDFS_SMALL_XCD (-DSDFS_DIAG builds only): 0 = its strided passes launch tile b on workgroup b (no XCD-aware order)
-  int no_bicg_merge = 0;       // SDFS_NO_BICG_MERGE: 1 = BiCGSTAB keeps its finishing kernels as launches of their own on small grids too
   int and_host = 0;            // SDFS_AND_HOST: 1 = Anderson with the Gram solve on the host (one synchronisation per iteration)
   int and_fused = 1;           // SDFS_AND_FUSED: 0 = Anderson on the small-grid plan keeps push / step / update as launches of their own
-  int a3_tables = 1;           // SDFS_A3_TABLES: 0 = the streamed last pass gathers a3 even where it factorises into two small tables
   int sa_fused = -1;           // SDFS_SA_FUSED: 0 = successive approximation keeps one launch per pass; 1 = fused end + start kernels;
                                // default (-1): fused on the small-grid plan, one launch per pass on the 6-D pair plan
-  int ablate = 0;              // SDFS_ABLATE, honoured only by -DSDFS_DIAG builds
 };
 
 }  // namespace
@@ -212,15 +203,13 @@ struct sdfs_handle {
     std::vector<double> tab_host;                             // its staging (kept alive across the async copy)
   } sim;
 
-  // Newton-Krylov with fp32 Krylov vectors / J.v streams (opts.krylov_f32); set while such a solve runs
-  bool krylov_f32 = false;
   std::vector<double> a3_host;       // host copy of the a3 table (the pair plan looks for its two-table form)
-  bool t32_active = false;           // successive approximation, opts.t_f32: T applications keep their intermediates as scaled floats
-  double t32_ref = 0.0;              // sharded handles (sdfs_set_t_f32): the reference value of that scale, the same on every rank
+  // sharded handles: the stage settings of sdfs_set_krylov_f32 / sdfs_set_t_f32 (sdfs_apply_stage_gated_dev's requests)
+  bool stage_f32 = false;            // J.v and linearising stages with fp32 Krylov storage
+  double lin_ref = 0.0;              // ... the reference value of the fp32 linearisation scale
+  bool stage_t32 = false;            // T stages with their intermediates as scaled floats
+  double t32_ref = 0.0;              // ... the reference value of that scale, the same on every rank
   bool check_every_default = false;  // the running solve was given check_every <= 0 (sdfs_solve_dev)
-  bool krylov_mfma32 = false;        // ... with the J.v passes of the pair plan on an fp32 LDS tile and fp32 MFMA (opts.krylov_f32 = 3: f32_kernels.hpp)
-  bool krylov_bf16 = false;          // ... with every store of those fp32 containers rounded to bfloat16 (opts.krylov_f32 = 2: bf16r, vec_kernels.hpp)
-  double lin_ref = 0.0;              // sharded handles: reference value of the fp32 linearisation scale (sdfs_set_krylov_f32)
   bool lin_stale = false;            // c1 / c2 hold the scaled floats of sdfs_debug_jvp_storage_dev: no fp64 J.v until the next
                                      // sdfs_linearize_dev / sdfs_param_tangent_dev
 
@@ -258,21 +247,12 @@ struct sdfs_handle {
   std::vector<EventPair> pending;
   std::vector<hipEvent_t> event_pool;
 
-  // graph cache for the SA chunk
-  const double* jvp_dot_with = nullptr;                // set around a J.v call: the last pass also sums <out, this> (small-grid plan)
-  // set around an application of T by the large-grid Anderson loop: the streamed last pass also does the pass's push
-  // (LineIO::and_*); `tiles` comes back as the number of partial sums it wrote (0: the pass was not a streamed one)
-  struct { double* y = nullptr; double* r = nullptr; double beta = 0.0; double* dot = nullptr; long long tiles = 0; } andpush;
-  // set around the J.v calls of a fused BiCGSTAB iteration on the compile-time pair plan (krylov_kernels.hpp): the first
-  // pass forms p or s on its registers (kind JF_P / JF_S, -1: plain first pass), the last pass is the streamed form with
-  // one workgroup per tile and, where dot_with is set, a third sum
-  struct { bool active = false; int kind = -1; double* upd = nullptr; const double* a = nullptr; const double* q = nullptr;
-           double* dot = nullptr; const double* dot_with = nullptr; } jf;
   double* jf_ss = nullptr; long long jf_ss_n = 0;     // per-wave-tile partial sums of <s, s>
   int bicg_graph_chunk[2] = {0, 0};                    // iterations in the captured graph
   hipGraphExec_t bicg_graph[2] = {nullptr, nullptr};   // one BiCGSTAB iteration (fp64 / fp32 Krylov storage)
   unsigned long long* bicg_gate = nullptr;             // device flag the iteration's kernels are gated on
   unsigned long long* bicg_gate_host = nullptr;        // pinned mirror
+  // graph cache for the SA chunk
   hipGraphExec_t sa_graph = nullptr;
   int sa_graph_chunk = 0;
   double sa_graph_tol = 0;   // the gate tolerance is baked into the captured kernel arguments
@@ -318,26 +298,6 @@ int env_int(const char* name, int dflt) {
 
 Knobs read_knobs() {
   Knobs k;
-#ifdef SDFS_DIAG
-  // planner / kernel-shape experiments of rounds 1-2: no test or tool sets them any more, so the shipped library does
-  // not read them (a stray variable cannot change the kernels that run); -DSDFS_DIAG builds still do
-  k.tile_budget = env_int("SDFS_TILE_BUDGET", 0);
-  k.filler_chunk = env_int("SDFS_FILLER_CHUNK", -1);
-  k.force_waves = env_int("SDFS_FORCE_WAVES", 0);
-  k.no_occ_blocks = env_int("SDFS_NO_OCC_BLOCKS", 0);
-  k.no_pad = env_int("SDFS_NO_PAD", 0);
-  k.no_vec2 = env_int("SDFS_NO_VEC2", 0);
-  k.no_vec4 = env_int("SDFS_NO_VEC4", 0);
-  k.no_dot_fusion = env_int("SDFS_NO_DOT_FUSION", 0);
-  k.cont_no_tensor = env_int("SDFS_CONT_NO_TENSOR", 0);
-  k.cont_lds_cap = env_int("SDFS_CONT_LDS_CAP", 4000);
-  k.no_bicg_merge = env_int("SDFS_NO_BICG_MERGE", 0);
-  k.small_xcd = env_int("SDFS_SMALL_XCD", 1);
-  // round 4: measured and settled in rounds 2-3, no test sets them any more
-  k.pair_order = env_int("SDFS_PAIR_ORDER", 1);
-  k.line_persist = env_int("SDFS_LINE_PERSIST", 0);
-  k.a3_tables = env_int("SDFS_A3_TABLES", 1);
-#endif
   k.no_slice_merge = env_int("SDFS_NO_SLICE_MERGE", 0);
   k.no_f32_stream = env_int("SDFS_NO_F32_STREAM", 0);
   k.no_and_push_fusion = env_int("SDFS_NO_AND_PUSH_FUSION", 0);
@@ -352,9 +312,6 @@ Knobs read_knobs() {
   const char* pl = getenv("SDFS_PLAN");
   if (pl && !strcmp(pl, "classic")) k.plan = 1;
   else if (pl && !strcmp(pl, "pair")) k.plan = 2;
-#ifdef SDFS_DIAG
-  k.ablate = env_int("SDFS_ABLATE", 0);
-#endif
   return k;
 }
 
@@ -372,8 +329,7 @@ int build_plan(sdfs_handle* h, Plan& plan, const std::vector<int>& todo_in, std:
     long long s = 1;
     for (int a = D - 1; a >= 0; --a) { stride[a] = s; s *= h->ax[a].nloc; }
   }
-  long long budget = h->knobs.tile_budget;
-  if (budget <= 0) budget = std::max<long long>(256, std::min<long long>(8192, nloc / 128));
+  const long long budget = std::max<long long>(256, std::min<long long>(8192, nloc / 128));
 
   std::vector<int> todo = todo_in;
   auto cond_ok = [&](int g, const std::vector<bool>& dn) {
@@ -429,13 +385,10 @@ int build_plan(sdfs_handle* h, Plan& plan, const std::vector<int>& todo_in, std:
       const bool want = (mincols < 16) || (nloc / e >= 512);
       if (e > budget || !want) break;
       tile = nt;
-      int fc = h->knobs.filler_chunk;
-      if (fc < 0) {
-        // automatic: a filler that makes the tile too big for more than two blocks per CU is taken in two
-        // halves (GCY 20^6 last pass: 20x10x20 tiles, four 256-thread blocks per CU, 0.384 -> 0.363 ms)
-        fc = 0;
-        if (pick != F && tile_elems(tile) * 8 > 53 * 1024 && h->ax[pick].nloc % 2 == 0) fc = h->ax[pick].nloc / 2;
-      }
+      // a filler that makes the tile too big for more than two blocks per CU is taken in two halves
+      // (GCY 20^6 last pass: 20x10x20 tiles, four 256-thread blocks per CU, 0.384 -> 0.363 ms)
+      int fc = 0;
+      if (pick != F && tile_elems(tile) * 8 > 53 * 1024 && h->ax[pick].nloc % 2 == 0) fc = h->ax[pick].nloc / 2;
       if (fc > 0 && chunk_axis < 0 && h->ax[pick].nloc % fc == 0 && fc < h->ax[pick].nloc &&
           tile_elems(tile) / h->ax[pick].nloc * fc / h->ax[G.back()].nloc >= 64) {
         chunk_axis = pick; chunk = fc;
@@ -496,7 +449,7 @@ int build_plan(sdfs_handle* h, Plan& plan, const std::vector<int>& todo_in, std:
     // LDS strides: pad the fastest stride to == 2 (mod 4) doubles when it is the
     // K dimension of an MFMA step (16 columns x 2 rows then hit 32 distinct b64 banks)
     int L1 = d.m[2];
-    if (contracts_fast_slot && d.m[1] * d.m[0] > 1 && h->knobs.no_pad == 0) { while ((L1 & 3) != 2) ++L1; }
+    if (contracts_fast_slot && d.m[1] * d.m[0] > 1) { while ((L1 & 3) != 2) ++L1; }
     d.L[2] = 1; d.L[1] = L1; d.L[0] = L1 * d.m[1];
     long long lds_elems = (long long)d.L[0] * d.m[0];
     lds_elems += lds_elems & 1;
@@ -521,20 +474,17 @@ int build_plan(sdfs_handle* h, Plan& plan, const std::vector<int>& todo_in, std:
         if (cost < best) { best = cost; w_mfma = w; }
       }
     }
-    int fw = h->knobs.force_waves;
     int waves = std::max(w_elem, w_mfma);
     // Resident waves per CU are capped at 16 by the ~128 VGPRs of the kernel.  Where LDS would allow more
     // than two blocks per CU (tiles well under 80 KB), smaller blocks keep those 16 waves but put more
     // independent blocks -- in different phases -- on the CU (GCY 16^6: 3031 -> 3519 iterations/s).
-    if (h->knobs.no_occ_blocks == 0) {
-      const int blocks_lds = (int)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(P.lds_bytes, 1));
-      if (blocks_lds > 2) {
-        int w = 2;                                  // power of two: 16-column tiles split evenly over the waves
-        while (2 * w <= 16 / blocks_lds) w *= 2;
-        waves = std::min(waves, w);
-      }
+    const int blocks_lds = (int)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(P.lds_bytes, 1));
+    if (blocks_lds > 2) {
+      int w = 2;                                    // power of two: 16-column tiles split evenly over the waves
+      while (2 * w <= 16 / blocks_lds) w *= 2;
+      waves = std::min(waves, w);
     }
-    P.block = 64 * (fw > 0 ? fw : waves);
+    P.block = 64 * waves;
     auto round_ept = [](long long e) { int r = 1; while (r < e) r <<= 1; return r; };
     auto units_per_thread = [&](long long units) { return round_ept((units + P.block - 1) / P.block); };
     while (units_per_thread(tot) > 16 && P.block < 512) P.block += 64;
@@ -545,8 +495,7 @@ int build_plan(sdfs_handle* h, Plan& plan, const std::vector<int>& todo_in, std:
     if (P.ept1 > 16) return fail(h, SDFS_ERR_UNSUPPORTED, "tile too large for one block");
     // 16-byte accesses: runs along slot 2 must be even, contiguous and every base even
     bool v2 = (d.m[2] % 2 == 0) && d.gstride[2] == 1 && (d.L[1] % 2 == 0) && (d.L[0] % 2 == 0) &&
-              (d.gstride[0] % 2 == 0 || d.m[0] == 1) && (d.gstride[1] % 2 == 0 || d.m[1] == 1) &&
-              h->knobs.no_vec2 == 0;
+              (d.gstride[0] % 2 == 0 || d.m[0] == 1) && (d.gstride[1] % 2 == 0 || d.m[1] == 1);
     for (int k = 0; k < d.nfixed; ++k) if (d.fstride[k] % 2 != 0 && d.fext[k] > 1) v2 = false;
     P.vec2 = v2;
     P.ept2 = v2 ? units_per_thread(tot / 2) : P.ept1;
@@ -632,6 +581,53 @@ int vec_grid(long long n) {
 // indices that are summed over).
 enum { MODE_T = 0, MODE_JVP = 1, MODE_T_LIN = 2, MODE_VJP = 3 };
 
+// storage precision of one application: fp64; the fp32 Krylov storage of opts.krylov_f32 = 1 / 2 / 3 (J.v streams, and c1 / c2
+// of a linearising T, as scaled floats; 2: every such store rounded to bfloat16; 3: the J.v passes of the pair plan on an fp32
+// LDS tile and fp32 MFMA); or opts.t_f32's intermediates of a plain T application as scaled floats
+enum { PREC_F64 = 0, PREC_F32 = 1, PREC_BF16 = 2, PREC_MFMA32 = 3, PREC_T32 = 4 };
+
+// One operator application: everything that selects and feeds its kernels besides the handle's cached state (the
+// linearisation c1 / c2, the plans, the buffers)
+struct Apply {
+  int mode;
+  const double* in; double* out; const double* old;
+  unsigned long long* resid = nullptr;          // T: max |T w - old| (the first pass clears the word)
+  const unsigned long long* gate = nullptr;     // every kernel returns at once while *gate <= gate_tol
+  double gate_tol = 0.0;
+  int minus_identity = 0;                       // J.v: out = J v - v
+  double* dotp = nullptr;                       // ... and its last pass writes per-workgroup partial sums of <out, in>, <out, out>
+  const double* lc1 = nullptr;                  // J.v scalings in place of the cached c1 / c2 (the tilted expectation's d1 / d2)
+  const double* lc2 = nullptr;
+  int prec = PREC_F64;
+  const double* dot_with = nullptr;             // small-grid plan: the last pass also sums <out, dot_with> (needs dotp)
+  // large-grid Anderson: the streamed last pass of T also does the push (LineIO::and_*); *tiles = the partial sums it
+  // wrote, 0 where the pass was not a streamed one
+  struct { double* y = nullptr; double* r = nullptr; double beta = 0.0; double* dot = nullptr; long long* tiles = nullptr; } push;
+  // fused BiCGSTAB iteration on the compile-time pair plan (krylov_kernels.hpp): the first pass forms p or s on its registers
+  // (kind JF_P / JF_S; -1: plain first pass), the last pass is the streamed form with one workgroup per tile and, where
+  // dot_with is set, a third sum
+  struct { int kind = -1; double* upd = nullptr; const double* a = nullptr; const double* q = nullptr; double* dot = nullptr;
+           const double* dot_with = nullptr; } bicg;
+  Apply(int mode_, const double* in_, double* out_, const double* old_) : mode(mode_), in(in_), out(out_), old(old_) {}
+  bool f32() const { return prec == PREC_F32 || prec == PREC_BF16 || prec == PREC_MFMA32; }   // fp32 Krylov storage
+};
+
+// counter, timing scope, launch and error check of one kernel of a plan (counter name "<tag>:<label>")
+template <typename Desc, typename IO>
+int launch_kernel(sdfs_handle* h, const void* fn, unsigned grid, int block, size_t lds, const Desc& d, const IO& io,
+                  const char* tag, const std::string& label, double bytes, double flops) {
+  int cid = -1;
+  if (h->profiling) {
+    char nm[48];
+    snprintf(nm, sizeof nm, "%s:%s", tag, label.c_str());
+    cid = counter_id(h, nm, bytes, flops);
+  }
+  ProfScope ps(h, cid);
+  hipLaunchKernelGGL((void (*)(const Desc, const IO))fn, dim3(grid), dim3(block), lds, h->stream, d, io);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 int launch_pass(sdfs_handle* h, Pass& P, int pro, int epi, const PassIO& io, int minus_identity,
                 const char* tag, double bytes, int prec = 0, bool transposed = false) {
   PassDesc d = P.d;
@@ -639,19 +635,13 @@ int launch_pass(sdfs_handle* h, Pass& P, int pro, int epi, const PassIO& io, int
     for (int s = 0; s < d.nsteps; ++s) d.Q[s] = h->ax[P.step_axes[s]].Qt;
   d.pro = pro; d.epi = epi; d.minus_identity = minus_identity;
   d.theta = h->theta; d.inv_theta = 1.0 / h->theta; d.beta = h->beta;
-  d.ablate = h->knobs.ablate;            // always 0 unless built with -DSDFS_DIAG
+  d.ablate = 0;
   d.a3 = (epi == EPI_CES || epi == EPI_CES_LIN) ? h->a3 : nullptr;
   d.ref_off = 0;
   d.lin_ref = h->sharded ? h->lin_ref : 0.0;
   if (!h->sharded) {                       // C-order offset of the mid-grid point
     long long stride = 1;
     for (int a = h->ndim - 1; a >= 0; --a) { d.ref_off += (long long)(h->shape[a] / 2) * stride; stride *= h->shape[a]; }
-  }
-  int cid = -1;
-  if (h->profiling) {
-    char nm[48];
-    snprintf(nm, sizeof nm, "%s:%s", tag, P.label.c_str());
-    cid = counter_id(h, nm, bytes, P.flops);
   }
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool v2 = P.vec2 && al16(io.in) && al16(io.out) && al16(io.aux_in) && al16(io.aux_out) && al16(io.old);
@@ -667,8 +657,7 @@ int launch_pass(sdfs_handle* h, Pass& P, int pro, int epi, const PassIO& io, int
   else if (epi == EPI_MUL) mode = M_JLAST;
   if (pro == PRO_MUL && epi == EPI_MUL) return fail(h, SDFS_ERR_UNSUPPORTED, "single-pass JVP not supported");
   const int block = P.block;
-  const bool v4 = v2 && P.vec4 && prec == 1 && (mode == M_JFIRST || mode == M_MID || mode == M_JLAST) &&
-                  h->knobs.no_vec4 == 0;
+  const bool v4 = v2 && P.vec4 && prec == 1 && (mode == M_JFIRST || mode == M_MID || mode == M_JLAST);
   const int vec = v4 ? 4 : (v2 ? 2 : 1), ept = v4 ? P.ept4 : (v2 ? P.ept2 : P.ept1);
   pass_fn fn = pass_kernel_variant(ept, vec, mode, prec);
   if (!fn) return fail(h, SDFS_ERR_UNSUPPORTED, "no kernel variant for EPT %d VEC %d", ept, vec);
@@ -702,10 +691,7 @@ int launch_pass(sdfs_handle* h, Pass& P, int pro, int epi, const PassIO& io, int
   }
   return 0;
 #endif
-  ProfScope ps(h, cid);
-  hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(block), P.lds_bytes, h->stream, d, io);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return launch_kernel(h, (const void*)fn, (unsigned)grid, block, P.lds_bytes, d, io, tag, P.label, bytes, P.flops);
 }
 
 int ensure_tmp(sdfs_handle* h) {
@@ -807,6 +793,40 @@ int upload_ints(sdfs_handle* h, const std::vector<int>& v, int** out) {
   return 0;
 }
 
+// Index tables of the aggregator's a3 gather in a pass over the pair (a, a + 1) of a block of the grid (shp = local extents,
+// off = global index of local index 0): a3 index = out_idx[outer] + x a3s[X] + y a3s[Y] + rest_idx[position behind Y].
+// The host copies stay in outv / restv, the device copies in od / rd.
+int a3_index_tables(sdfs_handle* h, const int* shp, const int* off, int a, std::vector<int>& outv, std::vector<int>& restv,
+                    int** od, int** rd) {
+  const int D = h->ndim;
+  long long nouter = 1, lrest = 1;
+  for (int c = 0; c < a; ++c) nouter *= shp[c];
+  for (int c = a + 2; c < D; ++c) lrest *= shp[c];
+  outv.assign((size_t)nouter, 0);
+  restv.assign((size_t)lrest, 0);
+  for (long long o = 0; o < nouter; ++o) {
+    long long r = o; int idx = 0;
+    for (int c = a - 1; c >= 0; --c) { idx += (off[c] + (int)(r % shp[c])) * h->ax[c].a3s; r /= shp[c]; }
+    outv[(size_t)o] = idx;
+  }
+  for (long long q = 0; q < lrest; ++q) {
+    long long r = q; int idx = 0;
+    for (int c = D - 1; c > a + 1; --c) { idx += (off[c] + (int)(r % shp[c])) * h->ax[c].a3s; r /= shp[c]; }
+    restv[(size_t)q] = idx;
+  }
+  int rc;
+  if ((rc = upload_ints(h, outv, od)) || (rc = upload_ints(h, restv, rd))) return rc;
+  return 0;
+}
+
+// Pair order of the pair, small-grid and padded plans: the two fastest axes (the first pass), then the slower pairs slowest
+// first, so that the last pass walks the pair whose rows lie closest together.  Entries: the slower axis of each pair.
+std::vector<int> pair_order(int D) {
+  std::vector<int> pairs = {D - 2};
+  for (int a = 0; a <= D - 4; a += 2) pairs.push_back(a);
+  return pairs;
+}
+
 // One pass of the pair plan over a block of the grid: shp = local extents (a sharded stage holds a block of one axis,
 // the whole-grid plan all of every axis), off = global index of local index 0 on every axis.
 void make_slice_pass(sdfs_handle* h, const int* shp, FastPass& P) {
@@ -850,21 +870,10 @@ int make_line_pass(sdfs_handle* h, const int* shp, const int* off, int a, bool t
   P.label = std::string("lines[") + h->ax[a].name + "," + h->ax[a + 1].name + "|" + std::to_string(n) + "x" +
             std::to_string(n) + "x16 tile]";
   if (!tables) return 0;
-  // index tables of the aggregator's a3 gather: a3 index = out_idx[outer] + x a3s[X] + y a3s[Y] + rest_idx[position behind Y]
-  std::vector<int> outv((size_t)L.nouter, 0), restv((size_t)L.lrest, 0);
-  for (long long o = 0; o < L.nouter; ++o) {
-    long long r = o; int idx = 0;
-    for (int c = a - 1; c >= 0; --c) { idx += (off[c] + (int)(r % shp[c])) * h->ax[c].a3s; r /= shp[c]; }
-    outv[(size_t)o] = idx;
-  }
-  for (long long q = 0; q < L.lrest; ++q) {
-    long long r = q; int idx = 0;
-    for (int c = D - 1; c > a + 1; --c) { idx += (off[c] + (int)(r % shp[c])) * h->ax[c].a3s; r /= shp[c]; }
-    restv[(size_t)q] = idx;
-  }
+  std::vector<int> outv, restv;
   int *od = nullptr, *rd = nullptr;
   int rc;
-  if ((rc = upload_ints(h, outv, &od)) || (rc = upload_ints(h, restv, &rd))) return rc;
+  if ((rc = a3_index_tables(h, shp, off, a, outv, restv, &od, &rd))) return rc;
   L.a3 = h->a3; L.out_idx = od; L.rest_idx = rd;
   // The aggregator's scale as two small tables (lever iii): for Rouwenhorst / Tauchen grids of the
   // GCY model z_states = sigma_z[h_z] g[z] + m[h_zpi, z_pi], so a3 = exp((1 - gamma)(mu_c + z_states)) is, for every
@@ -910,12 +919,11 @@ int prepare_fast_passes(sdfs_handle* h, std::vector<FastPass>& passes) {
       slice_fn f32 = slice_variant(P.n, m, true);
       if (f32) hipFuncSetAttribute((const void*)f32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slice_lds_bytes(P.n, m));
       if (slice_fn m32 = slice32_variant(P.n)) hipFuncSetAttribute((const void*)m32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slice32_lds_bytes(P.n));
-    } else for (int m = 0; m < L_NMODES; ++m) for (int pe = 0; pe < 2; ++pe) {
-      line_fn f = line_variant(P.n, m, pe != 0, P.ld.lrest % LINE_R == 0);
-      if (!f && pe != 0) continue;                           // (the persistent form exists in diagnostic builds only)
+    } else for (int m = 0; m < L_NMODES; ++m) {
+      line_fn f = line_variant(P.n, m, P.ld.lrest % LINE_R == 0);
       if (!f) return 1;
       hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)line_lds_bytes(P.n));
-      line_fn f32 = line_variant(P.n, m, false, true, true);
+      line_fn f32 = line_variant(P.n, m, true, true);
       if (f32) hipFuncSetAttribute((const void*)f32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)line_lds_bytes(P.n));
       for (int r32 = 16; r32 <= 32; r32 += 16) for (int d3 = 0; d3 < 2; ++d3)
         if (line_fn m32 = line32_variant(P.n, m, r32, d3 != 0)) hipFuncSetAttribute((const void*)m32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)line32_lds_bytes(P.n, r32));
@@ -978,11 +986,10 @@ int build_fast_plan(sdfs_handle* h) {
   std::vector<FastPass> passes(1);
   make_slice_pass(h, h->shape, passes[0]);
   long long min_tiles = 1LL << 60;
-  std::vector<int> line_axes;
-  for (int a = D - 4; a >= 0; a -= 2) line_axes.push_back(a);
-  if (h->knobs.pair_order == 1) std::reverse(line_axes.begin(), line_axes.end());
+  const std::vector<int> pairs = pair_order(D);
   // (successive approximation ends its applications on either line pair in turn: a3 tables for every line pass)
-  for (int a : line_axes) {
+  for (size_t i = 1; i < pairs.size(); ++i) {
+    const int a = pairs[i];
     FastPass P;
     const int rc = make_line_pass(h, h->shape, zero, a, true, P);
     if (rc == 1) return 0;
@@ -999,8 +1006,6 @@ int build_fast_plan(sdfs_handle* h) {
   bool f32_ok = true;
   for (const FastPass& P : passes) if (P.line && P.ld.lrest % LINE_R != 0) f32_ok = false;
   h->fast.f32_ok = f32_ok;
-  for (size_t i = 0; i < passes.size(); ++i)
-    if (passes[i].line) passes[i].persist = (h->knobs.line_persist >> (i + 1 == passes.size() ? 1 : 0)) & 1;
   h->fast.passes = passes;
   h->fast.ok = true;
   return 0;
@@ -1057,14 +1062,8 @@ int build_small_plan(sdfs_handle* h) {
   }
   long long stride[MAXD];
   { long long st = 1; for (int a = D - 1; a >= 0; --a) { stride[a] = st; st *= h->shape[a]; } }
-  std::vector<int> pairs;
-  pairs.push_back(D - 2);
-  {
-    std::vector<int> rest;
-    for (int a = D - 4; a >= 0; a -= 2) rest.push_back(a);
-    if (h->knobs.pair_order == 1) std::reverse(rest.begin(), rest.end());
-    pairs.insert(pairs.end(), rest.begin(), rest.end());
-  }
+  const std::vector<int> pairs = pair_order(D);
+  const int zero[MAXD] = {0, 0, 0, 0, 0, 0};
   std::vector<FastPass> passes;
   for (size_t i = 0; i < pairs.size(); ++i) {
     const int a = pairs[i];
@@ -1093,7 +1092,7 @@ int build_small_plan(sdfs_handle* h) {
     // strided pass with as many workgroups as fit the GPU at once: neighbouring tiles (they share their 128-byte
     // lines) to the same XCD (tools/probes/anderson_fused_probe.hip: 15^4 pair of passes 7.8 -> 7.0 us)
     S.cpx = 0;
-    if (lrest > 1 && h->knobs.small_xcd && small_grid(S.ntiles, P.wpt) <= 2u * (unsigned)h->num_cus) S.cpx = small_cpx(S.ntiles, P.wpt);
+    if (lrest > 1 && small_grid(S.ntiles, P.wpt) <= 2u * (unsigned)h->num_cus) S.cpx = small_cpx(S.ntiles, P.wpt);
     S.Qxp = h->ax[a].Qp; S.Qyp = h->ax[a + 1].Qp;
     S.theta = h->theta; S.inv_theta = 1.0 / h->theta; S.beta = h->beta;
     S.cbt = (double)powl((long double)h->beta, (long double)h->theta);
@@ -1104,20 +1103,10 @@ int build_small_plan(sdfs_handle* h) {
     if (P.wpt == 4) P.label.replace(P.label.find("|wave "), 6, "|workgroup ");
     // a3 index tables: the last pass of T needs them, and successive approximation ends on either end pair
     if (i + 1 == pairs.size() || i == 0) {
-      std::vector<int> outv((size_t)nouter, 0), restv((size_t)lrest, 0);
-      for (long long o = 0; o < nouter; ++o) {
-        long long q = o; int idx = 0;
-        for (int c = a - 1; c >= 0; --c) { idx += (int)(q % h->shape[c]) * h->ax[c].a3s; q /= h->shape[c]; }
-        outv[(size_t)o] = idx;
-      }
-      for (long long q0 = 0; q0 < lrest; ++q0) {
-        long long q = q0; int idx = 0;
-        for (int c = D - 1; c > a + 1; --c) { idx += (int)(q % h->shape[c]) * h->ax[c].a3s; q /= h->shape[c]; }
-        restv[(size_t)q0] = idx;
-      }
+      std::vector<int> outv, restv;
       int *od = nullptr, *rd = nullptr;
-      int rc;
-      if ((rc = upload_ints(h, outv, &od)) || (rc = upload_ints(h, restv, &rd))) return rc;
+      const int rc = a3_index_tables(h, h->shape, zero, a, outv, restv, &od, &rd);
+      if (rc) return rc;
       S.a3 = h->a3; S.out_idx = od; S.rest_idx = rd;
     }
     passes.push_back(P);
@@ -1153,13 +1142,8 @@ int build_pad_plan(sdfs_handle* h) {
   }
   long long stride[MAXD];
   { long long st = 1; for (int a = D - 1; a >= 0; --a) { stride[a] = st; st *= h->shape[a]; } }
-  std::vector<int> pairs = {D - 2};
-  {
-    std::vector<int> rest;
-    for (int a = D - 4; a >= 0; a -= 2) rest.push_back(a);
-    if (h->knobs.pair_order == 1) std::reverse(rest.begin(), rest.end());
-    pairs.insert(pairs.end(), rest.begin(), rest.end());
-  }
+  const std::vector<int> pairs = pair_order(D);
+  const int zero[MAXD] = {0, 0, 0, 0, 0, 0};
   std::vector<FastPass> passes;
   for (size_t i = 0; i < pairs.size(); ++i) {
     const int a = pairs[i];
@@ -1190,21 +1174,11 @@ int build_pad_plan(sdfs_handle* h) {
       for (int lm : {L_MID, L_TLAST, L_TLAST_LIN, L_JLAST})
         hipFuncSetAttribute((const void*)pad_line_variant(P.nt, lm, lrest % 2 == 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_line_lds(P.nt));
     if (i + 1 == pairs.size()) {
-      // a3 index tables of the last pass (as build_small_plan)
-      std::vector<int> outv((size_t)nouter, 0), restv((size_t)lrest, 0);
-      for (long long o = 0; o < nouter; ++o) {
-        long long q = o; int idx = 0;
-        for (int c = a - 1; c >= 0; --c) { idx += (int)(q % h->shape[c]) * h->ax[c].a3s; q /= h->shape[c]; }
-        outv[(size_t)o] = idx;
-      }
-      for (long long q0 = 0; q0 < lrest; ++q0) {
-        long long q = q0; int idx = 0;
-        for (int c = D - 1; c > a + 1; --c) { idx += (int)(q % h->shape[c]) * h->ax[c].a3s; q /= h->shape[c]; }
-        restv[(size_t)q0] = idx;
-      }
+      // a3 index tables of the last pass
+      std::vector<int> outv, restv;
       int *od = nullptr, *rd = nullptr;
-      int rc;
-      if ((rc = upload_ints(h, outv, &od)) || (rc = upload_ints(h, restv, &rd))) return rc;
+      const int rc = a3_index_tables(h, h->shape, zero, a, outv, restv, &od, &rd);
+      if (rc) return rc;
       S.a3 = h->a3; S.out_idx = od; S.rest_idx = rd;
     }
     passes.push_back(P);
@@ -1227,294 +1201,331 @@ unsigned stream_mid_grid(const sdfs_handle* h, const FastPass& P) {
   return (unsigned)std::max<long long>(g, 8);
 }
 
-// persistent line kernel: at most its resident workgroups per CU, each walking tiles b, b + grid, ...
-unsigned line_grid(const sdfs_handle* h, const FastPass& P) {
-  if (!P.persist) return (unsigned)P.ld.ntiles;
-  return (unsigned)std::min<long long>(P.ld.ntiles, (long long)line_blocks_per_cu(P.n) * h->num_cus);
-}
-
 // bf16r emulation (opts.krylov_f32 = 2): round an fp32 stream a J.v / linearising pass has just written
 int round_stream_bf16_n(sdfs_handle* h, void* p, long long n, const unsigned long long* gate) {
   hipLaunchKernelGGL(k_round_bf16, dim3(std::min<long long>((n / 4 + 255) / 256 + 1, 8192)), dim3(256), 0, h->stream, (float*)p, n, gate);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
-int round_stream_bf16(sdfs_handle* h, void* p, const unsigned long long* gate) { return round_stream_bf16_n(h, p, (long long)h->N, gate); }
 
-// fp = the whole-grid pair plan (has_first and has_last), or one stage of a sharded handle (build_stage_fast_plans:
-// stage 0 holds the first pass, stage 1 the last); nloc = grid points of the block
-int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, bool has_last, int mode, const double* in, double* out,
-                  const double* old, unsigned long long* resid, const unsigned long long* gate, double gate_tol, int minus_identity,
-                  double* dotp, const double* lc1 = nullptr, const double* lc2 = nullptr) {
-  const bool vjp = mode == MODE_VJP;       // the J.v launches with transposed matrices and c1 / c2 swapped (fp64)
-  if (vjp) mode = MODE_JVP;
-  // J.v scalings: the cached linearisation, or the caller's (lc1, lc2: the tilted expectation's d1 / d2)
-  const double* const C1 = lc1 ? lc1 : h->c1;
-  const double* const C2 = lc2 ? lc2 : h->c2;
+// What pass i of a pair / small-grid / padded plan launches for request `a`: kernel, geometry, counter.  The one place that
+// picks the form of a pass -- run_fast_plan launches it, sdfs_describe_plan prints it, the fused dot products of BiCGSTAB
+// size their partial sums by its grid.
+struct PassLaunch {
+  const void* fn = nullptr;
+  unsigned grid = 0;
+  int block = 256;
+  size_t lds = 0;
+  double bytes = 0;                  // algorithmic bytes of the counter
+  const char* tag = "";              // counter name "<tag>:<pass label>"
+  int kmode = 0;                     // the kernel's mode: S_* (slice passes), SM_* (small grid), L_* (line passes)
+  bool jfused = false;               // first pass with BiCGSTAB's p / s update (JFusedIO, JFused32IO with m32)
+  bool m32 = false;                  // fp32-MFMA form (f32_kernels.hpp, krylov_kernels.hpp)
+  bool persistent = false;           // ... its persistent middle pass, next tile in flight
+  bool push = false;                 // T's streamed last pass with the Anderson push
+  const double* dot_with = nullptr;  // J.v's last pass also sums <out, dot_with>
+  const char* err = nullptr;         // no kernel for this pass
+  int err_code = SDFS_ERR_UNSUPPORTED;
+};
+
+PassLaunch select_pass(const sdfs_handle* h, const FastPlan& fp, int i, long long nloc, bool has_first, bool has_last,
+                       const Apply& a) {
+  PassLaunch L;
+  const FastPass& P = fp.passes[i];
+  const bool vjp = a.mode == MODE_VJP;       // the J.v kernels with transposed matrices and c1 / c2 swapped (fp64)
+  const int mode = vjp ? MODE_JVP : a.mode;
+  // fp32 Krylov storage: every stream of a J.v application holds floats; a linearising T keeps fp64 streams and writes
+  // only c1 (first pass) and c2 (last pass) as scaled floats
+  const bool f32 = !vjp && a.f32() && mode != MODE_T;
+  // opts.t_f32: the intermediates between the passes of a plain T application as scaled floats (whole chunks everywhere)
+  // (a sharded handle's stages, sdfs_set_t_f32: stage 0 then WRITES floats -- the exchange moves half the bytes -- and
+  // stage 1 reads them)
+  const bool t32 = mode == MODE_T && a.prec == PREC_T32 && fp.f32_ok && !fp.small &&
+                   ((has_first && has_last) || (h->sharded && h->t32_ref > 0.0));
+  const bool last = has_last && i == (int)fp.passes.size() - 1;
+  const double n8 = 8.0 * (double)nloc;
+  L.tag = t32 ? "T32" : vjp ? "vjp" : (mode == MODE_JVP) ? (f32 ? "jvp32" : "jvp") : (mode == MODE_T_LIN ? "Tlin" : "T");
+  L.bytes = 2 * n8 + P.q_bytes;
+  // first pass: c1 written (linearising T) or read (J.v); last pass: the epilogue's extra streams
+  const int first_bytes = mode == MODE_T ? 0 : 1;
+  auto last_mode = [&](int t, int tlin, int j) {
+    if (mode == MODE_T) { if (a.resid) L.bytes += n8; return t; }
+    L.bytes += n8;
+    if (mode == MODE_T_LIN) { if (a.resid) L.bytes += n8; return tlin; }
+    if (a.minus_identity) L.bytes += n8;
+    return j;
+  };
+  if (P.pad) {
+    if (!P.line) {
+      L.kmode = mode == MODE_T_LIN ? S_TFIRST_LIN : (mode == MODE_JVP ? S_JFIRST : S_TFIRST);
+      L.bytes += first_bytes * n8;
+      L.fn = (const void*)pad_slice_variant(P.nt, L.kmode, P.pd.nx * P.pd.ny);
+      L.grid = (unsigned)(((P.pd.nslices + pad_slice_g(P.nt) - 1) / pad_slice_g(P.nt) + 3) / 4);
+    } else {
+      L.kmode = last ? last_mode(L_TLAST, L_TLAST_LIN, L_JLAST) : L_MID;
+      L.fn = (const void*)pad_line_variant(P.nt, L.kmode, P.pd.lrest % 2 == 0);
+      L.grid = (unsigned)P.pd.ntiles; L.block = pad_line_block(P.nt); L.lds = pad_line_lds(P.nt);
+    }
+    if (!L.fn) L.err = "no padded-plan kernel variant";
+    return L;
+  }
+  if (P.small) {
+    if (i == 0) {
+      L.kmode = mode == MODE_T ? SM_FIRST_T : (mode == MODE_T_LIN ? SM_FIRST_TLIN : SM_FIRST_J);
+      L.bytes += first_bytes * n8;
+    } else if (last) {
+      L.kmode = last_mode(SM_LAST_T, SM_LAST_TLIN, SM_LAST_J);
+      if (mode == MODE_JVP && a.dotp && a.dot_with) { L.dot_with = a.dot_with; L.bytes += n8; }
+    } else L.kmode = SM_MID;
+    L.fn = (const void*)small_variant(L.kmode, P.r, P.wpt);
+    L.grid = small_grid(P.sm, P.wpt);
+    if (!L.fn) L.err = "no small-grid kernel variant";
+    return L;
+  }
+  // opts.krylov_f32 = 3: fp32 LDS tile + fp32 MFMA for the J.v passes (f32_kernels.hpp)
+  const bool m32 = f32 && a.prec == PREC_MFMA32 && mode == MODE_JVP && !t32;
+  const bool bicg = mode == MODE_JVP && !vjp && a.bicg.kind >= 0;
+  L.m32 = m32;
+  if (!P.line) {
+    int sm = S_TFIRST;
+    if (t32) { sm = S_TFIRST32; L.bytes -= 0.5 * n8; }
+    if (mode == MODE_T_LIN) sm = S_TFIRST_LIN;
+    else if (mode == MODE_JVP) sm = S_JFIRST;
+    L.bytes += first_bytes * n8;
+    L.kmode = sm;
+    const int gsl = m32 ? slice32_tile_slices(P.n) : slice_tile_slices(P.n, sm);
+    L.lds = m32 ? slice32_lds_bytes(P.n) : slice_lds_bytes(P.n, sm);
+    if (bicg && (!f32 || m32)) {
+      // BiCGSTAB's p / s update on the registers of this pass (krylov_kernels.hpp; fp32-MFMA: vectors, c1 and the output
+      // are floats)
+      const int kind = a.bicg.kind;
+      if (!m32 && a.lc1) { L.err = "the fused BiCGSTAB first pass reads the cached linearisation only"; L.err_code = SDFS_ERR_ARG; return L; }
+      L.jfused = true;
+      L.fn = m32 ? (const void*)slice32_jfused_variant(P.n, kind) : (const void*)slice_jfused_variant(P.n, kind);
+      if (!L.fn) L.err = m32 ? "no fused fp32 first pass for this extent" : "no fused first pass for this extent";
+      L.bytes = (m32 ? 0.5 : 1.0) * (kind == JF_P ? 6.0 : 5.0) * n8 + P.q_bytes;
+      L.tag = m32 ? (kind == JF_P ? "jvpm32+p" : "jvpm32+s") : (kind == JF_P ? "jvp+p" : "jvp+s");
+    } else {
+      L.fn = m32 ? (const void*)slice32_variant(P.n) : (const void*)slice_variant(P.n, sm, f32);
+      if (!L.fn) L.err = "no slice kernel variant";
+      if (f32 && mode == MODE_JVP) L.bytes *= 0.5;
+      if (m32) L.tag = "jvpm32";
+    }
+    L.grid = (unsigned)(((P.sd.nslices + gsl - 1) / gsl + 3) / 4);
+    return L;
+  }
+  const int lm = last ? last_mode(L_TLAST, L_TLAST_LIN, L_JLAST) : L_MID;
+  const bool lf32 = f32 && (mode == MODE_JVP || lm == L_TLAST_LIN);
+  const bool a3f = P.ld.f1 != nullptr;
+  L.kmode = lm;
+  line_fn fn = lf32 ? line_variant(P.n, lm, true, true) : line_variant(P.n, lm, P.ld.lrest % LINE_R == 0);
+  unsigned grid = (unsigned)P.ld.ntiles;
+  if (t32) {
+    // fp32 intermediate: the fp32 middle form, or the last pass on a float tile (stream_kernels.hpp) ...
+    fn = last ? line_tlast32_variant(P.n) : line_variant(P.n, L_MID, true, true);
+    L.bytes -= last ? 0.5 * n8 : n8;
+    // ... on the streamed forms where the fp64 passes run them (stream_kernels.hpp, IN32 / OUT32)
+    if ((P.stream & (last ? 2 : 1)) && h->knobs.no_f32_stream == 0) {
+      if (line_fn sf = line_stream_t32_variant(P.n, last ? L_TLAST : L_MID, a3f)) {
+        fn = sf;
+        if (!last) {
+          long long g = std::min<long long>(P.ld.ntiles, (long long)line_stream_wpc_mid32(P.n) * h->num_cus);
+          g -= g % 8;
+          grid = (unsigned)std::max<long long>(g, 8);
+        }
+      }
+    }
+  } else if (!lf32 && ((lm == L_MID && (P.stream & 1)) || ((lm == L_TLAST || lm == L_TLAST_LIN) && (P.stream & 2)))) {
+    // stream_kernels.hpp: persistent middle pass with the next tile in flight; last pass with its side stream loaded early
+    fn = line_stream_variant(P.n, lm, a3f);
+    if (lm == L_MID) grid = stream_mid_grid(h, P);
+    if (lm == L_TLAST && a.push.r != nullptr && a.old != nullptr && P.ld.ntiles <= (long long)MAX_PARTIAL_BLOCKS * AND_MAX_M) {
+      L.push = true;
+      L.bytes += 3 * n8;                                   // x read, y and r written
+    }
+  }
+  if (lm == L_JLAST && !lf32 && bicg) {
+    // fused BiCGSTAB iteration: the streamed last pass, one workgroup per tile (the partial sums are counted per tile)
+    fn = line_stream_variant(P.n, L_JLAST);
+    L.dot_with = a.bicg.dot_with;
+    L.bytes += 0.5 * n8;       // (rhat is read by the first of an iteration's two applications: one counter, their mean)
+  }
+  if (m32) {
+    const int r32 = line32_row_floats(P.n, P.ld.lrest);
+    fn = line32_variant(P.n, lm, r32);
+    grid = (unsigned)(P.ld.ntiles * LINE_R / r32);
+    if (lm == L_MID && (P.stream & 1) && grid >= 8u * TK_SUB && h->knobs.no_f32_stream == 0) {
+      // persistent form, next tile in flight (krylov_kernels.hpp); a multiple of 8 workgroups, one ticket range per XCD
+      if (line_fn sf = line32_stream_mid_variant(P.n, r32)) {
+        long long g = std::min<long long>(grid, (long long)line32_stream_wpc(P.n, r32) * h->num_cus);
+        g -= g % (8 * TK_SUB);
+        fn = sf; grid = (unsigned)g;
+        L.persistent = true;
+      }
+    }
+    if (lm == L_JLAST && bicg) {
+      L.dot_with = a.bicg.dot_with;
+      L.bytes += n8;            // (halved below: the mean of the two applications)
+      if (L.dot_with) fn = line32_variant(P.n, lm, r32, true);
+    }
+    L.tag = "jvpm32"; L.block = 256; L.lds = line32_lds_bytes(P.n, r32);
+  } else {
+    L.block = line_block(P.n); L.lds = line_lds_bytes(P.n);
+  }
+  if (f32 && mode == MODE_JVP) L.bytes *= 0.5;
+  L.fn = (const void*)fn;
+  L.grid = grid;
+  if (!fn) L.err = "no line kernel variant";
+  return L;
+}
+
+// fp = the whole-grid pair / small-grid / padded plan (has_first and has_last), or one stage of a sharded handle
+// (build_stage_fast_plans: stage 0 holds the first pass, stage 1 the last); nloc = grid points of the block
+int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, bool has_last, const Apply& a) {
+  const bool vjp = a.mode == MODE_VJP;
+  const int mode = vjp ? MODE_JVP : a.mode;
+  // J.v scalings: the cached linearisation, or the caller's (the tilted expectation's d1 / d2)
+  const double* const C1 = a.lc1 ? a.lc1 : h->c1;
+  const double* const C2 = a.lc2 ? a.lc2 : h->c2;
   int rc = ensure_tmp(h);
   if (rc) return rc;
   if (mode != MODE_T) { rc = ensure_lin(h); if (rc) return rc; }
   const int np = (int)fp.passes.size();
-  const double n8 = 8.0 * (double)nloc;
-  // fp32 Krylov storage: every stream of a J.v application holds floats; a linearising T keeps fp64 streams
-  // and writes only c1 (first pass) and c2 (last pass) as scaled floats
-  const bool f32 = !vjp && h->krylov_f32 && mode != MODE_T;
-  // opts.t_f32: the intermediates between the passes of a plain T application as scaled floats (whole chunks everywhere)
-  // (a sharded handle's stages, sdfs_set_t_f32: stage 0 then WRITES floats -- the exchange moves half the bytes -- and stage 1
-  // reads them)
-  const bool t32 = mode == MODE_T && h->t32_active && fp.f32_ok && !fp.small && ((has_first && has_last) || (h->sharded && h->t32_ref > 0.0));
-  const char* tag = t32 ? "T32" : vjp ? "vjp" : (mode == MODE_JVP) ? (f32 ? "jvp32" : "jvp") : (mode == MODE_T_LIN ? "Tlin" : "T");
+  const bool bf16 = !vjp && a.prec == PREC_BF16 && mode != MODE_T;
+  // the first pass clears the word the last pass maximises into, and reads / writes c1; the last one reads / writes c2
+  auto first_io = [&](auto& io) {
+    io.zero = (mode != MODE_JVP) ? a.resid : nullptr;
+    if (mode == MODE_T_LIN) io.aux_out = h->c1;
+    else if (mode == MODE_JVP) io.aux_in = vjp ? C2 : C1;
+  };
+  auto last_io = [&](auto& io) {
+    io.old = a.old;
+    if (mode == MODE_JVP) { io.aux_in = vjp ? C1 : C2; if (a.minus_identity) io.dotp = a.dotp; return; }
+    io.resid = a.resid;
+    if (mode == MODE_T_LIN) io.aux_out = h->c2;
+  };
   for (int i = 0; i < np; ++i) {
-    FastPass& P = fp.passes[i];
+    const FastPass& P = fp.passes[i];
     const bool last = has_last && i == np - 1;
-    double bytes = 2 * n8 + P.q_bytes;
-    const double* pin = (i == 0) ? in : h->tmp;
-    double* pout = (i == np - 1) ? out : h->tmp;
+    const PassLaunch L = select_pass(h, fp, i, nloc, has_first, has_last, a);
+    if (L.err) return fail(h, L.err_code, "%s", L.err);
+    const double* pin = (i == 0) ? a.in : h->tmp;
+    double* pout = (i == np - 1) ? a.out : h->tmp;
     if (P.pad) {
       PadDesc d = P.pd;
-      d.minus_identity = minus_identity;
+      d.minus_identity = a.minus_identity;
       const int cls = P.nt == 16 ? 0 : (P.nt == 20 ? 1 : (P.nt == 24 ? 2 : 3));
       if (vjp) { d.Qx = h->ax[P.ax0].Qtpad[cls]; d.Qy = h->ax[P.ax1].Qtpad[cls]; }
-      int cid = -1;
       if (!P.line) {
         SliceIO io;
         memset(&io, 0, sizeof io);
-        io.in = pin; io.out = pout; io.gate = gate; io.gate_tol = gate_tol;
-        io.zero = (mode != MODE_JVP) ? resid : nullptr;
-        int sm = S_TFIRST;
-        if (mode == MODE_T_LIN) { sm = S_TFIRST_LIN; io.aux_out = h->c1; bytes += n8; }
-        else if (mode == MODE_JVP) { sm = S_JFIRST; io.aux_in = vjp ? C2 : C1; bytes += n8; }
-        if (h->profiling) { char nm[48]; snprintf(nm, sizeof nm, "%s:%s", tag, P.label.c_str()); cid = counter_id(h, nm, bytes, P.flops); }
-        const long long ntile = (d.nslices + pad_slice_g(P.nt) - 1) / pad_slice_g(P.nt);
-        ProfScope ps(h, cid);
-        hipLaunchKernelGGL(pad_slice_variant(P.nt, sm, d.nx * d.ny), dim3((unsigned)((ntile + 3) / 4)), dim3(256), 0, h->stream, d, io);
+        io.in = pin; io.out = pout; io.gate = a.gate; io.gate_tol = a.gate_tol;
+        first_io(io);
+        rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, d, io, L.tag, P.label, L.bytes, P.flops);
       } else {
         LineIO io;
         memset(&io, 0, sizeof io);
-        io.in = pin; io.out = pout; io.gate = gate; io.gate_tol = gate_tol;
-        int lm = L_MID;
-        if (last) {
-          if (mode == MODE_T) { lm = L_TLAST; io.old = old; io.resid = resid; if (resid) bytes += n8; }
-          else if (mode == MODE_T_LIN) { lm = L_TLAST_LIN; io.old = old; io.resid = resid; io.aux_out = h->c2; bytes += n8; if (resid) bytes += n8; }
-          else { lm = L_JLAST; io.aux_in = vjp ? C1 : C2; io.old = old; bytes += n8; if (minus_identity) { bytes += n8; io.dotp = dotp; } }
-        }
-        if (h->profiling) { char nm[48]; snprintf(nm, sizeof nm, "%s:%s", tag, P.label.c_str()); cid = counter_id(h, nm, bytes, P.flops); }
-        ProfScope ps(h, cid);
-        hipLaunchKernelGGL(pad_line_variant(P.nt, lm, d.lrest % 2 == 0), dim3((unsigned)d.ntiles), dim3(pad_line_block(P.nt)), pad_line_lds(P.nt), h->stream, d, io);
+        io.in = pin; io.out = pout; io.gate = a.gate; io.gate_tol = a.gate_tol;
+        if (last) last_io(io);
+        rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, d, io, L.tag, P.label, L.bytes, P.flops);
       }
     } else if (P.small) {
       SmallIO io;
       memset(&io, 0, sizeof io);
-      io.in = pin; io.out = pout; io.gate = gate; io.gate_tol = gate_tol;
+      io.in = pin; io.out = pout; io.gate = a.gate; io.gate_tol = a.gate_tol;
       SmallDesc d = P.sm;
-      d.minus_identity = minus_identity;
+      d.minus_identity = a.minus_identity;
       if (vjp) { d.Qxp = h->ax[P.ax0].Qtp; d.Qyp = h->ax[P.ax1].Qtp; }
-      int sm = SM_MID;
-      if (i == 0) {
-        io.zero = (mode != MODE_JVP) ? resid : nullptr;
-        if (mode == MODE_T) sm = SM_FIRST_T;
-        else if (mode == MODE_T_LIN) { sm = SM_FIRST_TLIN; io.aux_out = h->c1; bytes += n8; }
-        else { sm = SM_FIRST_J; io.aux_in = vjp ? C2 : C1; bytes += n8; }
-      } else if (last) {
-        if (mode == MODE_T) { sm = SM_LAST_T; io.old = old; io.resid = resid; if (resid) bytes += n8; }
-        else if (mode == MODE_T_LIN) { sm = SM_LAST_TLIN; io.old = old; io.resid = resid; io.aux_out = h->c2; bytes += n8; if (resid) bytes += n8; }
-        else {
-          sm = SM_LAST_J; io.aux_in = vjp ? C1 : C2; io.old = old; bytes += n8;
-          if (minus_identity) { bytes += n8; io.dotp = dotp; }
-          if (dotp && h->jvp_dot_with) { io.dot_with = h->jvp_dot_with; bytes += n8; }
-        }
-      }
-      small_fn fn = small_variant(sm, P.r, P.wpt);
-      if (!fn) return fail(h, SDFS_ERR_UNSUPPORTED, "no small-grid kernel variant");
-      int cid = -1;
-      if (h->profiling) { char nm[48]; snprintf(nm, sizeof nm, "%s:%s", tag, P.label.c_str()); cid = counter_id(h, nm, bytes, P.flops); }
-      ProfScope ps(h, cid);
-      hipLaunchKernelGGL(fn, dim3(small_grid(d, P.wpt)), dim3(256), 0, h->stream, d, io);
+      if (i == 0) first_io(io);
+      else if (last) { last_io(io); io.dot_with = L.dot_with; }
+      rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, d, io, L.tag, P.label, L.bytes, P.flops);
     } else if (!P.line) {
-      SliceIO io;
-      memset(&io, 0, sizeof io);
-      io.in = pin; io.out = pout; io.gate = gate; io.gate_tol = gate_tol;
-      io.zero = (mode != MODE_JVP) ? resid : nullptr;        // the first pass clears the word the last pass maximises into
-      int sm = S_TFIRST;
-      if (t32) { sm = S_TFIRST32; bytes -= 0.5 * n8; }
-      if (mode == MODE_T_LIN) { sm = S_TFIRST_LIN; io.aux_out = h->c1; bytes += n8; }
-      else if (mode == MODE_JVP) { sm = S_JFIRST; io.aux_in = vjp ? C2 : C1; bytes += n8; }
       SliceDesc sd = P.sd;
       if (vjp) { sd.Qf = h->ax[P.ax1].Qt; sd.Qe = h->ax[P.ax0].Qt; }
       if (h->sharded) sd.t32_ref = h->t32_ref;
-      if (mode == MODE_JVP && !vjp && !f32 && h->jf.active && h->jf.kind >= 0) {
-        if (lc1) return fail(h, SDFS_ERR_ARG, "the fused BiCGSTAB first pass reads the cached linearisation only");
-        // BiCGSTAB's p / s update on the registers of this pass (krylov_kernels.hpp)
-        jfused_fn jfn = slice_jfused_variant(P.n, h->jf.kind);
-        if (!jfn) return fail(h, SDFS_ERR_UNSUPPORTED, "no fused first pass for this extent");
-        JFusedIO jio;
-        memset(&jio, 0, sizeof jio);
-        jio.upd = h->jf.upd; jio.a = h->jf.a; jio.q = h->jf.q; jio.c1 = h->c1; jio.out = pout; jio.sc = h->sc; jio.dot = h->jf.dot; jio.gate = gate;
-        bytes = (h->jf.kind == JF_P ? 6.0 : 5.0) * n8 + P.q_bytes;
-        int cid = -1;
-        if (h->profiling) { char nm[48]; snprintf(nm, sizeof nm, "jvp+%s:%s", h->jf.kind == JF_P ? "p" : "s", P.label.c_str()); cid = counter_id(h, nm, bytes, P.flops); }
-        const int gsl = slice_tile_slices(P.n, S_JFIRST);
-        const long long ntile = (P.sd.nslices + gsl - 1) / gsl;
-        ProfScope ps(h, cid);
-        hipLaunchKernelGGL(jfn, dim3((unsigned)((ntile + 3) / 4)), dim3(256), slice_lds_bytes(P.n, S_JFIRST), h->stream, P.sd, jio);
-        HIPCHK(h, hipGetLastError());
-        continue;
-      }
-      if (mode == MODE_JVP && !vjp && f32 && h->krylov_mfma32 && h->jf.active && h->jf.kind >= 0) {
-        // ... and on the fp32-MFMA first pass (vectors, c1 and the output are floats)
-        jfused32_fn jfn = slice32_jfused_variant(P.n, h->jf.kind);
-        if (!jfn) return fail(h, SDFS_ERR_UNSUPPORTED, "no fused fp32 first pass for this extent");
+      if (L.jfused && L.m32) {
         JFused32IO jio;
         memset(&jio, 0, sizeof jio);
-        jio.upd = (float*)h->jf.upd; jio.a = (const float*)h->jf.a; jio.q = (const float*)h->jf.q; jio.c1 = (const float*)h->c1;
-        jio.out = (float*)pout; jio.sc = h->sc; jio.dot = h->jf.dot; jio.gate = gate;
-        bytes = 0.5 * (h->jf.kind == JF_P ? 6.0 : 5.0) * n8 + P.q_bytes;
-        int cid = -1;
-        if (h->profiling) { char nm[48]; snprintf(nm, sizeof nm, "jvpm32+%s:%s", h->jf.kind == JF_P ? "p" : "s", P.label.c_str()); cid = counter_id(h, nm, bytes, P.flops); }
-        const int gsl = slice32_tile_slices(P.n);
-        const long long ntile = (P.sd.nslices + gsl - 1) / gsl;
-        ProfScope ps(h, cid);
-        hipLaunchKernelGGL(jfn, dim3((unsigned)((ntile + 3) / 4)), dim3(256), slice32_lds_bytes(P.n), h->stream, P.sd, jio);
-        HIPCHK(h, hipGetLastError());
-        continue;
+        jio.upd = (float*)a.bicg.upd; jio.a = (const float*)a.bicg.a; jio.q = (const float*)a.bicg.q; jio.c1 = (const float*)h->c1;
+        jio.out = (float*)pout; jio.sc = h->sc; jio.dot = a.bicg.dot; jio.gate = a.gate;
+        rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, sd, jio, L.tag, P.label, L.bytes, P.flops);
+      } else if (L.jfused) {
+        JFusedIO jio;
+        memset(&jio, 0, sizeof jio);
+        jio.upd = a.bicg.upd; jio.a = a.bicg.a; jio.q = a.bicg.q; jio.c1 = h->c1; jio.out = pout; jio.sc = h->sc;
+        jio.dot = a.bicg.dot; jio.gate = a.gate;
+        rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, sd, jio, L.tag, P.label, L.bytes, P.flops);
+      } else {
+        SliceIO io;
+        memset(&io, 0, sizeof io);
+        io.in = pin; io.out = pout; io.gate = a.gate; io.gate_tol = a.gate_tol;
+        first_io(io);
+        rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, sd, io, L.tag, P.label, L.bytes, P.flops);
       }
-      // opts.krylov_f32 = 3: fp32 LDS tile + fp32 MFMA for the J.v passes (f32_kernels.hpp)
-      const bool m32 = f32 && h->krylov_mfma32 && mode == MODE_JVP;
-      slice_fn fn = m32 ? slice32_variant(P.n) : slice_variant(P.n, sm, f32);
-      if (f32 && mode == MODE_JVP) bytes *= 0.5;
-      int cid = -1;
-      if (h->profiling) { char nm[48]; snprintf(nm, sizeof nm, "%s:%s", m32 ? "jvpm32" : tag, P.label.c_str()); cid = counter_id(h, nm, bytes, P.flops); }
-      const int gsl = m32 ? slice32_tile_slices(P.n) : slice_tile_slices(P.n, sm);
-      const long long ntile = (P.sd.nslices + gsl - 1) / gsl;
-      const unsigned grid = (unsigned)((ntile + 3) / 4);
-      ProfScope ps(h, cid);
-      hipLaunchKernelGGL(fn, dim3(grid), dim3(256), m32 ? slice32_lds_bytes(P.n) : slice_lds_bytes(P.n, sm), h->stream, sd, io);
     } else {
       LineIO io;
       memset(&io, 0, sizeof io);
-      io.in = pin; io.out = pout; io.gate = gate; io.gate_tol = gate_tol;
+      io.in = pin; io.out = pout; io.gate = a.gate; io.gate_tol = a.gate_tol;
       io.sched = h->sched + SCHED_WORDS * i;
       LineDesc d = P.ld;
-      d.minus_identity = minus_identity;
+      d.minus_identity = a.minus_identity;
       if (h->sharded) d.t32_ref = h->t32_ref;
-      if (h->knobs.a3_tables == 0) { d.f1 = nullptr; d.f2 = nullptr; }
       if (vjp) { d.Qx = h->ax[P.ax0].Qt; d.Qy = h->ax[P.ax1].Qt; }
-      int lm = L_MID;
-      if (last) {
-        if (mode == MODE_T) { lm = L_TLAST; io.old = old; io.resid = resid; if (resid) bytes += n8; }
-        else if (mode == MODE_T_LIN) { lm = L_TLAST_LIN; io.old = old; io.resid = resid; io.aux_out = h->c2; bytes += n8; if (resid) bytes += n8; }
-        else { lm = L_JLAST; io.aux_in = vjp ? C1 : C2; io.old = old; bytes += n8; if (minus_identity) { bytes += n8; io.dotp = dotp; } }
+      if (last) last_io(io);
+      io.dot_with = L.dot_with;
+      if (L.push) {
+        io.and_y = a.push.y; io.and_r = a.push.r; io.and_beta = a.push.beta; io.and_dot = a.push.dot;
+        if (a.push.tiles) *a.push.tiles = P.ld.ntiles;
       }
-      const bool lf32 = f32 && (mode == MODE_JVP || lm == L_TLAST_LIN);
-      line_fn fn = lf32 ? line_variant(P.n, lm, false, true, true) : line_variant(P.n, lm, P.persist, P.ld.lrest % LINE_R == 0);
-      unsigned grid = lf32 ? (unsigned)d.ntiles : line_grid(h, P);
-      if (t32) {
-        // fp32 intermediate: the fp32 middle form, or the last pass on a float tile (stream_kernels.hpp)
-        fn = last ? line_tlast32_variant(P.n) : line_variant(P.n, L_MID, false, true, true);
-        grid = (unsigned)d.ntiles;
-        bytes -= last ? 0.5 * n8 : n8;
-        // ... on the streamed forms where the fp64 passes run them (stream_kernels.hpp, IN32 / OUT32)
-        if ((P.stream & (last ? 2 : 1)) && h->knobs.no_f32_stream == 0) {
-          if (line_fn sf = line_stream_t32_variant(P.n, last ? L_TLAST : L_MID, d.f1 != nullptr)) {
-            fn = sf;
-            if (!last) {
-              long long g = std::min<long long>(P.ld.ntiles, (long long)line_stream_wpc_mid32(P.n) * h->num_cus);
-              g -= g % 8;
-              grid = (unsigned)std::max<long long>(g, 8);
-            }
-          }
-        }
-      } else if (!lf32 && ((lm == L_MID && (P.stream & 1)) || ((lm == L_TLAST || lm == L_TLAST_LIN) && (P.stream & 2)))) {
-        // stream_kernels.hpp: persistent middle pass with the next tile in flight; last pass with its side stream loaded early
-        fn = line_stream_variant(P.n, lm, d.f1 != nullptr);
-        grid = lm == L_MID ? stream_mid_grid(h, P) : (unsigned)d.ntiles;
-        if (lm == L_TLAST && h->andpush.r != nullptr && old != nullptr && d.ntiles <= (long long)MAX_PARTIAL_BLOCKS * AND_MAX_M) {
-          io.and_y = h->andpush.y; io.and_r = h->andpush.r; io.and_beta = h->andpush.beta; io.and_dot = h->andpush.dot;
-          h->andpush.tiles = d.ntiles;
-          bytes += 3 * n8;                                   // x read, y and r written
-        }
-      }
-      if (lm == L_JLAST && !lf32 && !vjp && h->jf.active) {
-        // fused BiCGSTAB iteration: the streamed last pass, one workgroup per tile (the partial sums are counted per tile)
-        fn = line_stream_variant(P.n, L_JLAST);
-        grid = (unsigned)d.ntiles;
-        io.dot_with = h->jf.dot_with;
-        bytes += 0.5 * n8;       // (rhat is read by the first of an iteration's two applications: one counter, their mean)
-      }
-      const bool m32 = lf32 && h->krylov_mfma32 && mode == MODE_JVP && !t32;
-      const int r32 = line32_row_floats(P.n, P.ld.lrest);
-      if (m32) {
-        fn = line32_variant(P.n, lm, r32); grid = (unsigned)(d.ntiles * LINE_R / r32);
-        if (lm == L_MID && (P.stream & 1) && grid >= 8u * TK_SUB && h->knobs.no_f32_stream == 0) {
-          // persistent form, next tile in flight (krylov_kernels.hpp); a multiple of 8 workgroups, one ticket range per XCD
-          if (line_fn sf = line32_stream_mid_variant(P.n, r32)) {
-            long long g = std::min<long long>(grid, (long long)line32_stream_wpc(P.n, r32) * h->num_cus);
-            g -= g % (8 * TK_SUB);
-            fn = sf; grid = (unsigned)g;
-          }
-        }
-        if (lm == L_JLAST && !vjp && h->jf.active) {
-          io.dot_with = h->jf.dot_with; bytes += n8;      // (halved below: the mean of the two applications)
-          if (io.dot_with) fn = line32_variant(P.n, lm, r32, true);
-        }
-      }
-      if (!fn) return fail(h, SDFS_ERR_UNSUPPORTED, "no line kernel variant");
-      if (f32 && mode == MODE_JVP) bytes *= 0.5;
-      int cid = -1;
-      if (h->profiling) { char nm[48]; snprintf(nm, sizeof nm, "%s:%s", m32 ? "jvpm32" : tag, P.label.c_str()); cid = counter_id(h, nm, bytes, P.flops); }
-      ProfScope ps(h, cid);
-      hipLaunchKernelGGL(fn, dim3(grid), dim3(m32 ? 256 : line_block(P.n)), m32 ? line32_lds_bytes(P.n, r32) : line_lds_bytes(P.n), h->stream, d, io);
+      rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, d, io, L.tag, P.label, L.bytes, P.flops);
     }
-    HIPCHK(h, hipGetLastError());
-    if (f32 && h->krylov_bf16) {
+    if (rc) return rc;
+    if (bf16) {
       // bf16r emulation: what this pass stored as floats is rounded to bfloat16 (the BiCGSTAB gate is a zero word when closed)
-      if (mode == MODE_JVP && (rc = round_stream_bf16(h, pout, gate))) return rc;
-      if (mode == MODE_T_LIN && i == 0 && (rc = round_stream_bf16(h, h->c1, nullptr))) return rc;
-      if (mode == MODE_T_LIN && last && (rc = round_stream_bf16(h, h->c2, nullptr))) return rc;
+      if (mode == MODE_JVP && (rc = round_stream_bf16_n(h, pout, (long long)h->N, a.gate))) return rc;
+      if (mode == MODE_T_LIN && i == 0 && (rc = round_stream_bf16_n(h, h->c1, (long long)h->N, nullptr))) return rc;
+      if (mode == MODE_T_LIN && last && (rc = round_stream_bf16_n(h, h->c2, (long long)h->N, nullptr))) return rc;
     }
   }
   return 0;
 }
 
-// tiles of the last pass of a J.v application (per-block partial sums of the fused dots)
-long long jvp_last_tiles(sdfs_handle* h) {
+// The pair / small-grid / padded plan, or a sharded stage on the pair plan's kernels, that serves request `a` on `plan`;
+// nullptr: the generic tiles.  The pair plan's fp32-storage forms need whole 16-element chunks in every line pass, otherwise
+// fp32 Krylov storage (and its linearisation) stays on the generic kernels; the sharded stages run fp64 streams only.
+FastPlan* fast_plan_for(sdfs_handle* h, const Plan& plan, bool has_first, bool has_last, const Apply& a) {
+  const bool f32 = a.f32() && a.mode != MODE_T;
+  if (h->fast.ok && &plan == &h->plan[0] && has_first && has_last && !(f32 && !h->fast.f32_ok)) return &h->fast;
+  const int st = &plan == &h->plan[0] ? 0 : (&plan == &h->plan[1] ? 1 : -1);
+  if (h->sharded && st >= 0 && h->sfast[st].ok && a.mode != MODE_VJP && !f32 && has_first == (st == 0) && has_last == (st == 1))
+    return &h->sfast[st];
+  return nullptr;
+}
+
+// workgroups of the last pass of the whole-grid application `a` (one partial sum each of the fused dot products)
+long long last_pass_grid(sdfs_handle* h, const Apply& a) {
   if (h->cont || h->dense) return 0;
-  if (h->fast.ok && h->fast.small) return h->krylov_f32 ? h->plan[0].passes.back().d.ntiles : (long long)small_grid(h->fast.passes.back().sm, h->fast.passes.back().wpt);
-  if (h->fast.ok && h->krylov_f32 && h->fast.f32_ok) {
-    const FastPass& PL = h->fast.passes.back();
-    // (the fp32-MFMA last pass walks chunks of 32 floats where the remainder allows it: half the workgroups)
-    if (h->krylov_mfma32 && !h->fast.small && PL.line) return PL.ld.ntiles * LINE_R / line32_row_floats(PL.n, PL.ld.lrest);
-    return PL.ld.ntiles;
-  }
-  if (h->fast.ok && h->fast.pad) return h->krylov_f32 ? (h->plan[0].passes.empty() ? 0 : h->plan[0].passes.back().d.ntiles) : h->fast.passes.back().pd.ntiles;
-  if (h->fast.ok && !h->krylov_f32) return line_grid(h, h->fast.passes.back());
+  if (const FastPlan* fp = fast_plan_for(h, h->plan[0], true, true, a))
+    return select_pass(h, *fp, (int)fp->passes.size() - 1, h->N, true, true, a).grid;
   return h->plan[0].passes.empty() ? 0 : h->plan[0].passes.back().d.ntiles;
 }
 
-int run_plan(sdfs_handle* h, Plan& plan, int mode, bool has_first, bool has_last,
-             const double* in, double* out, const double* old, unsigned long long* resid,
-             const unsigned long long* gate, double gate_tol, int minus_identity, double* dotp = nullptr,
-             const double* lc1 = nullptr, const double* lc2 = nullptr) {
-  if (mode == MODE_VJP) {
+int run_plan(sdfs_handle* h, Plan& plan, bool has_first, bool has_last, const Apply& a) {
+  if (a.mode == MODE_VJP) {
     if (h->cont || h->dense) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product exists for the discretised operator only");
-    for (int a = 0; a < h->ndim; ++a)
-      if (!h->ax[a].Qt) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product needs unconditional transition tensors "
-                                    "(axis %s is conditional)", h->ax[a].name);
+    for (int ax = 0; ax < h->ndim; ++ax)
+      if (!h->ax[ax].Qt) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product needs unconditional transition tensors "
+                                     "(axis %s is conditional)", h->ax[ax].name);
   }
-  if (h->cont) return run_cont(h, mode, in, out, old, resid, gate, gate_tol, minus_identity);
-  if (h->dense) return run_dense(h, mode, in, out, old, resid, gate, gate_tol, minus_identity);
-  // the pair plan serves the whole-grid operator; its fp32-storage forms need whole 16-element chunks in
-  // every line pass, otherwise fp32 Krylov storage (and its linearisation) stays on the generic kernels
-  if (h->fast.ok && &plan == &h->plan[0] && has_first && has_last && !(h->krylov_f32 && mode != MODE_T && !h->fast.f32_ok))
-    return run_fast_plan(h, h->fast, h->N, true, true, mode, in, out, old, resid, gate, gate_tol, minus_identity, dotp, lc1, lc2);
-  // sharded stages on the pair plan's kernels (fp64 streams)
-  if (h->sharded && (&plan == &h->plan[0] || &plan == &h->plan[1]) && h->sfast[&plan - h->plan].ok && mode != MODE_VJP &&
-      !(h->krylov_f32 && mode != MODE_T) && has_first == (&plan == &h->plan[0]) && has_last == (&plan == &h->plan[1]))
-    return run_fast_plan(h, h->sfast[&plan - h->plan], plan.nloc, has_first, has_last, mode, in, out, old, resid, gate, gate_tol, minus_identity, dotp);
-  const bool vjp = mode == MODE_VJP;       // the J.v launches with transposed matrices and c1 / c2 swapped
-  if (vjp) mode = MODE_JVP;
-  const double* const C1 = lc1 ? lc1 : h->c1;   // (lc1, lc2: the caller's J.v scalings, see run_fast_plan)
-  const double* const C2 = lc2 ? lc2 : h->c2;
+  if (h->cont) return run_cont(h, a.mode, a.in, a.out, a.old, a.resid, a.gate, a.gate_tol, a.minus_identity);
+  if (h->dense) return run_dense(h, a.mode, a.in, a.out, a.old, a.resid, a.gate, a.gate_tol, a.minus_identity);
+  if (FastPlan* fp = fast_plan_for(h, plan, has_first, has_last, a))
+    return run_fast_plan(h, *fp, fp == &h->fast ? h->N : plan.nloc, has_first, has_last, a);
+  const bool vjp = a.mode == MODE_VJP;       // the J.v launches with transposed matrices and c1 / c2 swapped
+  const int mode = vjp ? MODE_JVP : a.mode;
+  const double* const C1 = a.lc1 ? a.lc1 : h->c1;   // (lc1, lc2: the caller's J.v scalings, see run_fast_plan)
+  const double* const C2 = a.lc2 ? a.lc2 : h->c2;
+  const bool f32 = !vjp && a.f32();
   int rc = ensure_tmp(h);
   if (rc) return rc;
   if (mode != MODE_T) { rc = ensure_lin(h); if (rc) return rc; }
@@ -1525,9 +1536,9 @@ int run_plan(sdfs_handle* h, Plan& plan, int mode, bool has_first, bool has_last
     const bool first = has_first && i == 0, last = has_last && i == np - 1;
     PassIO io;
     memset(&io, 0, sizeof io);
-    io.in = (i == 0) ? in : h->tmp;
-    io.out = (i == np - 1) ? out : h->tmp;
-    io.gate = gate; io.gate_tol = gate_tol;
+    io.in = (i == 0) ? a.in : h->tmp;
+    io.out = (i == np - 1) ? a.out : h->tmp;
+    io.gate = a.gate; io.gate_tol = a.gate_tol;
     int pro = PRO_NONE, epi = EPI_NONE;
     double bytes = 2 * n8 + P.q_bytes;
     if (first) {
@@ -1536,9 +1547,9 @@ int run_plan(sdfs_handle* h, Plan& plan, int mode, bool has_first, bool has_last
       else { pro = PRO_MUL; io.aux_in = vjp ? C2 : C1; bytes += n8; }
     }
     if (last) {
-      if (mode == MODE_T) { epi = EPI_CES; io.old = old; io.resid = resid; if (resid) bytes += n8; }
+      if (mode == MODE_T) { epi = EPI_CES; io.old = a.old; io.resid = a.resid; if (a.resid) bytes += n8; }
       else if (mode == MODE_T_LIN) {
-        epi = EPI_CES_LIN; io.old = old; io.resid = resid; bytes += n8; if (resid) bytes += n8;
+        epi = EPI_CES_LIN; io.old = a.old; io.resid = a.resid; bytes += n8; if (a.resid) bytes += n8;
         // aux_out of the LAST pass is c2; if the same pass is also the first, c1 and c2
         // would collide on aux_out -- a single-pass plan splits linearisation in two launches
         if (first) return fail(h, SDFS_ERR_UNSUPPORTED, "single-pass linearise not supported");
@@ -1546,19 +1557,19 @@ int run_plan(sdfs_handle* h, Plan& plan, int mode, bool has_first, bool has_last
       } else {
         epi = EPI_MUL; bytes += n8;
         if (first) return fail(h, SDFS_ERR_UNSUPPORTED, "single-pass JVP not supported");
-        io.aux_in = vjp ? C1 : C2; io.old = old; if (minus_identity) bytes += n8;
-        if (minus_identity) io.dotp = dotp;
+        io.aux_in = vjp ? C1 : C2; io.old = a.old; if (a.minus_identity) bytes += n8;
+        if (a.minus_identity) io.dotp = a.dotp;
       }
     }
     // fp32 Krylov storage: every stream of a J.v application is fp32; a linearising T keeps fp64
     // streams and writes only c1 (first pass) and c2 (last pass) as fp32
-    const int prec = (!vjp && h->krylov_f32 && (mode == MODE_JVP || (mode == MODE_T_LIN && (first || last)))) ? 1 : 0;
+    const int prec = (f32 && (mode == MODE_JVP || (mode == MODE_T_LIN && (first || last)))) ? 1 : 0;
     if (prec && mode == MODE_JVP) bytes *= 0.5;
-    const char* tag = vjp ? "vjp" : (mode == MODE_JVP) ? (h->krylov_f32 ? "jvp32" : "jvp") : (mode == MODE_T_LIN ? "Tlin" : "T");
-    rc = launch_pass(h, P, pro, epi, io, minus_identity, tag, bytes, prec, vjp);
+    const char* tag = vjp ? "vjp" : (mode == MODE_JVP) ? (f32 ? "jvp32" : "jvp") : (mode == MODE_T_LIN ? "Tlin" : "T");
+    rc = launch_pass(h, P, pro, epi, io, a.minus_identity, tag, bytes, prec, vjp);
     if (rc) return rc;
-    if (prec && h->krylov_bf16) {
-      if (mode == MODE_JVP && (rc = round_stream_bf16_n(h, io.out, plan.nloc, gate))) return rc;
+    if (prec && a.prec == PREC_BF16) {
+      if (mode == MODE_JVP && (rc = round_stream_bf16_n(h, io.out, plan.nloc, a.gate))) return rc;
       if (mode == MODE_T_LIN && first && (rc = round_stream_bf16_n(h, h->c1, plan.nloc, nullptr))) return rc;
       if (mode == MODE_T_LIN && last && (rc = round_stream_bf16_n(h, h->c2, plan.nloc, nullptr))) return rc;
     }
@@ -1566,9 +1577,14 @@ int run_plan(sdfs_handle* h, Plan& plan, int mode, bool has_first, bool has_last
   return 0;
 }
 
+// one application on the whole grid
+int apply(sdfs_handle* h, const Apply& a) { return run_plan(h, h->plan[0], true, true, a); }
+
 int apply_T_dev(sdfs_handle* h, const double* w, double* Tw, unsigned long long* resid,
-                const unsigned long long* gate, double gate_tol) {
-  return run_plan(h, h->plan[0], MODE_T, true, true, w, Tw, w, resid, gate, gate_tol, 0);
+                const unsigned long long* gate, double gate_tol, int prec = PREC_F64) {
+  Apply a(MODE_T, w, Tw, w);
+  a.resid = resid; a.gate = gate; a.gate_tol = gate_tol; a.prec = prec;
+  return apply(h, a);
 }
 
 int ensure_slots(sdfs_handle* h, int n) {
@@ -1608,8 +1624,7 @@ int big_sa_line(sdfs_handle* h, int pass, bool first_only, const double* in, dou
   io.sched = h->sched + SCHED_WORDS * pass;
   LineDesc d = P.ld;
   d.first_only = first_only ? 1 : 0;
-  if (h->knobs.a3_tables == 0) { d.f1 = nullptr; d.f2 = nullptr; }
-  line_fn fn = line_variant(P.n, L_TFUSED, false, P.ld.lrest % LINE_R == 0);
+  line_fn fn = line_variant(P.n, L_TFUSED, P.ld.lrest % LINE_R == 0);
   if (!fn) return fail(h, SDFS_ERR_UNSUPPORTED, "no fused line kernel variant");
   int cid = -1;
   const double n8 = 8.0 * (double)h->N;
@@ -1700,9 +1715,11 @@ double bits_to_double(unsigned long long b) { double d; memcpy(&d, &b, 8); retur
 // Iteration it computes x_{it+1} = T(x_it) and err_it = max|x_{it+1} - x_it| into
 // slot it%chunk; every later kernel is gated on the previous slot, so once
 // err <= tol the remaining launches of the chunk are no-ops and the iterate stays.
-int solve_sa(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int64_t* n_apply, double* final_err) {
+// prec: the storage of T's intermediates (PREC_T32: phase A of opts.t_f32, below)
+int solve_sa(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int64_t* n_apply, double* final_err,
+             int prec = PREC_F64) {
   int rc;
-  if (o.t_f32 && !h->t32_active && h->fast.ok && !h->fast.small && h->fast.f32_ok && !h->cont && !h->dense && !h->sharded) {
+  if (o.t_f32 && prec != PREC_T32 && h->fast.ok && !h->fast.small && h->fast.f32_ok && !h->cont && !h->dense && !h->sharded) {
     // BASELINE config 5, T passes: phase A applies T with its intermediates stored as scaled floats (40 instead of 56
     // bytes per point and iteration) down to a step just above what that storage can resolve, phase B finishes in
     // fp64 from there.  One stored float carries 2^-24 relative, i.e. ~ w 2^-24 / |theta| on T w after the 1/theta
@@ -1720,9 +1737,7 @@ int solve_sa(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int
       oa.t_f32 = 0; oa.tol = switch_tol; oa.use_graph = 0;
       int64_t it_a = 0, ap_a = 0;
       double err_a = 0.0;
-      h->t32_active = true;
-      rc = solve_sa(h, oa, w, &it_a, &ap_a, &err_a);
-      h->t32_active = false;
+      rc = solve_sa(h, oa, w, &it_a, &ap_a, &err_a, PREC_T32);
       const std::vector<double> trace_a = h->trace;
       *n_iter = it_a; *n_apply = ap_a; *final_err = err_a;
       if (rc || it_a >= o.max_iter) return rc;
@@ -1755,7 +1770,7 @@ int solve_sa(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int
   // 16^6 0.195 against 0.207 ms per iteration, 24^6 2.45 against 2.71, 32^4 x 16^2 4.21 against 4.45 -- so the fused form
   // runs on request only)
   const bool fusedbig = h->fast.ok && !h->fast.small && !h->fast.pad && h->fast.passes.size() == 3 && !h->cont && !h->dense && h->knobs.sa_fused > 0 &&
-                        !h->t32_active;
+                        prec != PREC_T32;
   if (fusedbig && (rc = big_sa_line(h, 2, true, h->buf0, nullptr, nullptr, nullptr, nullptr, 0.0))) return rc;
   // ... and the residual without atomics: per-workgroup maxima, reduced by the next iteration's kernels
   bool ring = false;
@@ -1785,7 +1800,7 @@ int solve_sa(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int
       int r2 = fused ? small_sa_iteration(h, it, bufs[it & 1], bufs[(it + 1) & 1], h->slots + i, i == 0 ? carry : h->slots + i - 1, o.tol,
                                           ring, i == 0 ? nullptr : h->slots + i - 1)
                      : fusedbig ? big_sa_iteration(h, it, bufs[it & 1], bufs[(it + 1) & 1], h->slots + i, i == 0 ? carry : h->slots + i - 1, o.tol)
-                     : apply_T_dev(h, bufs[it & 1], bufs[(it + 1) & 1], h->slots + i, i == 0 ? carry : h->slots + i - 1, o.tol);
+                     : apply_T_dev(h, bufs[it & 1], bufs[(it + 1) & 1], h->slots + i, i == 0 ? carry : h->slots + i - 1, o.tol, prec);
       if (r2) return r2;
     }
     if (ring) {
@@ -1854,11 +1869,13 @@ int solve_sa(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int
 // (dot products in the last J.v pass, the merged small-grid loop, the slice_jfused updates, the captured graph) are
 // J.v-only: the transposed solve runs the plain iteration.  lc1 / lc2 (fp64 MODE_JVP only): the J.v scalings to use in
 // place of the cached c1 / c2 (the tilted expectation, sdfs_solve_tilted_dev); they too run the plain iteration.
+// prec: the storage of the J.v applications (PREC_F64, or the fp32 Krylov storage T = float / bf16r stands for).
 template <typename T>
-int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mode = MODE_JVP,
+int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int prec, int mode = MODE_JVP,
                    const double* lc1 = nullptr, const double* lc2 = nullptr) {
   const bool vjp = mode == MODE_VJP;
   const bool plain = vjp || lc1 != nullptr;     // only the plain iteration takes explicit scalings
+  const bool f32 = prec != PREC_F64;
   T *r = (T*)h->kry[0], *rhat = (T*)h->kry[1], *p = (T*)h->kry[2], *q = (T*)h->kry[3], *t = (T*)h->kry[4],
     *x = (T*)h->kry[5];
   const double* b = h->kry[6];
@@ -1875,6 +1892,12 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
     HIPCHK(h, hipHostMalloc((void**)&h->bicg_gate_host, 64));
   }
   unsigned long long* gate = h->bicg_gate;
+  // the J.v application in -> out of an iteration, (J - I) in with the partial sums of its fused dot products in dotp
+  auto jv = [&](const T* in, T* out, double* dotp) {
+    Apply a(mode, (const double*)in, (double*)out, (const double*)in);
+    a.gate = gate; a.minus_identity = 1; a.dotp = dotp; a.prec = prec; a.lc1 = lc1; a.lc2 = lc2;
+    return a;
+  };
   {
     ProfScope ps(h, cvec);
     hipLaunchKernelGGL(k_bicg_init<T>, dim3(g), dim3(VEC_BLOCK), 0, st, b, r, rhat, p, q, x, n);
@@ -1883,10 +1906,10 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
   }
   const long long maxit = o.inner_max_iter > 0 ? o.inner_max_iter : 10 * n;
   // <t, s> and <t, t> come out of the last J.v pass when its tiles fit the partial-sum buffer
-  const long long last_tiles = jvp_last_tiles(h);
+  const long long last_tiles = last_pass_grid(h, jv(p, q, h->partial));
   const bool fused_dots = !plain && last_tiles > 0 && 2 * last_tiles <= (long long)MAX_PARTIAL_BLOCKS * AND_MAX_M &&
-                          (h->plan[0].passes.size() > 1 || (h->fast.ok && (!h->krylov_f32 || h->fast.f32_ok))) && h->knobs.no_dot_fusion == 0 &&
-                          !h->krylov_bf16;      // (the fused sums would see the J.v output before its rounding)
+                          (h->plan[0].passes.size() > 1 || (h->fast.ok && (!f32 || h->fast.f32_ok))) &&
+                          prec != PREC_BF16;      // (the fused sums would see the J.v output before its rounding)
   // small grids are launch-bound: the finishing kernels merge into the vector kernels behind them (vec_kernels.hpp),
   // each reduction with its own region of the partial-sum buffer
   constexpr int PR = 2 * MAX_PARTIAL_BLOCKS;
@@ -1894,22 +1917,20 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
   double* const pss = h->partial + PR;          // <s, s>
   double* const pt = h->partial + 2 * PR;       // <t, s>, <t, t>
   double* const prr = h->partial + 4 * PR;      // <r, r>, <rhat, r>
-  const bool merged = !plain && n <= (1LL << 22) && (!fused_dots || last_tiles <= MAX_PARTIAL_BLOCKS) && h->knobs.no_bicg_merge == 0;
+  const bool merged = !plain && n <= (1LL << 22) && (!fused_dots || last_tiles <= MAX_PARTIAL_BLOCKS);
   auto iteration_merged = [&]() -> int {
     int rc2;
     { ProfScope ps(h, cvec);
       hipLaunchKernelGGL(k_bicg_update_p<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)r, p, (const T*)q, n, h->sc, (const unsigned long long*)gate); }
     // small-grid plan, fp64 vectors: <rhat, q> comes out of the last J.v pass as well
     const bool fused_rhat = fused_dots && h->fast.ok && h->fast.small && std::is_same<T, double>::value;
-    if (fused_rhat) h->jvp_dot_with = (const double*)rhat;
-    rc2 = run_plan(h, h->plan[0], MODE_JVP, true, true, (const double*)p, (double*)q, (const double*)p, nullptr, gate, 0.0, 1, fused_rhat ? pdot : nullptr);
-    h->jvp_dot_with = nullptr;
-    if (rc2) return rc2;
+    Apply a = jv(p, q, fused_rhat ? pdot : nullptr);
+    if (fused_rhat) a.dot_with = (const double*)rhat;
+    if ((rc2 = apply(h, a))) return rc2;
     { ProfScope ps(h, cvec);
       if (!fused_rhat) hipLaunchKernelGGL(k_dot<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)rhat, (const T*)q, n, pdot, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_s_m<T>, dim3(g), dim3(VEC_BLOCK), 0, st, r, (const T*)q, n, h->sc, (const double*)pdot, fused_rhat ? (int)last_tiles : g, pss, (const unsigned long long*)gate); }
-    if ((rc2 = run_plan(h, h->plan[0], MODE_JVP, true, true, (const double*)r, (double*)t, (const double*)r, nullptr, gate, 0.0, 1,
-                        fused_dots ? pt : nullptr))) return rc2;
+    if ((rc2 = apply(h, jv(r, t, fused_dots ? pt : nullptr)))) return rc2;
     { ProfScope ps(h, cvec);
       if (!fused_dots) hipLaunchKernelGGL(k_dot2<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)t, (const T*)r, n, pt, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_update_xr_m<T>, dim3(g), dim3(VEC_BLOCK), 0, st, x, r, (const T*)p, (const T*)t, (const T*)rhat, n, h->sc,
@@ -1922,15 +1943,13 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
     int rc2;
     { ProfScope ps(h, cvec);
       hipLaunchKernelGGL(k_bicg_update_p<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)r, p, (const T*)q, n, h->sc, (const unsigned long long*)gate); }
-    if ((rc2 = run_plan(h, h->plan[0], mode, true, true, (const double*)p, (double*)q, (const double*)p, nullptr, gate, 0.0, 1,
-                        nullptr, lc1, lc2))) return rc2;
+    if ((rc2 = apply(h, jv(p, q, nullptr)))) return rc2;
     { ProfScope ps(h, cvec);
       hipLaunchKernelGGL(k_dot<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)rhat, (const T*)q, n, h->partial, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_alpha_finish, dim3(1), dim3(VEC_BLOCK), 0, st, h->partial, g, h->sc, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_s<T>, dim3(g), dim3(VEC_BLOCK), 0, st, r, (const T*)q, n, h->sc, h->partial, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_s_finish, dim3(1), dim3(VEC_BLOCK), 0, st, h->partial, g, h->sc, (const unsigned long long*)gate); }
-    if ((rc2 = run_plan(h, h->plan[0], mode, true, true, (const double*)r, (double*)t, (const double*)r, nullptr, gate, 0.0, 1,
-                        fused_dots ? h->partial : nullptr, lc1, lc2))) return rc2;
+    if ((rc2 = apply(h, jv(r, t, fused_dots ? h->partial : nullptr)))) return rc2;
     { ProfScope ps(h, cvec);
       if (!fused_dots) hipLaunchKernelGGL(k_dot2<T>, dim3(g), dim3(VEC_BLOCK), 0, st, (const T*)t, (const T*)r, n, h->partial, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_omega_finish, dim3(1), dim3(VEC_BLOCK), 0, st, h->partial, fused_dots ? (int)last_tiles : g, h->sc, (const unsigned long long*)gate);
@@ -1946,12 +1965,20 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
 #ifdef SDFS_NO_JF32      // (build-time probe: the fp32-MFMA loop with the separate BLAS-1 kernels)
   const bool jf32 = false;
 #else
-  const bool jf32 = std::is_same<T, float>::value && h->krylov_f32 && h->krylov_mfma32 && !h->krylov_bf16 && h->fast.f32_ok;
+  const bool jf32 = std::is_same<T, float>::value && prec == PREC_MFMA32 && h->fast.f32_ok;
 #endif
-  bool jfuse = !plain && ((std::is_same<T, double>::value && !h->krylov_f32) || jf32) && !merged && h->fast.ok && !h->fast.small && !h->fast.pad &&
-               h->fast.passes.size() >= 2 && !P0->line && !P0->pad && PL->line && PL->ld.lrest % LINE_R == 0 && h->knobs.no_dot_fusion == 0;
+  bool jfuse = !plain && ((std::is_same<T, double>::value && !f32) || jf32) && !merged && h->fast.ok && !h->fast.small && !h->fast.pad &&
+               h->fast.passes.size() >= 2 && !P0->line && !P0->pad && PL->line && PL->ld.lrest % LINE_R == 0;
+  // the two applications of a fused iteration: q = (J - I) p, p = r + beta (p - omega q) formed in the first pass, <rhat, q>
+  // summed by the last; t = (J - I) s, s = r - alpha q (in r) and <s, s> formed in the first pass, <t, s> and <t, t> summed
+  // by the last (partial sums dp: [0, nt) <out, in>, [nt, 2 nt) <out, out>, [2 nt, 3 nt) <out, rhat>)
+  double* const dp = h->partial;
+  Apply jfp = jv(p, q, dp), jfs = jv(r, t, dp);
+  jfp.bicg.kind = JF_P; jfp.bicg.upd = (double*)p; jfp.bicg.a = (const double*)r; jfp.bicg.q = (const double*)q;
+  jfp.bicg.dot_with = (const double*)rhat;
+  jfs.bicg.kind = JF_S; jfs.bicg.upd = (double*)r; jfs.bicg.q = (const double*)q;
   // workgroups of the last pass (one partial sum each per inner product), wave tiles of the first
-  const long long jf_last = jfuse ? (jf32 ? PL->ld.ntiles * LINE_R / line32_row_floats(PL->n, PL->ld.lrest) : PL->ld.ntiles) : 0;
+  const long long jf_last = jfuse ? last_pass_grid(h, jfp) : 0;
   if (3 * jf_last > (long long)MAX_PARTIAL_BLOCKS * AND_MAX_M) jfuse = false;
   long long jf_tiles0 = 0;
   if (jfuse) {
@@ -1972,24 +1999,14 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
       hipFuncSetAttribute((const void*)line_stream_variant(PL->n, L_JLAST), hipFuncAttributeMaxDynamicSharedMemorySize, (int)line_lds_bytes(PL->n));
     }
   }
-  struct JfGuard { sdfs_handle* h; ~JfGuard() { h->jf.active = false; h->jf.kind = -1; h->jf.dot_with = nullptr; } } jf_guard{h};
+  jfs.bicg.dot = h->jf_ss;
   auto iteration_jfused = [&]() -> int {
     int rc2;
     const int nt = (int)jf_last;
-    double* const dp = h->partial;                       // [0, nt): <out, v>, [nt, 2 nt): <out, out>, [2 nt, 3 nt): <out, rhat>
-    h->jf.active = true;
-    // q = (J - I) p, p = r + beta (p - omega q) formed in the first pass, <rhat, q> summed by the last
-    h->jf.kind = JF_P; h->jf.upd = (double*)p; h->jf.a = (const double*)r; h->jf.q = (const double*)q; h->jf.dot = nullptr; h->jf.dot_with = (const double*)rhat;
-    rc2 = run_plan(h, h->plan[0], MODE_JVP, true, true, (const double*)p, (double*)q, (const double*)p, nullptr, gate, 0.0, 1, dp);
-    h->jf.dot_with = nullptr;
-    if (rc2) return rc2;
+    if ((rc2 = apply(h, jfp))) return rc2;
     { ProfScope ps(h, cvec);
       hipLaunchKernelGGL(k_bicg_alpha_finish, dim3(1), dim3(1024), 0, st, (const double*)(dp + 2 * (size_t)nt), nt, h->sc, (const unsigned long long*)gate); }
-    // t = (J - I) s, s = r - alpha q (in r) and <s, s> formed in the first pass, <t, s> and <t, t> summed by the last
-    h->jf.kind = JF_S; h->jf.upd = (double*)r; h->jf.a = nullptr; h->jf.q = (const double*)q; h->jf.dot = h->jf_ss;
-    rc2 = run_plan(h, h->plan[0], MODE_JVP, true, true, (const double*)r, (double*)t, (const double*)r, nullptr, gate, 0.0, 1, dp);
-    h->jf.kind = -1; h->jf.active = false;
-    if (rc2) return rc2;
+    if ((rc2 = apply(h, jfs))) return rc2;
     { ProfScope ps(h, cvec);
       hipLaunchKernelGGL(k_bicg_s_finish_wide, dim3(1), dim3(1024), 0, st, (const double*)h->jf_ss, (int)jf_tiles0, h->sc, (const unsigned long long*)gate);
       hipLaunchKernelGGL(k_bicg_omega_finish, dim3(1), dim3(1024), 0, st, (const double*)dp, nt, h->sc, (const unsigned long long*)gate);
@@ -2041,9 +2058,9 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int mod
 // Newton on g = T - id (code/solvers.py:51-95): x <- x - J(x)^{-1} g(x), outer loop is
 // the successive_approx stopping rule on the Newton map.
 
-int bicgstab_dev(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs) {
-  if (h->krylov_f32 && h->krylov_bf16) return bicgstab_dev_t<bf16r>(h, o, matvecs);
-  return h->krylov_f32 ? bicgstab_dev_t<float>(h, o, matvecs) : bicgstab_dev_t<double>(h, o, matvecs);
+int bicgstab_dev(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int prec) {
+  if (prec == PREC_BF16) return bicgstab_dev_t<bf16r>(h, o, matvecs, prec);
+  return prec != PREC_F64 ? bicgstab_dev_t<float>(h, o, matvecs, prec) : bicgstab_dev_t<double>(h, o, matvecs, prec);
 }
 
 int solve_newton(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int64_t* n_apply, double* final_err) {
@@ -2068,25 +2085,26 @@ int solve_newton(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter,
   // opts.krylov_f32: inexact Newton with the inner solve in fp32 storage (Krylov vectors, c1 / c2, the
   // J.v intermediates) and fp64 arithmetic / reductions; the outer residual T(x) - x and the iterate
   // stay fp64, so the fixed point is reached to the same tolerance.  Discretised, unsharded handles only.
-  struct F32Guard { sdfs_handle* h; ~F32Guard() { h->krylov_f32 = false; h->krylov_bf16 = false; h->krylov_mfma32 = false; } } f32_guard{h};
   const bool want_f32 = o.krylov_f32 != 0 && !h->cont && !h->dense && !h->sharded;
+  const int prec_f32 = (o.krylov_f32 == PREC_BF16 || o.krylov_f32 == PREC_MFMA32) ? o.krylov_f32 : PREC_F32;
+  int prec = want_f32 ? prec_f32 : PREC_F64;      // the storage of this step's inner solve
   int f32_failures = 0;
-  h->krylov_f32 = want_f32;
-  h->krylov_bf16 = want_f32 && o.krylov_f32 == 2;
-  h->krylov_mfma32 = want_f32 && o.krylov_f32 == 3;
   while (err > o.tol && it < o.max_iter) {
     // g(x) = T(x) - x, linearisation cached for the J.v products
-    if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, x, Tx, x, nullptr, nullptr, 0.0, 0))) return rc;
+    Apply lin(MODE_T_LIN, x, Tx, x);
+    lin.prec = prec;
+    if ((rc = apply(h, lin))) return rc;
     ++applies;
     { ProfScope ps(h, cvec);
       hipLaunchKernelGGL(k_sub_dot, dim3(g), dim3(VEC_BLOCK), 0, st, Tx, x, h->kry[6], n, h->partial); }
-    if ((rc = bicgstab_dev(h, o, &applies))) return rc;
+    if ((rc = bicgstab_dev(h, o, &applies, prec))) return rc;
+    const bool f32 = prec != PREC_F64;
     // fp32 storage can overflow while the iterate is still far from the fixed point ((w / w_0)^(theta-1)
     // spans more than fp32's range): keep the iterate so that such a step can be redone in fp64
-    if (h->krylov_f32) HIPCHK(h, hipMemcpyAsync(Tx, x, nb, hipMemcpyDeviceToDevice, st));
+    if (f32) HIPCHK(h, hipMemcpyAsync(Tx, x, nb, hipMemcpyDeviceToDevice, st));
     HIPCHK(h, hipMemsetAsync(h->slots, 0, 8, st));
     { ProfScope ps(h, cvec);
-      if (h->krylov_f32) hipLaunchKernelGGL(k_newton_update<float>, dim3(g), dim3(VEC_BLOCK), 0, st, x, (const float*)h->kry[5], x, n, h->slots);
+      if (f32) hipLaunchKernelGGL(k_newton_update<float>, dim3(g), dim3(VEC_BLOCK), 0, st, x, (const float*)h->kry[5], x, n, h->slots);
       else hipLaunchKernelGGL(k_newton_update<double>, dim3(g), dim3(VEC_BLOCK), 0, st, x, (const double*)h->kry[5], x, n, h->slots); }
     HIPCHK(h, hipMemcpyAsync(h->slots_host, h->slots, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
@@ -2098,17 +2116,17 @@ int solve_newton(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter,
     // because |g|_2 <= inner_atol is the reference's own rule and stays.)
     // (a NaN or infinite right-hand side -- an iterate that left the domain -- closes the solve's gate at once: also a zero step)
     const bool broke = err == 0.0 && (h->sc_host[SC_BREAK] != 0.0 || !std::isfinite(h->sc_host[SC_BB]));
-    if (broke && !h->krylov_f32) { status = SDFS_ERR_NUMERIC; ++it; break; }
-    if ((!std::isfinite(err) || broke) && h->krylov_f32) {
+    if (broke && !f32) { status = SDFS_ERR_NUMERIC; ++it; break; }
+    if ((!std::isfinite(err) || broke) && f32) {
       HIPCHK(h, hipMemcpyAsync(x, Tx, nb, hipMemcpyDeviceToDevice, st));
-      h->krylov_f32 = false;                 // redo this step in fp64
+      prec = PREC_F64;                       // redo this step in fp64
       ++f32_failures;
       err = o.tol + 1;
       continue;
     }
     // an fp64 step after an overflow went through: the iterate has usually calmed down, try fp32 again
     // (twice at most -- every failed attempt costs one inner solve)
-    if (want_f32 && !h->krylov_f32 && f32_failures < 3) h->krylov_f32 = true;
+    if (want_f32 && !f32 && f32_failures < 3) prec = prec_f32;
     if (o.record_errors) h->trace.push_back(err);
     ++it;
     if (!std::isfinite(err)) { status = SDFS_ERR_NUMERIC; break; }
@@ -2427,12 +2445,13 @@ int solve_anderson(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_ite
       double* const xo = (i & 1) ? x : fx;
       // the push rides on T's last pass where that is the streamed form (stream_kernels.hpp, LineIO::and_*): x is read
       // once, T x is not read back -- 9 grid streams per pass instead of 10, on a pass that is bound by its power, not its bytes
-      h->andpush.y = hp.X[pos]; h->andpush.r = hp.R[pos]; h->andpush.beta = o.beta; h->andpush.dot = h->partial; h->andpush.tiles = 0;
-      if (h->knobs.no_and_push_fusion) h->andpush.r = nullptr;
-      int r2 = apply_T_dev(h, xi, xo, nullptr, &S->gate, 0.0);
-      const long long ptiles = h->andpush.tiles;
-      h->andpush.r = nullptr; h->andpush.y = nullptr; h->andpush.tiles = 0;
-      if (r2) return r2;
+      long long ptiles = 0;
+      Apply a(MODE_T, xi, xo, xi);
+      a.gate = &S->gate;
+      if (!h->knobs.no_and_push_fusion) {
+        a.push.y = hp.X[pos]; a.push.r = hp.R[pos]; a.push.beta = o.beta; a.push.dot = h->partial; a.push.tiles = &ptiles;
+      }
+      if (int r2 = apply(h, a)) return r2;
       ProfScope ps(h, cvec);
       if (ptiles == 0)
         hipLaunchKernelGGL(k_and_push_lite, dim3(g), dim3(VEC_BLOCK), 0, st, (const double*)xi, (const double*)xo, hp.X[pos], hp.R[pos], o.beta, n, h->partial,
@@ -2991,7 +3010,7 @@ int sdfs_create_continuous(int model, int ndim, const int64_t* shapes, const dou
     for (int d = 0; d < ndim; ++d) pw *= c;
     if (pw == M) tq = c;
   }
-  if (tq && h->knobs.cont_no_tensor == 0) {
+  if (tq) {
     long long st = 1;
     for (int d = 0; d < ndim && tq; ++d, st *= tq) {
       cd.tstride[d] = (int)st;
@@ -3020,7 +3039,7 @@ int sdfs_create_continuous(int model, int ndim, const int64_t* shapes, const dou
     vmax *= mext;
     if (d < ndim - 2) uomax *= mext;
   }
-  const int cap_limit = std::max(64, std::min(4000, h->knobs.cont_lds_cap));   // doubles; 2 * cap * 8 < 64 KB
+  const int cap_limit = 4000;   // doubles; 2 * cap * 8 < 64 KB
   cd.cap = (int)std::min<long long>(vmax, cap_limit);
   cd.cap += cd.cap & 1;
   cd.tq = 0; cd.ucap = 0;
@@ -3182,7 +3201,7 @@ int sdfs_linearize_dev(sdfs_handle* h, const double* w, double* Tw) {
   if (h->sharded) return fail(h, SDFS_ERR_ARG, "sharded handle: use sdfs_apply_stage_dev");
   double* out = Tw;
   if (!out) { if ((rc = ensure_buf(h, &h->hostio3))) return rc; out = h->hostio3; }
-  if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, w, out, w, nullptr, nullptr, 0.0, 0))) return rc;
+  if ((rc = apply(h, Apply(MODE_T_LIN, w, out, w)))) return rc;
   h->lin_stale = false;
   return 0;
 }
@@ -3192,7 +3211,9 @@ int sdfs_apply_jvp_dev(sdfs_handle* h, const double* v, double* out, int minus_i
   if (!v || !out) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
   if (h->sharded) return fail(h, SDFS_ERR_ARG, "sharded handle: use sdfs_apply_stage_dev");
   if (!h->c1 || !h->c2 || h->lin_stale) return fail(h, SDFS_ERR_ARG, "sdfs_apply_jvp_dev before sdfs_linearize_dev");
-  return run_plan(h, h->plan[0], MODE_JVP, true, true, v, out, v, nullptr, nullptr, 0.0, minus_identity);
+  Apply a(MODE_JVP, v, out, v);
+  a.minus_identity = minus_identity;
+  return apply(h, a);
 }
 
 int sdfs_apply_jvp(sdfs_handle* h, const double* w_host, const double* v_host, double* out_host) {
@@ -3214,11 +3235,9 @@ int sdfs_apply_vjp_dev(sdfs_handle* h, const double* u, double* out, int minus_i
   if (!u || !out) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
   if (h->sharded) return fail(h, SDFS_ERR_ARG, "sharded handle: no vector-Jacobian product");
   if (!h->c1 || !h->c2 || h->lin_stale) return fail(h, SDFS_ERR_ARG, "sdfs_apply_vjp_dev before sdfs_linearize_dev");
-  const bool f32 = h->krylov_f32;
-  h->krylov_f32 = false;
-  rc = run_plan(h, h->plan[0], MODE_VJP, true, true, u, out, u, nullptr, nullptr, 0.0, minus_identity);
-  h->krylov_f32 = f32;
-  return rc;
+  Apply a(MODE_VJP, u, out, u);
+  a.minus_identity = minus_identity;
+  return apply(h, a);
 }
 
 int sdfs_apply_vjp(sdfs_handle* h, const double* w_host, const double* u_host, double* out_host) {
@@ -3255,7 +3274,7 @@ int sdfs_param_tangent_dev(sdfs_handle* h, const double* w, const double* dparam
                              hipMemcpyHostToDevice, h->stream));
   }
   // linearise at w (T w, and the cache of c1 / c2 the J.v below and a later sdfs_solve_linear_dev use)
-  if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, w, Tw, w, nullptr, nullptr, 0.0, 0))) return rc;
+  if ((rc = apply(h, Apply(MODE_T_LIN, w, Tw, w)))) return rc;
   h->lin_stale = false;
   SensGeom g;
   memset(&g, 0, sizeof g);
@@ -3269,7 +3288,7 @@ int sdfs_param_tangent_dev(sdfs_handle* h, const double* w, const double* dparam
       ProfScope ps(h, cid);
       hipLaunchKernelGGL(k_sens_prologue, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, g, dla1, dtheta, w, h->sens.v);
       HIPCHK(h, hipGetLastError()); }
-    if ((rc = run_plan(h, h->plan[0], MODE_JVP, true, true, h->sens.v, out, h->sens.v, nullptr, nullptr, 0.0, 0))) return rc;
+    if ((rc = apply(h, Apply(MODE_JVP, h->sens.v, out, h->sens.v)))) return rc;
   }
   g.ax_tab = h->sens.ax_a2;
   {
@@ -3285,7 +3304,7 @@ int sdfs_param_tangent_dev(sdfs_handle* h, const double* w, const double* dparam
 
 namespace {
 // x = (I - A)^{-1} rhs with the fp64 device BiCGSTAB, A = J (MODE_JVP), J^T (MODE_VJP) or, with (lc1, lc2), the J.v
-// kernels on those scalings.  Runs on fp64 storage whatever fp32 settings the handle carries, and restores them.
+// kernels on those scalings.  fp64 storage.
 int linear_solve(sdfs_handle* h, const sdfs_opts& o, int mode, const double* rhs, double* x, int64_t* n_iter,
                  double* final_rel_resid, const double* lc1, const double* lc2, const char* what) {
   int rc;
@@ -3296,12 +3315,8 @@ int linear_solve(sdfs_handle* h, const sdfs_opts& o, int mode, const double* rhs
   // the loop solves (A - I) y = b: b = -rhs gives y = (I - A)^{-1} rhs
   hipLaunchKernelGGL(k_sens_neg, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, rhs, h->kry[6], n);
   HIPCHK(h, hipGetLastError());
-  const bool f32 = h->krylov_f32;
-  h->krylov_f32 = false;
   int64_t mv = 0;
-  rc = bicgstab_dev_t<double>(h, o, &mv, mode, lc1, lc2);
-  h->krylov_f32 = f32;
-  if (rc) return rc;
+  if ((rc = bicgstab_dev_t<double>(h, o, &mv, PREC_F64, mode, lc1, lc2))) return rc;
   HIPCHK(h, hipMemcpyAsync(x, h->kry[5], sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));          // (the loop's last read of the scalars preceded this copy)
   const double rr = h->sc_host[SC_RR], bb = h->sc_host[SC_BB], a2 = h->sc_host[SC_ATOL2];
@@ -3347,16 +3362,6 @@ PriceGeom price_geom(const sdfs_handle* h) {
   return g;
 }
 
-// Pricing is fp64 end to end: the fp32 settings a handle may carry are off while a pricing call runs, then restored.
-struct Fp64Scope {
-  sdfs_handle* h;
-  bool kf32, kbf16, kmfma, t32;
-  explicit Fp64Scope(sdfs_handle* hh) : h(hh), kf32(hh->krylov_f32), kbf16(hh->krylov_bf16), kmfma(hh->krylov_mfma32), t32(hh->t32_active) {
-    h->krylov_f32 = h->krylov_bf16 = h->krylov_mfma32 = h->t32_active = false;
-  }
-  ~Fp64Scope() { h->krylov_f32 = kf32; h->krylov_bf16 = kbf16; h->krylov_mfma32 = kmfma; h->t32_active = t32; }
-};
-
 int price_handle_ok(sdfs_handle* h, const char* fn, bool need_tilt) {
   if (h->cont || h->dense || h->sharded)
     return fail(h, SDFS_ERR_UNSUPPORTED, "%s: pricing exists for unsharded discretised (multi-index) handles only", fn);
@@ -3399,11 +3404,10 @@ int sdfs_set_tilt_dev(sdfs_handle* h, const double* w, int sdf_power, double kap
     for (size_t i = 0; i < S.z.size(); ++i) Pr.ez_host[i] = std::exp(xz * (S.mu_c + S.z[i]));
     HIPCHK(h, hipMemcpyAsync(Pr.ez, Pr.ez_host.data(), sizeof(double) * S.z.size(), hipMemcpyHostToDevice, h->stream));
   }
-  Fp64Scope f64(h);
   if (w) {
     // linearise at w in fp64: c1 = w^(theta-1), c2 = beta^theta (Tw - 1)^(1-theta) (replaces the cached linearisation)
     if ((rc = ensure_buf(h, &h->hostio3))) return rc;
-    if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, w, h->hostio3, w, nullptr, nullptr, 0.0, 0))) return rc;
+    if ((rc = apply(h, Apply(MODE_T_LIN, w, h->hostio3, w)))) return rc;
     h->lin_stale = false;
   }
   const PriceGeom g = price_geom(h);
@@ -3433,8 +3437,9 @@ int sdfs_apply_tilted_dev(sdfs_handle* h, const double* f, double* out) {
   int rc = check(h); if (rc) return rc;
   if ((rc = price_handle_ok(h, "sdfs_apply_tilted_dev", true))) return rc;
   if (!f || !out) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
-  Fp64Scope f64(h);
-  return run_plan(h, h->plan[0], MODE_JVP, true, true, f, out, f, nullptr, nullptr, 0.0, 0, nullptr, h->price.d1, h->price.d2);
+  Apply a(MODE_JVP, f, out, f);
+  a.lc1 = h->price.d1; a.lc2 = h->price.d2;
+  return apply(h, a);
 }
 
 int sdfs_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const double* rhs, double* x, int64_t* n_iter,
@@ -3445,7 +3450,6 @@ int sdfs_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const double* r
   sdfs_opts o;
   if (opts) o = *opts; else sdfs_default_opts(&o);
   o.krylov_f32 = 0;                        // (fp64 whatever the options say)
-  Fp64Scope f64(h);
   return linear_solve(h, o, MODE_JVP, rhs, x, n_iter, final_rel_resid, h->price.d1, h->price.d2, "tilted");
 }
 
@@ -3479,7 +3483,6 @@ int sdfs_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* const*
     HIPCHK(h, hipMalloc((void**)&Pr.res, sizeof(double) * PRICE_NSUM * (size_t)n_max));
     Pr.res_cap = n_max;
   }
-  Fp64Scope f64(h);
   const PriceGeom g = price_geom(h);
   const int rgrid = price_grid(h);
   const int fgrid = (int)std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK, (long long)h->num_cus * 16);
@@ -3490,7 +3493,9 @@ int sdfs_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* const*
   double* cur = Pr.pb;
   int64_t js = 0;
   for (int64_t n = 1; n <= n_max; ++n) {
-    if ((rc = run_plan(h, h->plan[0], MODE_JVP, true, true, prev, cur, prev, nullptr, nullptr, 0.0, 0, nullptr, Pr.d1, Pr.d2))) return rc;
+    Apply a(MODE_JVP, prev, cur, prev);
+    a.lc1 = Pr.d1; a.lc2 = Pr.d2;
+    if ((rc = apply(h, a))) return rc;
     {
       ProfScope ps(h, cid);
       hipLaunchKernelGGL(k_horizon_reduce, dim3(rgrid), dim3(PRICE_BLOCK), 0, h->stream, g, wt, (const double*)cur,
@@ -3722,9 +3727,13 @@ int sdfs_apply_stage_gated_dev(sdfs_handle* h, int stage, int mode, const double
   if (!in || !out) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
   // (a closed gate leaves the cleared word at zero, so every later gate on it stays closed)
   if (resid_dev && stage == 1) HIPCHK(h, hipMemsetAsync(resid_dev, 0, 8, h->stream));
-  return run_plan(h, h->plan[stage], mode, stage == 0, stage == 1, in, out, old,
-                  stage == 1 ? (unsigned long long*)resid_dev : nullptr, (const unsigned long long*)gate_dev, gate_tol,
-                  (mode == MODE_JVP && old) ? 1 : 0);
+  Apply a(mode, in, out, old);
+  a.resid = stage == 1 ? (unsigned long long*)resid_dev : nullptr;
+  a.gate = (const unsigned long long*)gate_dev; a.gate_tol = gate_tol;
+  a.minus_identity = (mode == MODE_JVP && old) ? 1 : 0;
+  // the handle's stage settings (sdfs_set_krylov_f32, sdfs_set_t_f32)
+  a.prec = mode == MODE_T ? (h->stage_t32 ? PREC_T32 : PREC_F64) : (h->stage_f32 ? PREC_F32 : PREC_F64);
+  return run_plan(h, h->plan[stage], stage == 0, stage == 1, a);
 }
 
 int sdfs_apply_stage_dev(sdfs_handle* h, int stage, int mode, const double* in, double* out,
@@ -3955,7 +3964,7 @@ int sdfs_set_krylov_f32(sdfs_handle* h, int on, double w_ref) {
   int rc = check(h); if (rc) return rc;
   if (!h->sharded) return fail(h, SDFS_ERR_ARG, "sdfs_set_krylov_f32 is for sharded handles (opts.krylov_f32 otherwise)");
   if (on && !(w_ref > 0.0 && std::isfinite(w_ref))) return fail(h, SDFS_ERR_ARG, "reference value must be positive and finite");
-  h->krylov_f32 = on != 0;
+  h->stage_f32 = on != 0;
   h->lin_ref = on ? w_ref : 0.0;
   return 0;
 }
@@ -3968,7 +3977,7 @@ int sdfs_set_t_f32(sdfs_handle* h, int on, double w_ref) {
     for (const FastPass& P : h->sfast[st].passes)
       if (P.line && P.ld.lrest % LINE_R != 0) return fail(h, SDFS_ERR_UNSUPPORTED, "fp32 intermediates need whole 16-element chunks in every line pass");
   if (on && !(w_ref > 0.0 && std::isfinite(w_ref))) return fail(h, SDFS_ERR_ARG, "reference value must be positive and finite");
-  h->t32_active = on != 0;
+  h->stage_t32 = on != 0;
   h->t32_ref = on ? w_ref : 0.0;
   return 0;
 }
@@ -4037,17 +4046,16 @@ int sdfs_debug_jvp_storage_dev(sdfs_handle* h, int krylov_f32, const double* w_d
     return fail(h, SDFS_ERR_UNSUPPORTED, "reduced-precision J.v storage exists for unsharded discretised handles only");
   if (h->sharded) return fail(h, SDFS_ERR_ARG, "sharded handle: use sdfs_apply_stage_dev");
   if ((rc = ensure_buf(h, &h->hostio3))) return rc;
-  Fp64Scope keep(h);                       // (restores the handle's own flags on every exit path)
-  // the storage flags exactly as solve_newton sets them for opts.krylov_f32
-  h->krylov_f32 = krylov_f32 != 0;
-  h->krylov_bf16 = krylov_f32 == 2;
-  h->krylov_mfma32 = krylov_f32 == 3;
+  // the storage solve_newton's inner solve uses for opts.krylov_f32 (PREC_* = opts.krylov_f32 for 0 ... 3)
+  Apply lin(MODE_T_LIN, w_dev, h->hostio3, w_dev);
+  lin.prec = krylov_f32;
+  Apply jv(MODE_JVP, (const double*)v_dev, (double*)out_dev, (const double*)v_dev);
+  jv.prec = krylov_f32; jv.minus_identity = minus_identity;
   // from here on c1 / c2 may hold scaled floats: an fp64 J.v must relinearise first
   if (krylov_f32 != 0) h->lin_stale = true;
-  if ((rc = run_plan(h, h->plan[0], MODE_T_LIN, true, true, w_dev, h->hostio3, w_dev, nullptr, nullptr, 0.0, 0))) return rc;
+  if ((rc = apply(h, lin))) return rc;
   if (krylov_f32 == 0) h->lin_stale = false;
-  return run_plan(h, h->plan[0], MODE_JVP, true, true, (const double*)v_dev, (double*)out_dev, (const double*)v_dev, nullptr,
-                  nullptr, 0.0, minus_identity);
+  return apply(h, jv);
 }
 
 int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
@@ -4077,18 +4085,21 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
         snprintf(line, sizeof line, "small-grid plan pass %zu: %s %d wave%s per tile, run %d, tiles %lld, workgroups %u\n", i,
                  P.label.c_str(), P.wpt, P.wpt == 1 ? "" : "s", P.r, P.sm.ntiles, small_grid(P.sm, P.wpt));
       } else if (!P.line) {
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)slice_variant(P.n, S_TFIRST), 256, slice_lds_bytes(P.n, S_TFIRST));
+        // (the first pass of T)
+        const PassLaunch L = select_pass(h, h->fast, (int)i, h->N, true, true, Apply(MODE_T, nullptr, nullptr, nullptr));
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, L.fn, L.block, L.lds);
         const long long nt = (P.sd.nslices + slice_tile_slices(P.n, S_TFIRST) - 1) / slice_tile_slices(P.n, S_TFIRST);
         snprintf(line, sizeof line, "pair plan pass %zu: %s lds %zu B block 256 (4 wave tiles) wave-tiles %lld blocks/CU %d\n", i,
-                 P.label.c_str(), slice_lds_bytes(P.n, S_TFIRST), nt, occ);
+                 P.label.c_str(), L.lds, nt, occ);
       } else {
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)line_variant(P.n, L_MID, P.persist, P.ld.lrest % LINE_R == 0), line_block(P.n), line_lds_bytes(P.n));
+        // (the occupancy of the plain middle form, one tile per workgroup)
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)line_variant(P.n, L_MID, P.ld.lrest % LINE_R == 0), line_block(P.n), line_lds_bytes(P.n));
         snprintf(line, sizeof line, "pair plan pass %zu: %s lds %zu B block %d tiles %lld (outer %lld x %d chunks of 128 B) %s grid %u blocks/CU %d\n", i,
                  P.label.c_str(), line_lds_bytes(P.n), line_block(P.n), P.ld.ntiles, P.ld.nouter, P.ld.nchunks,
                  P.stream == 3 ? "streamed (middle pass: persistent, next tile in flight; T's last pass: side stream loaded early)" :
                  P.stream == 1 ? "streamed as a middle pass (persistent, next tile in flight)" :
-                 P.stream == 2 ? "streamed as T's last pass (side stream loaded early)" :
-                 P.persist ? "persistent" : "one tile per workgroup", line_grid(h, P), occ);
+                 P.stream == 2 ? "streamed as T's last pass (side stream loaded early)" : "one tile per workgroup",
+                 (unsigned)P.ld.ntiles, occ);
       }
       s += line;
     }
@@ -4096,19 +4107,18 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
       s += "small-grid plan, Anderson: passes in reverse order, push on the last pass, control step + update of x on the first\n";
     // the fp32 J.v forms of each pass (opts.krylov_f32 = 1 / 2: fp32 streams on the fp64 tile; 3: the fp32-MFMA kernel
     // run_fast_plan picks, with its row width and, for a middle pass, whether it runs persistent)
+    Apply m32(MODE_JVP, nullptr, nullptr, nullptr);
+    m32.prec = PREC_MFMA32; m32.minus_identity = 1;
     for (size_t i = 0; i < h->fast.passes.size() && h->fast.f32_ok && !h->fast.small && !h->fast.pad; ++i) {
       const FastPass& P = h->fast.passes[i];
       const bool last = i + 1 == h->fast.passes.size();
+      const PassLaunch L = select_pass(h, h->fast, (int)i, h->N, true, true, m32);
       if (!P.line) {
-        snprintf(line, sizeof line, "pair plan pass %zu fp32: %s mfma32 %s\n", i, P.label.c_str(), slice32_variant(P.n) ? "slice32" : "none");
+        snprintf(line, sizeof line, "pair plan pass %zu fp32: %s mfma32 %s\n", i, P.label.c_str(), L.fn ? "slice32" : "none");
       } else {
-        const int r32 = line32_row_floats(P.n, P.ld.lrest);
-        const long long grid = P.ld.ntiles * LINE_R / r32;
-        const bool persist = !last && (P.stream & 1) && grid >= 8 * TK_SUB && h->knobs.no_f32_stream == 0 &&
-                             line32_stream_mid_variant(P.n, r32) != nullptr;
         snprintf(line, sizeof line, "pair plan pass %zu fp32: %s mfma32 %s row %d floats %s\n", i, P.label.c_str(),
-                 line32_variant(P.n, last ? L_JLAST : L_MID, r32) ? "line32" : "none", r32,
-                 last ? "last pass" : persist ? "persistent middle pass" : "one tile per workgroup");
+                 L.fn ? "line32" : "none", line32_row_floats(P.n, P.ld.lrest),
+                 last ? "last pass" : L.persistent ? "persistent middle pass" : "one tile per workgroup");
       }
       s += line;
     }

@@ -329,7 +329,21 @@ def test_one_newton_step_true_residual(S, model, shapes, knobs, expect, beta):
 # -- (d) one application of T with fp32 intermediates --------------------------------------------------------------------
 T32_SHAPES = [("gcy", (20,) * 6), ("gcy", (16,) * 6), ("gcy", (24, 24, 20, 20, 16, 16)),
               ("ssy", (16, 16, 24, 24)), ("ssy", (32, 32, 16, 16)), ("ssy", (20, 20, 20, 20))]
-T32_KNOBS = [dict(), dict(SDFS_NO_F32_STREAM=1), dict(SDFS_A3_TABLES=0)]
+# (knobs, gathered): as built; the fp32 middle pass unstreamed; T's last pass gathering a3 (z states perturbed, see
+# gathered_a3_inputs)
+T32_CASES = [(dict(), False), (dict(SDFS_NO_F32_STREAM=1), False), (dict(), True)]
+
+
+def gathered_a3_inputs(arr):
+    """GCY arrays whose z states are no longer sigma_z[h_z] g[z] + m[h_zpi, z_pi]: a term in h_z times h_zpi makes the
+    aggregator's scale a3 = exp((1 - gamma)(mu_c + z)) fail the two-table check of the pair plan's last pass, which then
+    gathers a3 from its table."""
+    z = np.asarray(arr[0])                        # z_states[z_pi, h_z, h_zpi, z]
+    hz = np.arange(z.shape[1])[None, :, None, None]
+    hzpi = np.arange(z.shape[2])[None, None, :, None]
+    out = list(arr)
+    out[0] = z + 1e-3 * float(np.std(z)) * hz * hzpi
+    return out
 
 
 @limit(420)
@@ -338,15 +352,22 @@ T32_KNOBS = [dict(), dict(SDFS_NO_F32_STREAM=1), dict(SDFS_A3_TABLES=0)]
 def test_t_f32_one_application(S, model, shapes, inputs):
     """solve(w, "successive_approx", tol=0, max_iter=1, t_f32=1) = T32(w): |T32 - T|_i <= 8 u (T_i - 1) / |theta|, and the
     fused residual max|T32(w) - w| within the largest of those of the oracle's max|T(w) - w|; as built, with the
-    fp32 middle pass unstreamed (SDFS_NO_F32_STREAM=1) and with a3 gathered (SDFS_A3_TABLES=0)."""
-    params, arr = model_inputs(S, model, shapes, inputs)
-    ref = oracle(model, shapes, params, arr)
-    w = wbench(shapes)
-    T = ref(w)
+    fp32 middle pass unstreamed (SDFS_NO_F32_STREAM=1) and, on GCY, with a3 gathered by the last pass (z states that
+    break its two-table form, given to the handle and the oracle alike; SSY's a3 does not vary along the last pass's
+    pair, so its two tables always hold)."""
+    params, arr0 = model_inputs(S, model, shapes, inputs)
     theta = (S.SSY() if model == "ssy" else S.GCY()).θ
-    lim = fb.t32_bound(T, theta)
-    want_res = float(np.max(np.abs(T - w)))
-    for knobs in T32_KNOBS:
+    w = wbench(shapes)
+    want = {}
+    for knobs, gathered in T32_CASES:
+        if gathered and model != "gcy":
+            continue
+        arr = gathered_a3_inputs(arr0) if gathered else arr0
+        if gathered not in want:
+            want[gathered] = oracle(model, shapes, params, arr)(w)
+        T = want[gathered]
+        lim = fb.t32_bound(T, theta)
+        want_res = float(np.max(np.abs(T - w)))
         op = build(S, model, shapes, params, arr, SDFS_PLAN="pair", **knobs)
         assert PAIR in op.describe_plan()
         op.set_profiling(True)
@@ -356,7 +377,7 @@ def test_t_f32_one_application(S, model, shapes, inputs):
         op.close()
         assert n == 1 and any(nm.startswith("T32:") for nm in names), names
         err = np.abs(x - T)
-        what = f"{model} {shapes} {inputs} {knobs}"
+        what = f"{model} {shapes} {inputs} {knobs}{' a3 gathered' if gathered else ''}"
         assert np.all(err <= lim), f"{what}: {float(np.max(err / lim)):.3g} x the bound"
         assert np.max(err) > 0, what
         assert abs(info["final_err"] - want_res) <= float(np.max(lim)), (what, info["final_err"], want_res)

@@ -14,18 +14,13 @@ import torch  # noqa: E402
 import sdfs_via_autodiff_amd as S  # noqa: E402
 
 VARIANTS = {
-    "pair o1 p0 (default)": {},
-    "a3 gathers (SDFS_A3_TABLES=0)": {"SDFS_A3_TABLES": "0"},
+    "default": {},
     "stream 0 (plain line kernels)": {"SDFS_LINE_STREAM": "0"},
     "stream 1 (middle only)": {"SDFS_LINE_STREAM": "1"},
     "stream 2 (last only)": {"SDFS_LINE_STREAM": "2"},
     "stream 7 (both, every extent)": {"SDFS_LINE_STREAM": "7"},
     "stream 5 (middle, every extent)": {"SDFS_LINE_STREAM": "5"},
     "stream 6 (last, every extent)": {"SDFS_LINE_STREAM": "6"},
-    "pair o1 p2": {"SDFS_LINE_PERSIST": "2"},
-    "pair o1 p3": {"SDFS_LINE_PERSIST": "3"},
-    "pair o0 p2": {"SDFS_PAIR_ORDER": "0"},
-    "pair o0 p0": {"SDFS_PAIR_ORDER": "0", "SDFS_LINE_PERSIST": "0"},
     "classic": {"SDFS_PLAN": "classic"},
 }
 
