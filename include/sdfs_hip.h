@@ -400,6 +400,48 @@ int sdfs_stream_copy_dev(sdfs_handle* h, const double* src_dev, double* dst_dev,
 /* Human-readable description of the kernel plan (passes, tiles, grid sizes). */
 int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap);
 
+/* ---- Batched successive approximation: B parameter vectors of one model on one grid shape ---------------------------
+ * The loop of code/solvers.py:19-48 (error = max|x_new - x|, while error > tol and it < max_iter) for B problems at once,
+ * one workgroup per problem with the problem's grid in the LDS of its CU (csrc/batch_kernels.hpp); every problem stops on
+ * its own.  What an estimation loop (SMM, MCMC, a grid search over gamma or psi) calls instead of B times sdfs_create +
+ * sdfs_solve.  fp64; unconditional (slice-identical) transition tensors only, i.e. every Rouwenhorst or Tauchen
+ * discretisation; grids that fit 160 KiB of LDS only (sdfs_batch_lds_bytes).  A problem's result depends on its own
+ * inputs only: not on B, its position in the batch or check_every. */
+typedef struct sdfs_batch sdfs_batch;
+
+enum { SDFS_BATCH_CONVERGED = 0, SDFS_BATCH_MAX_ITER = 1, SDFS_BATCH_NONFINITE = 2 };
+
+/* Dynamic LDS in bytes the batch plan needs for this shape (>= 8 N, <= 163840), SDFS_ERR_UNSUPPORTED if the grid with
+ * its tables does not fit one CU or an extent exceeds 32, SDFS_ERR_ARG for a bad model / ndim / extent.  Makes no
+ * device call. */
+int64_t sdfs_batch_lds_bytes(int model, int ndim, const int64_t* shapes);
+
+/* `params`: B x 13 (SSY) or B x 18 (GCY) scalars, problem-major.  `arrays[i]`: the B copies of array i of sdfs_create,
+ * problem-major (array_sizes[i] elements each).  The folded matrices and the a3 table of every problem come from the
+ * host code sdfs_create runs, so a problem of the batch is the operator sdfs_create builds from the same inputs. */
+int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, const double* params,
+                      const double* const* arrays, const int64_t* array_sizes, int narrays, int device_id,
+                      sdfs_batch** out);
+void sdfs_batch_destroy(sdfs_batch* h);
+const char* sdfs_batch_last_error(const sdfs_batch* h);   /* h == NULL: the last failed sdfs_batch_create / _lds_bytes */
+int sdfs_batch_set_stream(sdfs_batch* h, void* hip_stream, int use_own);   /* as sdfs_set_stream */
+int sdfs_batch_synchronize(sdfs_batch* h);
+
+/* One application per problem: Tw[b] = T_b(w[b]), resid[b] = max|Tw[b] - w[b]| (resid_dev may be NULL).  w_dev and
+ * Tw_dev: B x N doubles, problem-major; w_dev is not written.  Asynchronous on the handle's stream. */
+int sdfs_batch_apply_T_dev(sdfs_batch* h, const double* w_dev, double* Tw_dev, double* resid_dev);
+
+/* Solve all B problems from the start values in w_inout_dev (B x N, results in place).  Read from opts: tol, max_iter,
+ * check_every (most iterations of one launch; 0 = the library's choice, sized so that a launch stays near 0.05 s);
+ * the other fields are ignored.  Host outputs, B entries each: n_iter, final_err (the last max|x_new - x|; +inf for
+ * status 2) and status: 0 converged, 1 max_iter reached, 2 the iterate left the finite range.  Returns when every
+ * problem has stopped; a numerical status of a problem is not an error of the call. */
+int sdfs_batch_solve_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_dev, int64_t* n_iter, double* final_err,
+                         int32_t* status);
+
+/* Human-readable description of the batch plan. */
+int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

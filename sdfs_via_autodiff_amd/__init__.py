@@ -28,6 +28,7 @@ from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_rat
                           wc_ratio_gradient)
 from .pricing import stationary_weights, sdf_moments, term_structure, claim_prices
 from .simulation import simulate
+from .batch import BatchOperator, BatchResult, solve_batch, batch_lds_bytes
 from ._lib import SdfsError, LIB_PATH
 
 __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize_gcy",
@@ -42,4 +43,5 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "single_to_multi", "multi_to_single",
            "discretize_ssy_tangent", "discretize_gcy_tangent", "wc_ratio_sensitivities", "wc_ratio_gradient",
            "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate",
+           "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes",
            "SdfsError", "LIB_PATH"]

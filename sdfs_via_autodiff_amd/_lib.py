@@ -16,6 +16,7 @@ SDFS_ERR_ARG = -1
 SDFS_ERR_UNSUPPORTED = -3
 SDFS_ERR_NUMERIC = -4
 SDFS_MAX_KERNELS = 16
+SDFS_BATCH_CONVERGED, SDFS_BATCH_MAX_ITER, SDFS_BATCH_NONFINITE = 0, 1, 2
 
 
 class SdfsError(RuntimeError):
@@ -110,6 +111,16 @@ SYMBOLS = {
     "sdfs_debug_pow": (C.c_int, [_P, C.c_double, _P, C.c_int64, C.c_int]),
     "sdfs_debug_powy": (C.c_int, [_P, C.c_double, _P, C.c_int64, C.c_int, C.c_int]),
     "sdfs_debug_jvp_storage_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int]),
+    "sdfs_batch_lds_bytes": (C.c_int64, [C.c_int, C.c_int, _I64]),
+    "sdfs_batch_create": (C.c_int, [C.c_int, C.c_int, _I64, C.c_int64, _D, C.POINTER(_D), _I64, C.c_int, C.c_int,
+                                    C.POINTER(_P)]),
+    "sdfs_batch_destroy": (None, [_P]),
+    "sdfs_batch_last_error": (C.c_char_p, [_P]),
+    "sdfs_batch_set_stream": (C.c_int, [_P, _P, C.c_int]),
+    "sdfs_batch_synchronize": (C.c_int, [_P]),
+    "sdfs_batch_apply_T_dev": (C.c_int, [_P, _P, _P, _P]),
+    "sdfs_batch_solve_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _I64, _D, C.POINTER(C.c_int32)]),
+    "sdfs_batch_describe": (C.c_int, [_P, C.c_char_p, C.c_int64]),
 }
 
 

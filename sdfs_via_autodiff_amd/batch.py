@@ -1,0 +1,220 @@
+"""
+Batched fixed-point solves: many parameter vectors of one model on one grid shape.
+
+An estimation loop (SMM, MCMC, a grid search or comparative statics over γ or ψ) solves the same grid at hundreds of
+parameter vectors.  ``solve_batch`` runs them as one batch: successive approximation with the reference's semantics
+(code/solvers.py:19-48), one workgroup per problem with the problem's grid in the LDS of its CU, every problem stopping on
+its own (csrc/batch_kernels.hpp).  Shapes whose grid does not fit one CU run through the single-problem device solve,
+problem after problem, so the call works for every shape the package supports.
+
+    models = [SSY(γ=g) for g in np.linspace(7.5, 10.5, 256)]
+    res = solve_batch(models, (10, 10, 10, 10), tol=1e-6)
+    res.w[b], res.n_iter[b], res.error[b], res.status[b], res.plan
+"""
+import ctypes as C
+import weakref
+from collections import namedtuple
+
+import numpy as np
+
+from . import _lib
+from ._lib import lib
+from .discretize import discretize_gcy, discretize_ssy
+from .models import GCY, SSY
+from .operators import KoopmansOperator, _as_f64
+
+BatchResult = namedtuple("BatchResult", ["w", "n_iter", "error", "status", "plan"])
+BatchResult.__doc__ = """w: (B, *shapes) host array; n_iter, error, status: length B (status 0 converged, 1 max_iter
+reached, 2 the iterate left the finite range); plan: "batch" or "loop"."""
+
+_KINDS = {"ssy": (_lib.SDFS_MODEL_SSY, 4, 13, 10), "gcy": (_lib.SDFS_MODEL_GCY, 6, 18, 15)}   # id, ndim, nparams, narrays
+
+
+def batch_lds_bytes(kind, shapes):
+    """Dynamic LDS in bytes the batch plan needs for ``shapes`` of model ``kind`` ("ssy" / "gcy"), or None where the grid
+    does not fit one CU (sdfs_batch_lds_bytes; no device call)."""
+    model = _KINDS[kind][0]
+    shp = (C.c_int64 * len(shapes))(*[int(s) for s in shapes])
+    n = lib.sdfs_batch_lds_bytes(model, len(shapes), shp)
+    if n == _lib.SDFS_ERR_UNSUPPORTED:
+        return None
+    if n < 0:
+        raise _lib.SdfsError(f"sdfs_batch_lds_bytes failed ({n}): {lib.sdfs_batch_last_error(None).decode()}")
+    return int(n)
+
+
+class BatchOperator:
+    """The handle of one batch as an object: B problems of one model kind on one grid shape, device-resident.
+    ``params``: (B, nparams); ``arrays``: per array of the model's discretisation, its B copies stacked problem-major."""
+
+    def __init__(self, kind, shapes, params, arrays, device=0):
+        model, ndim, nparams, narrays = _KINDS[kind]
+        self.kind = kind
+        self.shapes = tuple(int(s) for s in shapes)
+        if len(self.shapes) != ndim:
+            raise ValueError(f"{kind} grids have {ndim} axes, got shapes {self.shapes}")
+        self._params = _as_f64(params)
+        if self._params.ndim != 2 or self._params.shape[1] != nparams:
+            raise ValueError(f"params must be (B, {nparams}), got {self._params.shape}")
+        self.B = int(self._params.shape[0])
+        if len(arrays) != narrays:
+            raise ValueError(f"{kind} needs {narrays} arrays, got {len(arrays)}")
+        self._arrays = [_as_f64(a).reshape(self.B, -1) for a in arrays]
+        self.device = int(device)
+        self.size = int(np.prod(self.shapes))
+        shp = (C.c_int64 * ndim)(*self.shapes)
+        ptrs = (C.POINTER(C.c_double) * narrays)(*[a.ctypes.data_as(C.POINTER(C.c_double)) for a in self._arrays])
+        sizes = (C.c_int64 * narrays)(*[a.shape[1] for a in self._arrays])
+        h = C.c_void_p()
+        rc = lib.sdfs_batch_create(model, ndim, shp, self.B, self._params.ctypes.data_as(C.POINTER(C.c_double)), ptrs,
+                                   sizes, narrays, self.device, C.byref(h))
+        if rc != 0:
+            raise _lib.SdfsError(f"sdfs_batch_create failed ({rc}): {lib.sdfs_batch_last_error(None).decode()}")
+        self._h = h
+        self._finalizer = weakref.finalize(self, lib.sdfs_batch_destroy, h)
+
+    @classmethod
+    def from_models(cls, models, shapes, method="rouwenhorst", device=0):
+        """The batch of a sequence of SSY or of GCY instances, each discretised on ``shapes``."""
+        models, kind = _kind_of(models)
+        shapes = tuple(int(s) for s in shapes)
+        disc = discretize_ssy if kind == "ssy" else discretize_gcy
+        per_model = [disc(m, shapes, method) for m in models]
+        arrays = [np.stack([_as_f64(a[i]).ravel() for a in per_model]) for i in range(len(per_model[0]))]
+        params = np.array([m.params for m in models], dtype=np.float64)
+        return cls(kind, shapes, params, arrays, device)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        self._finalizer()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise _lib.SdfsError(f"libsdfs_hip error {rc}: {lib.sdfs_batch_last_error(self._h).decode()}")
+
+    def describe_plan(self):
+        buf = C.create_string_buffer(4096)
+        self._check(lib.sdfs_batch_describe(self._h, buf, len(buf)))
+        return buf.value.decode()
+
+    def set_stream(self, stream_ptr, use_own=False):
+        self._check(lib.sdfs_batch_set_stream(self._h, stream_ptr, int(use_own)))
+
+    def synchronize(self):
+        self._check(lib.sdfs_batch_synchronize(self._h))
+
+    # -- device-pointer forms: B x N doubles, problem-major ---------------------------------------------------
+    def apply_dev(self, w_ptr, out_ptr, resid_ptr=None):
+        """out[b] = T_b(w[b]), resid[b] = max|out[b] - w[b]|; asynchronous on the handle's stream."""
+        self._check(lib.sdfs_batch_apply_T_dev(self._h, w_ptr, out_ptr, resid_ptr))
+
+    def solve_dev(self, w_ptr, tol=1e-7, max_iter=10**6, check_every=0):
+        """Successive approximation of every problem from the start values at ``w_ptr`` (results in place).
+        Returns host arrays (n_iter, error, status) of length B."""
+        o = _lib.default_opts()
+        o.tol, o.max_iter, o.check_every = float(tol), int(max_iter), int(check_every)
+        n_iter = np.zeros(self.B, dtype=np.int64)
+        err = np.zeros(self.B, dtype=np.float64)
+        status = np.zeros(self.B, dtype=np.int32)
+        self._check(lib.sdfs_batch_solve_dev(self._h, C.byref(o), w_ptr, n_iter.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             err.ctypes.data_as(C.POINTER(C.c_double)),
+                                             status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return n_iter, err, status
+
+    # -- host forms ------------------------------------------------------------------------------------------
+    def _to_dev(self, a):
+        import torch
+        dev = torch.device("cuda", self.device)
+        t = torch.from_numpy(a).to(dev)
+        torch.cuda.current_stream(dev).synchronize()       # (the library runs on its own stream)
+        return t
+
+    def _host_in(self, w):
+        w = _as_f64(w)
+        if w.shape != (self.B,) + self.shapes:
+            raise ValueError(f"w has shape {w.shape}, the batch is {(self.B,) + self.shapes}")
+        return w
+
+    def __call__(self, w, return_resid=False):
+        """Tw[b] = T_b(w[b]); host ndarray (B, *shapes) in, new host ndarray out."""
+        import torch
+        wd = self._to_dev(self._host_in(w))
+        out = torch.empty_like(wd)
+        res = torch.empty(self.B, dtype=torch.float64, device=wd.device)
+        torch.cuda.current_stream(wd.device).synchronize()
+        self.apply_dev(wd.data_ptr(), out.data_ptr(), res.data_ptr())
+        self.synchronize()
+        Tw = out.cpu().numpy()
+        return (Tw, res.cpu().numpy()) if return_resid else Tw
+
+    def solve(self, w0, tol=1e-7, max_iter=10**6, check_every=0):
+        """Host start values (B, *shapes) in; returns (w, n_iter, error, status)."""
+        wd = self._to_dev(self._host_in(w0).copy())
+        n_iter, err, status = self.solve_dev(wd.data_ptr(), tol, max_iter, check_every)
+        return wd.cpu().numpy(), n_iter, err, status
+
+
+def _kind_of(models):
+    try:
+        models = list(models)
+    except TypeError:
+        raise TypeError("models must be a sequence of SSY or of GCY instances") from None
+    if not models:
+        raise ValueError("models is empty")
+    if all(isinstance(m, SSY) for m in models):
+        return models, "ssy"
+    if all(isinstance(m, GCY) for m in models):
+        return models, "gcy"
+    raise TypeError("models must be all SSY or all GCY instances")
+
+
+def _start_values(w0, B, shapes):
+    if w0 is None:
+        return np.full((B,) + shapes, 800.0)               # the reference's drivers start from 800 everywhere
+    w0 = _as_f64(w0)
+    if w0.shape == shapes:
+        return np.ascontiguousarray(np.broadcast_to(w0, (B,) + shapes))
+    if w0.shape == (B,) + shapes:
+        return w0.copy()
+    raise ValueError(f"w0 has shape {w0.shape}: expected {shapes} or {(B,) + shapes}")
+
+
+def solve_batch(models, shapes, w0=None, tol=1e-7, max_iter=10**6, method="rouwenhorst", device=0, check_every=0):
+    """Wealth-consumption ratios of ``models`` (a sequence of SSY or of GCY instances) on one grid shape by successive
+    approximation, each problem stopping on its own.  ``w0``: None (800 everywhere), one grid for all, or (B, *shapes).
+    Returns a BatchResult; ``plan`` says whether the batch kernel ran ("batch") or the single-problem device solve,
+    problem after problem ("loop": the grid does not fit the LDS of one CU)."""
+    models, kind = _kind_of(models)
+    shapes = tuple(int(s) for s in shapes)
+    ndim = _KINDS[kind][1]
+    if len(shapes) != ndim:
+        raise ValueError(f"{kind} grids have {ndim} axes, got shapes {shapes}")
+    B = len(models)
+    w = _start_values(w0, B, shapes)
+    disc = discretize_ssy if kind == "ssy" else discretize_gcy
+    if batch_lds_bytes(kind, shapes) is not None:
+        op = BatchOperator.from_models(models, shapes, method, device)
+        try:
+            w, n_iter, err, status = op.solve(w, tol, max_iter, check_every)
+        finally:
+            op.close()
+        return BatchResult(w, n_iter, err, status, "batch")
+    n_iter = np.zeros(B, dtype=np.int64)
+    err = np.zeros(B)
+    status = np.zeros(B, dtype=np.int32)
+    kw = {"check_every": int(check_every)} if check_every else {}
+    for b, m in enumerate(models):
+        T = KoopmansOperator(kind, shapes, m.params, disc(m, shapes, method), device)
+        try:
+            w[b], n_iter[b], info = T.solve(w[b], "successive_approx", tol=tol, max_iter=max_iter, **kw)
+        finally:
+            T.close()
+        err[b] = info["final_err"]
+        if info["status"] == _lib.SDFS_ERR_NUMERIC or not np.isfinite(err[b]):
+            status[b] = _lib.SDFS_BATCH_NONFINITE
+        else:
+            status[b] = _lib.SDFS_BATCH_CONVERGED if err[b] <= tol else _lib.SDFS_BATCH_MAX_ITER
+    return BatchResult(w, n_iter, err, status, "loop")

@@ -15,6 +15,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <map>
+#include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -32,6 +34,7 @@
 #include "sens_kernels.hpp"
 #include "price_kernels.hpp"
 #include "sim_kernels.hpp"
+#include "batch_kernels.hpp"
 
 using namespace sdfs;
 
@@ -2522,8 +2525,17 @@ bool slices_identical(const double* p, long long count, size_t len) {
   return true;
 }
 
-int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, const double* params, int nparams,
-                const double* const* arrays, const int64_t* sizes, int narrays) {
+// What setup_model works out on the host: the transition matrices with the scale tables folded in, and the a3 table
+// where it stays a table.  sdfs_create uploads them as they are; sdfs_batch_create packs one set per problem.
+struct ModelTables {
+  std::vector<double> q[MAXD];   // per axis: qcount matrices of n x n
+  std::vector<double> a3;
+  bool keep_a3 = false;          // the z tensor is slice-identical: a3 stays a table the aggregator applies
+};
+
+// The host half of setup_model: checks, the handle's host fields, and the tables into M.  Touches no device.
+int fill_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, const double* params, int nparams,
+               const double* const* arrays, const int64_t* sizes, int narrays, ModelTables& M) {
   h->model = model; h->ndim = ndim;
   long long N = 1;
   for (int a = 0; a < ndim; ++a) {
@@ -2539,7 +2551,9 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
     return 0;
   };
   int rc;
-  std::vector<double> a1, a2, a3;
+  std::vector<double> a1, a2;
+  std::vector<double>& a3 = M.a3;
+  auto& qf = M.q;
   if (model == SDFS_MODEL_SSY) {
     if (ndim != 4 || nparams != 13 || narrays != 10) return fail(h, SDFS_ERR_ARG, "SSY needs ndim 4, 13 params, 10 arrays");
     // params: beta, gamma, psi, mu_c, ...  (ssy_model.py:81)
@@ -2560,7 +2574,6 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
     const char* nm[4] = {"h_lam", "h_c", "h_z", "z"};
     // The scale tables are folded into the transition tensors once, here, so the kernels' pow loops
     // need no lookups:  Ql[l,L]*a1[L] (next state),  a2[k]*Qc[k,K]  and  a3[i,j]*zQ[i,j,J] (current state).
-    std::vector<double> qf[4];
     for (int a = 0; a < 4; ++a) qf[a].assign(arrays[qi[a]], arrays[qi[a]] + sizes[qi[a]]);
     for (int l = 0; l < nl; ++l) for (int L = 0; L < nl; ++L) qf[0][(size_t)l * nl + L] *= a1[L];
     for (int k = 0; k < nc; ++k) for (int K = 0; K < nc; ++K) qf[1][(size_t)k * nc + K] *= a2[k];
@@ -2570,17 +2583,14 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
     if (z_same) qf[3].resize((size_t)nj * nj);
     else for (size_t r = 0; r < a3.size(); ++r) for (int J = 0; J < nj; ++J) qf[3][r * nj + J] *= a3[r];
     for (int a = 0; a < 4; ++a) {
-      double* q = nullptr;
-      if ((rc = upload(h, &q, qf[a].data(), qf[a].size()))) return rc;
-      h->ax[a].Q = q; h->ax[a].qcount = (long long)qf[a].size() / ((long long)h->shape[a] * h->shape[a]);
+      h->ax[a].qcount = (long long)qf[a].size() / ((long long)h->shape[a] * h->shape[a]);
       strncpy(h->ax[a].name, nm[a], sizeof h->ax[a].name - 1);
     }
     h->sens.ip_beta = 0; h->sens.ip_gamma = 1; h->sens.ip_psi = 2; h->sens.ip_mu_c = 3;
     h->sens.ia_hlam = 0; h->sens.ia_sigc = 8; h->sens.ia_z = 6; h->sens.trans = {1, 3, 5, 7};
     h->sens.ax_a1 = 0; h->sens.ax_a2 = 1; h->sens.a3s[2] = nj; h->sens.a3s[3] = 1;
     if (z_same) {
-      if ((rc = upload(h, &h->a3, a3.data(), a3.size()))) return rc;
-      h->a3_host = a3;
+      M.keep_a3 = true;
       h->ax[2].a3s = nj; h->ax[3].a3s = 1;            // a3[i, j]
     } else {
       h->ax[3].qs[2] = 1;               // z_Q[i, j, J] conditioned on the current h_z index
@@ -2606,7 +2616,6 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
     const char* nm[6] = {"z", "z_pi", "h_z", "h_c", "h_zpi", "h_lam"};
     // scale tables folded into the transition tensors (see SSY above):
     // Qhl[f,F]*a1[F],  a2[d]*Qhc[d,D],  a3[b,c,e,a]*zQ[b,c,e,a,A]
-    std::vector<double> qf[6];
     for (int a = 0; a < 6; ++a) qf[a].assign(arrays[qi[a]], arrays[qi[a]] + sizes[qi[a]]);
     for (int f = 0; f < nf; ++f) for (int F = 0; F < nf; ++F) qf[5][(size_t)f * nf + F] *= a1[F];
     for (int d = 0; d < nd; ++d) for (int D = 0; D < nd; ++D) qf[3][(size_t)d * nd + D] *= a2[d];
@@ -2618,9 +2627,7 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
     else for (size_t r = 0; r < a3.size(); ++r) for (int A = 0; A < na; ++A) qf[0][r * na + A] *= a3[r];
     if (zpi_same) qf[1].resize((size_t)(nbp * nbp));
     for (int a = 0; a < 6; ++a) {
-      double* q = nullptr;
-      if ((rc = upload(h, &q, qf[a].data(), qf[a].size()))) return rc;
-      h->ax[a].Q = q; h->ax[a].qcount = (long long)qf[a].size() / ((long long)h->shape[a] * h->shape[a]);
+      h->ax[a].qcount = (long long)qf[a].size() / ((long long)h->shape[a] * h->shape[a]);
       strncpy(h->ax[a].name, nm[a], sizeof h->ax[a].name - 1);
     }
     h->sens.ip_beta = 0; h->sens.ip_gamma = 2; h->sens.ip_psi = 1; h->sens.ip_mu_c = 5;
@@ -2628,8 +2635,7 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
     h->sens.ax_a1 = 5; h->sens.ax_a2 = 3;
     h->sens.a3s[0] = 1; h->sens.a3s[4] = (int)na; h->sens.a3s[2] = (int)(ne * na); h->sens.a3s[1] = (int)(nc * ne * na);
     if (z_same) {
-      if ((rc = upload(h, &h->a3, a3.data(), a3.size()))) return rc;
-      h->a3_host = a3;
+      M.keep_a3 = true;
       h->ax[0].a3s = 1; h->ax[4].a3s = (int)na; h->ax[2].a3s = (int)(ne * na); h->ax[1].a3s = (int)(nc * ne * na);  // a3[b,c,e,a]
     } else {
       // z_Q[b, c, e, a, A]: conditioned on current (z_pi, h_z, h_zpi)
@@ -2649,6 +2655,23 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
     S.hlam.assign(arrays[S.ia_hlam], arrays[S.ia_hlam] + sizes[S.ia_hlam]);
     S.sigc.assign(arrays[S.ia_sigc], arrays[S.ia_sigc] + sizes[S.ia_sigc]);
     S.z.assign(arrays[S.ia_z], arrays[S.ia_z] + sizes[S.ia_z]);
+  }
+  return 0;
+}
+
+int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, const double* params, int nparams,
+                const double* const* arrays, const int64_t* sizes, int narrays) {
+  ModelTables M;
+  int rc = fill_model(h, model, ndim, shapes, params, nparams, arrays, sizes, narrays, M);
+  if (rc) return rc;
+  for (int a = 0; a < ndim; ++a) {
+    double* q = nullptr;
+    if ((rc = upload(h, &q, M.q[a].data(), M.q[a].size()))) return rc;
+    h->ax[a].Q = q;
+  }
+  if (M.keep_a3) {
+    if ((rc = upload(h, &h->a3, M.a3.data(), M.a3.size()))) return rc;
+    h->a3_host = M.a3;
   }
   return 0;
 }
@@ -4152,6 +4175,303 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
                P.vec2 ? P.ept2 : P.ept1, P.d.ntiles, occ);
       s += line;
     }
+  }
+  snprintf(buf, (size_t)cap, "%s", s.c_str());
+  return 0;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// Batched successive approximation (batch_kernels.hpp): B parameter vectors of one model on one grid shape, one
+// workgroup per problem.
+struct sdfs_batch {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  int model = 0, B = 0, num_cus = 256;
+  BatchDesc d;
+  BatchDesc* d_dev = nullptr;    // the kernel reads it from device memory
+  batch_fn fn = nullptr;
+  int nt = 0, k = 0;
+  size_t lds_bytes = 0;
+  double* tab = nullptr;         // [B][tabwords]
+  double* scal = nullptr;        // [B][4]
+  int* status = nullptr;         // [B]
+  long long* it = nullptr;       // [B]
+  double* err = nullptr;         // [B]
+  int* status_host = nullptr;    // pinned
+  std::string errmsg;
+};
+
+namespace {
+
+int bfail(sdfs_batch* h, int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (h) h->errmsg = buf; else g_create_error = buf;
+  return code;
+}
+#define BHIPCHK(h, call)                                                                    \
+  do {                                                                                      \
+    hipError_t e_ = (call);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return bfail((h), SDFS_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
+                   __FILE__, __LINE__);                                                     \
+  } while (0)
+
+// Geometry of the batch plan for one shape; *lds = the dynamic LDS of a workgroup.  Host only.
+int batch_geometry(int model, int ndim, const int64_t* shapes, BatchDesc& d, long long* lds, std::string* why) {
+  auto no = [&](int code, const char* fmt, long long a, long long b) {
+    char buf[256];
+    snprintf(buf, sizeof buf, fmt, a, b);
+    if (why) *why = buf;
+    return code;
+  };
+  if (!shapes) return no(SDFS_ERR_ARG, "shapes is NULL", 0, 0);
+  if (!((model == SDFS_MODEL_SSY && ndim == 4) || (model == SDFS_MODEL_GCY && ndim == 6)))
+    return no(SDFS_ERR_ARG, "model %lld with ndim %lld: SSY needs 4 axes, GCY 6", model, ndim);
+  memset(&d, 0, sizeof d);
+  long long N = 1;
+  for (int a = 0; a < ndim; ++a) {
+    if (shapes[a] < 2) return no(SDFS_ERR_ARG, "shapes[%lld] = %lld: every axis needs >= 2 states", a, shapes[a]);
+    if (shapes[a] > MAXN) return no(SDFS_ERR_UNSUPPORTED, "shapes[%lld] = %lld exceeds the longest axis of the library", a, shapes[a]);
+    N *= shapes[a];
+    if (N * 8 > BATCH_LDS_MAX) return no(SDFS_ERR_UNSUPPORTED, "the grid does not fit the %lld bytes of LDS of one CU (axis %lld)", BATCH_LDS_MAX, a);
+  }
+  d.ndim = ndim; d.N = (int)N; d.nwork = (int)((N + 1) & ~1LL);
+  int off = 0;
+  long long st = N;
+  for (int a = 0; a < ndim; ++a) {
+    d.n[a] = (int)shapes[a];
+    st /= shapes[a];
+    d.stride[a] = (int)st;
+    d.np[a] = batch_row_class(d.n[a]);
+    d.qoff[a] = off;
+    off += d.n[a] * d.np[a];
+  }
+  int na3;
+  if (model == SDFS_MODEL_SSY) {       // a3[i, j] over (h_z, z)
+    d.a3s[2] = d.n[3]; d.a3s[3] = 1;
+    na3 = d.n[2] * d.n[3];
+  } else {                             // a3[b, c, e, a] over (z_pi, h_z, h_zpi, z)
+    d.a3s[0] = 1; d.a3s[4] = d.n[0]; d.a3s[2] = d.n[4] * d.n[0]; d.a3s[1] = d.n[2] * d.n[4] * d.n[0];
+    na3 = d.n[1] * d.n[2] * d.n[4] * d.n[0];
+  }
+  d.a3off = off;
+  d.tabwords = (off + na3 + 1) & ~1;
+  const long long bytes = 8LL * ((long long)d.nwork + d.tabwords + BATCH_RED);
+  if (bytes > BATCH_LDS_MAX)
+    return no(SDFS_ERR_UNSUPPORTED, "grid and tables need %lld bytes of LDS, one CU has %lld", bytes, BATCH_LDS_MAX);
+  int nt, k;
+  if (!batch_kernel_for(d.N, &nt, &k)) return no(SDFS_ERR_UNSUPPORTED, "no kernel for %lld points", N, 0);
+  *lds = bytes;
+  return 0;
+}
+
+int bcheck(sdfs_batch* h) {
+  if (!h) return SDFS_ERR_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return bfail(h, SDFS_ERR_HIP, "hipSetDevice failed");
+  return 0;
+}
+
+int batch_launch(sdfs_batch* h, const BatchArgs& A) {
+  hipLaunchKernelGGL(h->fn, dim3(h->B), dim3(h->nt), h->lds_bytes, h->stream, (const BatchDesc*)h->d_dev, A);
+  BHIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// Iterations per launch when the caller leaves the choice to the library: a launch is to stay near 0.05 s (never
+// above about 0.1 s).  An iteration of one workgroup was measured at 5.5 us (SSY 5^4), 35 us (SSY 10^4) and 62 us
+// (GCY 5^6): about 3 us plus 3.8 ns per grid point (profiles/batch_times.txt); a batch beyond the CU count runs in rounds.
+int batch_default_chunk(const sdfs_batch* h) {
+  const double t_iter = 3e-6 + 3.8e-9 * h->d.N;
+  const double rounds = (double)((h->B + h->num_cus - 1) / h->num_cus);
+  const double c = 0.05 / (t_iter * rounds);
+  return (int)std::min(4096.0, std::max(64.0, c));
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t sdfs_batch_lds_bytes(int model, int ndim, const int64_t* shapes) {
+  BatchDesc d;
+  long long lds = 0;
+  std::string why;
+  const int rc = batch_geometry(model, ndim, shapes, d, &lds, &why);
+  if (rc) { g_create_error = why; return rc; }
+  return lds;
+}
+
+void sdfs_batch_destroy(sdfs_batch* h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  if (h->stream) hipStreamSynchronize(h->stream);
+  if (h->tab) hipFree(h->tab);
+  if (h->d_dev) hipFree(h->d_dev);
+  if (h->scal) hipFree(h->scal);
+  if (h->status) hipFree(h->status);
+  if (h->it) hipFree(h->it);
+  if (h->err) hipFree(h->err);
+  if (h->status_host) hipHostFree(h->status_host);
+  if (h->own_stream) hipStreamDestroy(h->own_stream);
+  delete h;
+}
+
+int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, const double* params,
+                      const double* const* arrays, const int64_t* array_sizes, int narrays, int device_id,
+                      sdfs_batch** out) {
+  if (!out) return bfail(nullptr, SDFS_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  if (!shapes || !params || !arrays || !array_sizes) return bfail(nullptr, SDFS_ERR_ARG, "NULL argument");
+  if (B < 1 || B > (1 << 20)) return bfail(nullptr, SDFS_ERR_ARG, "batch of %lld problems: need 1 .. 2^20", (long long)B);
+  if (narrays < 1 || narrays > 32) return bfail(nullptr, SDFS_ERR_ARG, "narrays %d out of range", narrays);
+  const int nparams = model == SDFS_MODEL_SSY ? 13 : 18;     // ssy_model.py:81, gcy_model.py:72-75
+  BatchDesc d;
+  long long lds = 0;
+  std::string why;
+  int rc = batch_geometry(model, ndim, shapes, d, &lds, &why);
+  if (rc) return bfail(nullptr, rc, "%s", why.c_str());
+  // the tables of every problem, by the host code of sdfs_create (fill_model), packed into the kernel's layout
+  std::vector<double> tab((size_t)B * d.tabwords, 0.0), scal((size_t)B * 4, 0.0);
+  for (int64_t b = 0; b < B; ++b) {
+    sdfs_handle hh;                        // host fields only: fill_model touches no device
+    hh.knobs = read_knobs();
+    const double* arr[32];
+    for (int i = 0; i < narrays; ++i) {
+      if (!arrays[i] || array_sizes[i] < 0) return bfail(nullptr, SDFS_ERR_ARG, "arrays[%d] is NULL", i);
+      arr[i] = arrays[i] + (size_t)b * (size_t)array_sizes[i];
+    }
+    ModelTables M;
+    rc = fill_model(&hh, model, ndim, shapes, params + (size_t)b * nparams, nparams, arr, array_sizes, narrays, M);
+    if (rc) return bfail(nullptr, rc, "problem %lld: %s", (long long)b, hh.err.c_str());
+    if (!M.keep_a3) return bfail(nullptr, SDFS_ERR_UNSUPPORTED, "problem %lld: conditional transition tensors are not supported by the batch plan", (long long)b);
+    for (int a = 0; a < ndim; ++a)
+      if (hh.ax[a].qcount != 1) return bfail(nullptr, SDFS_ERR_UNSUPPORTED, "problem %lld: conditional transition tensors are not supported by the batch plan", (long long)b);
+    double* t = tab.data() + (size_t)b * d.tabwords;
+    for (int a = 0; a < ndim; ++a)
+      for (int r = 0; r < d.n[a]; ++r)
+        for (int c = 0; c < d.n[a]; ++c) t[d.qoff[a] + r * d.np[a] + c] = M.q[a][(size_t)r * d.n[a] + c];
+    if ((long long)M.a3.size() + d.a3off > d.tabwords) return bfail(nullptr, SDFS_ERR_ARG, "a3 table of %zu entries", M.a3.size());
+    std::copy(M.a3.begin(), M.a3.end(), t + d.a3off);
+    scal[4 * b] = hh.beta; scal[4 * b + 1] = hh.theta; scal[4 * b + 2] = 1.0 / hh.theta;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return bfail(nullptr, SDFS_ERR_HIP, "no HIP device available (libsdfs_hip has no CPU fallback)");
+  if (device_id < 0 || device_id >= ndev) return bfail(nullptr, SDFS_ERR_ARG, "device_id %d out of range (%d devices)", device_id, ndev);
+  sdfs_batch* h = new sdfs_batch();
+  h->device = device_id; h->model = model; h->B = (int)B; h->d = d; h->lds_bytes = (size_t)lds;
+  h->fn = batch_kernel_for(d.N, &h->nt, &h->k);
+  auto bail = [&](int rc_) { g_create_error = h->errmsg; sdfs_batch_destroy(h); return rc_; };
+  auto hip = [&](hipError_t e, const char* what) { return e == hipSuccess ? 0 : bfail(h, SDFS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
+  if ((rc = hip(hipSetDevice(device_id), "hipSetDevice"))) return bail(rc);
+  if ((rc = hip(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking), "hipStreamCreate"))) return bail(rc);
+  h->stream = h->own_stream;
+  {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) h->num_cus = prop.multiProcessorCount;
+  }
+  {
+    // dynamic LDS above 64 KB has to be allowed per kernel and device; the attribute is the kernel's, not the handle's,
+    // so it only ever grows
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> allowed;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = allowed[{(const void*)h->fn, device_id}];
+    if (h->lds_bytes > have) {
+      if ((rc = hip(hipFuncSetAttribute((const void*)h->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes), "hipFuncSetAttribute"))) return bail(rc);
+      have = h->lds_bytes;
+    }
+  }
+  if ((rc = hip(hipMalloc((void**)&h->tab, tab.size() * 8), "hipMalloc")) || (rc = hip(hipMalloc((void**)&h->scal, scal.size() * 8), "hipMalloc")) ||
+      (rc = hip(hipMalloc((void**)&h->status, (size_t)B * sizeof(int)), "hipMalloc")) ||
+      (rc = hip(hipMalloc((void**)&h->it, (size_t)B * sizeof(long long)), "hipMalloc")) ||
+      (rc = hip(hipMalloc((void**)&h->err, (size_t)B * 8), "hipMalloc")) ||
+      (rc = hip(hipHostMalloc((void**)&h->status_host, (size_t)B * sizeof(int)), "hipHostMalloc")) ||
+      (rc = hip(hipMalloc((void**)&h->d_dev, sizeof(BatchDesc)), "hipMalloc")) ||
+      (rc = hip(hipMemcpy(h->d_dev, &h->d, sizeof(BatchDesc), hipMemcpyHostToDevice), "hipMemcpy")) ||
+      (rc = hip(hipMemcpy(h->tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice), "hipMemcpy")) ||
+      (rc = hip(hipMemcpy(h->scal, scal.data(), scal.size() * 8, hipMemcpyHostToDevice), "hipMemcpy")))
+    return bail(rc);
+  *out = h;
+  return 0;
+}
+
+const char* sdfs_batch_last_error(const sdfs_batch* h) { return h ? h->errmsg.c_str() : g_create_error.c_str(); }
+
+int sdfs_batch_set_stream(sdfs_batch* h, void* s, int use_own) {
+  int rc = bcheck(h); if (rc) return rc;
+  h->stream = use_own ? h->own_stream : (hipStream_t)s;
+  return 0;
+}
+
+int sdfs_batch_synchronize(sdfs_batch* h) {
+  int rc = bcheck(h); if (rc) return rc;
+  BHIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int sdfs_batch_apply_T_dev(sdfs_batch* h, const double* w_dev, double* Tw_dev, double* resid_dev) {
+  int rc = bcheck(h); if (rc) return rc;
+  if (!w_dev || !Tw_dev) return bfail(h, SDFS_ERR_ARG, "NULL argument");
+  BatchArgs A;
+  memset(&A, 0, sizeof A);
+  A.tab = h->tab; A.scal = h->scal; A.w_in = w_dev; A.w_out = Tw_dev; A.resid = resid_dev;
+  A.tol = 0.0; A.max_iter = 1; A.chunk = 1; A.apply = 1;
+  return batch_launch(h, A);
+}
+
+int sdfs_batch_solve_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_dev, int64_t* n_iter, double* final_err,
+                         int32_t* status) {
+  int rc = bcheck(h); if (rc) return rc;
+  if (!opts || !w_inout_dev || !n_iter || !final_err || !status) return bfail(h, SDFS_ERR_ARG, "NULL argument");
+  if (!(opts->tol >= 0.0)) return bfail(h, SDFS_ERR_ARG, "tol must be >= 0");
+  const int B = h->B;
+  hipStream_t st = h->stream;
+  BatchArgs A;
+  memset(&A, 0, sizeof A);
+  A.tab = h->tab; A.scal = h->scal; A.w_in = w_inout_dev; A.w_out = w_inout_dev;
+  A.status = h->status; A.it = h->it; A.err = h->err;
+  A.tol = opts->tol; A.max_iter = opts->max_iter;
+  A.chunk = opts->check_every > 0 ? (int)opts->check_every : batch_default_chunk(h);
+  hipLaunchKernelGGL(batch_init_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, h->status, h->it, h->err, A.tol, (long long)A.max_iter);
+  BHIPCHK(h, hipGetLastError());
+  // every launch is bounded by A.chunk iterations per problem; the host reads B status words per launch
+  bool open = opts->max_iter > 0;
+  while (open) {
+    if ((rc = batch_launch(h, A))) return rc;
+    BHIPCHK(h, hipMemcpyAsync(h->status_host, h->status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    BHIPCHK(h, hipStreamSynchronize(st));
+    open = false;
+    for (int b = 0; b < B && !open; ++b) open = h->status_host[b] == BATCH_OPEN;
+  }
+  std::vector<long long> it((size_t)B);
+  BHIPCHK(h, hipMemcpyAsync(it.data(), h->it, (size_t)B * sizeof(long long), hipMemcpyDeviceToHost, st));
+  BHIPCHK(h, hipMemcpyAsync(final_err, h->err, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  BHIPCHK(h, hipMemcpyAsync(h->status_host, h->status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+  BHIPCHK(h, hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b) { n_iter[b] = it[b]; status[b] = h->status_host[b]; }
+  return 0;
+}
+
+int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap) {
+  if (!h || !buf || cap < 1) return SDFS_ERR_ARG;
+  std::string s;
+  char line[512];
+  snprintf(line, sizeof line, "batch plan: %d problems, one workgroup each; grid of %d points in LDS, %d threads x %d points in registers\n",
+           h->B, h->d.N, h->nt, h->k);
+  s += line;
+  snprintf(line, sizeof line, "dynamic LDS %zu B: work %d + tables %d + %d doubles; default chunk %d iterations per launch\n",
+           h->lds_bytes, h->d.nwork, h->d.tabwords, BATCH_RED, batch_default_chunk(h));
+  s += line;
+  for (int a = 0; a < h->d.ndim; ++a) {
+    snprintf(line, sizeof line, "axis %d: extent %d stride %d, lines of fp64 FMAs unrolled to %d\n", a, h->d.n[a], h->d.stride[a], h->d.np[a]);
+    s += line;
   }
   snprintf(buf, (size_t)cap, "%s", s.c_str());
   return 0;
