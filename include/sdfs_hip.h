@@ -439,6 +439,24 @@ int sdfs_batch_apply_T_dev(sdfs_batch* h, const double* w_dev, double* Tw_dev, d
 int sdfs_batch_solve_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_dev, int64_t* n_iter, double* final_err,
                          int32_t* status);
 
+/* Newton-Krylov for all B problems from the start values in w_inout_dev (B x N, results in place): the loop of
+ * code/solvers.py:51-95 per problem (x <- x - step, step = BiCGSTAB on (J - I) step = T x - x with x0 = 0, stopped when
+ * |r|^2 <= max(inner_rtol^2 |T x - x|^2, inner_atol^2), on |s|^2 below that threshold, after inner_max_iter iterations
+ * (0 -> 10 N) or on a breakdown (rho, omega or alpha = 0: the step is the x reached so far); error = max|step|, while
+ * error > tol and it < max_iter), one workgroup per problem, every problem stopping on its own
+ * (csrc/batch_newton.hpp).  As in the reference, a step whose |T x - x|_2 <= inner_atol is exactly 0 and ends the problem
+ * as converged.  Read from opts: tol, max_iter, inner_rtol, inner_atol, inner_max_iter and check_every (most
+ * applications, T or J.v, of one launch per problem; 0 = the library's choice, sized so that a launch stays near
+ * 0.05 s); krylov_f32 != 0 is SDFS_ERR_ARG (the vectors are fp64).  Host outputs, B entries each: n_iter (Newton steps),
+ * n_apply (applications of T plus J.v), final_err (the last max|step|; +inf for status 2) and status: 0 converged,
+ * 1 max_iter reached (max_iter < 1: before any application), 2 the iterate, a step or an inner product left the finite
+ * range or an iterate has a point <= 0.  The eight vectors of a problem live in registers up to 2048 grid points and in
+ * global memory beyond (sdfs_batch_describe says which): the handle allocates 7 N doubles per problem at its first
+ * Newton solve, at most 2 GiB -- a larger batch runs group after group.  A problem's w, counts and error depend on its
+ * own inputs only: not on B, its position in the batch or check_every.  Returns when every problem has stopped. */
+int sdfs_batch_newton_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_dev, int64_t* n_iter, int64_t* n_apply,
+                          double* final_err, int32_t* status);
+
 /* Human-readable description of the batch plan. */
 int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap);
 

@@ -4,12 +4,15 @@ Batched fixed-point solves: many parameter vectors of one model on one grid shap
 An estimation loop (SMM, MCMC, a grid search or comparative statics over γ or ψ) solves the same grid at hundreds of
 parameter vectors.  ``solve_batch`` runs them as one batch: successive approximation with the reference's semantics
 (code/solvers.py:19-48), one workgroup per problem with the problem's grid in the LDS of its CU, every problem stopping on
-its own (csrc/batch_kernels.hpp).  Shapes whose grid does not fit one CU run through the single-problem device solve,
+its own (csrc/batch_kernels.hpp), or, with ``algorithm="newton"``, the reference's Newton-Krylov loop
+(code/solvers.py:51-95) in the same one-workgroup-per-problem form (csrc/batch_newton.hpp).  Shapes whose grid does not fit one CU run through the single-problem device solve,
 problem after problem, so the call works for every shape the package supports.
 
     models = [SSY(γ=g) for g in np.linspace(7.5, 10.5, 256)]
     res = solve_batch(models, (10, 10, 10, 10), tol=1e-6)
     res.w[b], res.n_iter[b], res.error[b], res.status[b], res.plan
+    res = solve_batch(models, (10, 10, 10, 10), algorithm="newton", inner_rtol=1e-5, inner_atol=0.0)
+    res.n_apply[b]                       # applications of T plus J.v of problem b
 """
 import ctypes as C
 import weakref
@@ -23,9 +26,23 @@ from .discretize import discretize_gcy, discretize_ssy
 from .models import GCY, SSY
 from .operators import KoopmansOperator, _as_f64
 
-BatchResult = namedtuple("BatchResult", ["w", "n_iter", "error", "status", "plan"])
-BatchResult.__doc__ = """w: (B, *shapes) host array; n_iter, error, status: length B (status 0 converged, 1 max_iter
-reached, 2 the iterate left the finite range); plan: "batch" or "loop"."""
+ALGORITHMS = ("successive_approx", "newton")
+
+
+class BatchResult(namedtuple("BatchResult", ["w", "n_iter", "error", "status", "plan"])):
+    """w: (B, *shapes) host array; n_iter, error, status: length B (status 0 converged, 1 max_iter
+    reached, 2 the iterate left the finite range); plan: "batch" or "loop".  The attribute ``n_apply`` (not a field
+    of the tuple) holds the applications of T plus J.v per problem of a Newton solve; None for successive approximation."""
+
+    def __new__(cls, w, n_iter, error, status, plan, n_apply=None):
+        self = super().__new__(cls, w, n_iter, error, status, plan)
+        self.n_apply = n_apply
+        return self
+
+
+def _check_algorithm(algorithm):
+    if algorithm not in ALGORITHMS:
+        raise ValueError(f"algorithm {algorithm!r}: the batched solve supports \"successive_approx\" and \"newton\"")
 
 _KINDS = {"ssy": (_lib.SDFS_MODEL_SSY, 4, 13, 10), "gcy": (_lib.SDFS_MODEL_GCY, 6, 18, 15)}   # id, ndim, nparams, narrays
 
@@ -111,14 +128,33 @@ class BatchOperator:
         """out[b] = T_b(w[b]), resid[b] = max|out[b] - w[b]|; asynchronous on the handle's stream."""
         self._check(lib.sdfs_batch_apply_T_dev(self._h, w_ptr, out_ptr, resid_ptr))
 
-    def solve_dev(self, w_ptr, tol=1e-7, max_iter=10**6, check_every=0):
-        """Successive approximation of every problem from the start values at ``w_ptr`` (results in place).
-        Returns host arrays (n_iter, error, status) of length B."""
+    def solve_dev(self, w_ptr, tol=1e-7, max_iter=10**6, check_every=0, algorithm="successive_approx", inner_rtol=None,
+                  inner_atol=None, inner_max_iter=None, **opts):
+        """Every problem from the start values at ``w_ptr`` (results in place) by successive approximation, or by
+        Newton-Krylov with ``algorithm="newton"`` (inner_rtol, inner_atol, inner_max_iter: None = the reference's
+        1e-5, 1e-4 and 10 N; further fields of sdfs_opts as keywords).  Returns host arrays (n_iter, error, status) of
+        length B; a Newton solve returns (n_iter, error, status, n_apply)."""
+        _check_algorithm(algorithm)
         o = _lib.default_opts()
         o.tol, o.max_iter, o.check_every = float(tol), int(max_iter), int(check_every)
         n_iter = np.zeros(self.B, dtype=np.int64)
         err = np.zeros(self.B, dtype=np.float64)
         status = np.zeros(self.B, dtype=np.int32)
+        if algorithm == "newton":
+            for k, v in dict(opts, inner_rtol=inner_rtol, inner_atol=inner_atol, inner_max_iter=inner_max_iter).items():
+                if v is None:
+                    continue
+                if not hasattr(o, k):
+                    raise TypeError(f"unknown solver option {k!r}")
+                setattr(o, k, type(getattr(o, k))(v))
+            n_apply = np.zeros(self.B, dtype=np.int64)
+            self._check(lib.sdfs_batch_newton_dev(self._h, C.byref(o), w_ptr, n_iter.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  n_apply.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  err.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  status.ctypes.data_as(C.POINTER(C.c_int32))))
+            return n_iter, err, status, n_apply
+        if opts:
+            raise TypeError(f"unknown solver option {next(iter(opts))!r}")
         self._check(lib.sdfs_batch_solve_dev(self._h, C.byref(o), w_ptr, n_iter.ctypes.data_as(C.POINTER(C.c_int64)),
                                              err.ctypes.data_as(C.POINTER(C.c_double)),
                                              status.ctypes.data_as(C.POINTER(C.c_int32))))
@@ -150,11 +186,15 @@ class BatchOperator:
         Tw = out.cpu().numpy()
         return (Tw, res.cpu().numpy()) if return_resid else Tw
 
-    def solve(self, w0, tol=1e-7, max_iter=10**6, check_every=0):
-        """Host start values (B, *shapes) in; returns (w, n_iter, error, status)."""
+    def solve(self, w0, tol=1e-7, max_iter=10**6, check_every=0, algorithm="successive_approx", inner_rtol=None,
+              inner_atol=None, inner_max_iter=None, **opts):
+        """Host start values (B, *shapes) in; returns (w, n_iter, error, status), and n_apply behind them for
+        ``algorithm="newton"`` (the keywords of solve_dev)."""
+        _check_algorithm(algorithm)
         wd = self._to_dev(self._host_in(w0).copy())
-        n_iter, err, status = self.solve_dev(wd.data_ptr(), tol, max_iter, check_every)
-        return wd.cpu().numpy(), n_iter, err, status
+        out = self.solve_dev(wd.data_ptr(), tol, max_iter, check_every, algorithm, inner_rtol, inner_atol, inner_max_iter,
+                             **opts)
+        return (wd.cpu().numpy(),) + tuple(out)
 
 
 def _kind_of(models):
@@ -182,11 +222,17 @@ def _start_values(w0, B, shapes):
     raise ValueError(f"w0 has shape {w0.shape}: expected {shapes} or {(B,) + shapes}")
 
 
-def solve_batch(models, shapes, w0=None, tol=1e-7, max_iter=10**6, method="rouwenhorst", device=0, check_every=0):
+def solve_batch(models, shapes, w0=None, tol=1e-7, max_iter=10**6, method="rouwenhorst", device=0, check_every=0,
+                algorithm="successive_approx", inner_rtol=None, inner_atol=None, inner_max_iter=None):
     """Wealth-consumption ratios of ``models`` (a sequence of SSY or of GCY instances) on one grid shape by successive
     approximation, each problem stopping on its own.  ``w0``: None (800 everywhere), one grid for all, or (B, *shapes).
+    ``algorithm="newton"`` runs the reference's Newton-Krylov loop instead (inner_rtol, inner_atol, inner_max_iter:
+    None = its 1e-5, 1e-4 and 10 N); the result then carries ``n_apply``.  Any other name is a ValueError.
     Returns a BatchResult; ``plan`` says whether the batch kernel ran ("batch") or the single-problem device solve,
     problem after problem ("loop": the grid does not fit the LDS of one CU)."""
+    _check_algorithm(algorithm)
+    newton = algorithm == "newton"
+    inner = dict(inner_rtol=inner_rtol, inner_atol=inner_atol, inner_max_iter=inner_max_iter) if newton else {}
     models, kind = _kind_of(models)
     shapes = tuple(int(s) for s in shapes)
     ndim = _KINDS[kind][1]
@@ -198,23 +244,26 @@ def solve_batch(models, shapes, w0=None, tol=1e-7, max_iter=10**6, method="rouwe
     if batch_lds_bytes(kind, shapes) is not None:
         op = BatchOperator.from_models(models, shapes, method, device)
         try:
-            w, n_iter, err, status = op.solve(w, tol, max_iter, check_every)
+            out = op.solve(w, tol, max_iter, check_every, algorithm, **inner)
         finally:
             op.close()
-        return BatchResult(w, n_iter, err, status, "batch")
+        return BatchResult(out[0], out[1], out[2], out[3], "batch", out[4] if newton else None)
     n_iter = np.zeros(B, dtype=np.int64)
+    n_apply = np.zeros(B, dtype=np.int64) if newton else None
     err = np.zeros(B)
     status = np.zeros(B, dtype=np.int32)
     kw = {"check_every": int(check_every)} if check_every else {}
     for b, m in enumerate(models):
         T = KoopmansOperator(kind, shapes, m.params, disc(m, shapes, method), device)
         try:
-            w[b], n_iter[b], info = T.solve(w[b], "successive_approx", tol=tol, max_iter=max_iter, **kw)
+            w[b], n_iter[b], info = T.solve(w[b], algorithm, tol=tol, max_iter=max_iter, **inner, **kw)
         finally:
             T.close()
         err[b] = info["final_err"]
+        if newton:
+            n_apply[b] = info["n_apply"]
         if info["status"] == _lib.SDFS_ERR_NUMERIC or not np.isfinite(err[b]):
             status[b] = _lib.SDFS_BATCH_NONFINITE
         else:
             status[b] = _lib.SDFS_BATCH_CONVERGED if err[b] <= tol else _lib.SDFS_BATCH_MAX_ITER
-    return BatchResult(w, n_iter, err, status, "loop")
+    return BatchResult(w, n_iter, err, status, "loop", n_apply)

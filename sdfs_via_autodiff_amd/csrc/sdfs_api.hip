@@ -35,6 +35,7 @@
 #include "price_kernels.hpp"
 #include "sim_kernels.hpp"
 #include "batch_kernels.hpp"
+#include "batch_newton.hpp"
 
 using namespace sdfs;
 
@@ -4201,6 +4202,12 @@ struct sdfs_batch {
   long long* it = nullptr;       // [B]
   double* err = nullptr;         // [B]
   int* status_host = nullptr;    // pinned
+  // Newton-Krylov (batch_newton.hpp); the workspace is allocated at the first Newton solve
+  batch_newton_fn nfn = nullptr;
+  int newton_reg = 0;            // 1: the eight vectors live in registers, 0: in global memory
+  int ws_slots = 0;              // problems per group: the workspace holds this many
+  double* ws = nullptr;          // [ws_slots][7][nwork]
+  BatchNewtonState* nst = nullptr;   // [B]
   std::string errmsg;
 };
 
@@ -4294,6 +4301,43 @@ int batch_default_chunk(const sdfs_batch* h) {
   return (int)std::min(4096.0, std::max(64.0, c));
 }
 
+// problems per group of a Newton solve: the workspace of a group stays within BATCH_NEWTON_WS_MAX
+int batch_newton_slots(const sdfs_batch* h) {
+  const long long per = 8LL * BATCH_NEWTON_VECS * h->d.nwork;
+  return (int)std::min<long long>(h->B, std::max<long long>(1, BATCH_NEWTON_WS_MAX / per));
+}
+
+// Applications per launch of the Newton kernel when the caller leaves the choice to the library: a J.v is taken at the
+// cost of an SA iteration (it has the contractions but no power; the vector updates take their place), so the launch
+// stays near 0.05 s as on the SA path.
+int batch_newton_default_budget(const sdfs_batch* h) {
+  const double t_app = 3e-6 + 3.8e-9 * h->d.N;
+  const int slots = batch_newton_slots(h);
+  const double rounds = (double)((slots + h->num_cus - 1) / h->num_cus);
+  return (int)std::min(4096.0, std::max(64.0, 0.05 / (t_app * rounds)));
+}
+
+// workspace, state and the LDS attribute of the Newton kernel, at the first Newton solve of the handle
+int batch_newton_prepare(sdfs_batch* h) {
+  if (h->ws) return 0;
+  if (!h->nfn) return bfail(h, SDFS_ERR_UNSUPPORTED, "no Newton kernel for %d points", h->d.N);
+  {
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> allowed;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = allowed[{(const void*)h->nfn, h->device}];
+    if (h->lds_bytes > have) {
+      BHIPCHK(h, hipFuncSetAttribute((const void*)h->nfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+      have = h->lds_bytes;
+    }
+  }
+  const int slots = batch_newton_slots(h);
+  if (!h->nst) BHIPCHK(h, hipMalloc((void**)&h->nst, (size_t)h->B * sizeof(BatchNewtonState)));
+  BHIPCHK(h, hipMalloc((void**)&h->ws, (size_t)slots * BATCH_NEWTON_VECS * h->d.nwork * 8));
+  h->ws_slots = slots;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4318,6 +4362,8 @@ void sdfs_batch_destroy(sdfs_batch* h) {
   if (h->it) hipFree(h->it);
   if (h->err) hipFree(h->err);
   if (h->status_host) hipHostFree(h->status_host);
+  if (h->ws) hipFree(h->ws);
+  if (h->nst) hipFree(h->nst);
   if (h->own_stream) hipStreamDestroy(h->own_stream);
   delete h;
 }
@@ -4367,6 +4413,10 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
   sdfs_batch* h = new sdfs_batch();
   h->device = device_id; h->model = model; h->B = (int)B; h->d = d; h->lds_bytes = (size_t)lds;
   h->fn = batch_kernel_for(d.N, &h->nt, &h->k);
+  {
+    int nt = 0, k = 0;
+    h->nfn = batch_newton_kernel_for(d.N, &nt, &k, &h->newton_reg);     // the threads and points of h->fn
+  }
   auto bail = [&](int rc_) { g_create_error = h->errmsg; sdfs_batch_destroy(h); return rc_; };
   auto hip = [&](hipError_t e, const char* what) { return e == hipSuccess ? 0 : bfail(h, SDFS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
   if ((rc = hip(hipSetDevice(device_id), "hipSetDevice"))) return bail(rc);
@@ -4459,6 +4509,53 @@ int sdfs_batch_solve_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_d
   return 0;
 }
 
+int sdfs_batch_newton_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_dev, int64_t* n_iter, int64_t* n_apply,
+                          double* final_err, int32_t* status) {
+  int rc = bcheck(h); if (rc) return rc;
+  if (!opts || !w_inout_dev || !n_iter || !n_apply || !final_err || !status) return bfail(h, SDFS_ERR_ARG, "NULL argument");
+  if (!(opts->tol >= 0.0)) return bfail(h, SDFS_ERR_ARG, "tol must be >= 0");
+  if (!(opts->inner_rtol >= 0.0) || !(opts->inner_atol >= 0.0)) return bfail(h, SDFS_ERR_ARG, "inner_rtol and inner_atol must be >= 0");
+  if (opts->inner_max_iter < 0) return bfail(h, SDFS_ERR_ARG, "inner_max_iter must be >= 0");
+  if (opts->krylov_f32 != 0) return bfail(h, SDFS_ERR_ARG, "the batch Newton solve keeps its Krylov vectors in fp64: krylov_f32 must be 0");
+  if ((rc = batch_newton_prepare(h))) return rc;
+  const int B = h->B;
+  hipStream_t st = h->stream;
+  BatchNewtonArgs A;
+  memset(&A, 0, sizeof A);
+  A.tab = h->tab; A.scal = h->scal; A.w = w_inout_dev; A.ws = h->ws; A.st = h->nst;
+  A.status = h->status; A.it = h->it; A.err = h->err;
+  A.tol = opts->tol; A.rtol2 = opts->inner_rtol * opts->inner_rtol; A.atol2 = opts->inner_atol * opts->inner_atol;
+  A.max_iter = opts->max_iter;
+  A.inner_max = opts->inner_max_iter > 0 ? (long long)opts->inner_max_iter : 10LL * h->d.N;
+  A.budget = opts->check_every > 0 ? (int)opts->check_every : batch_newton_default_budget(h);
+  hipLaunchKernelGGL(batch_newton_init_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, h->status, h->it, h->err, h->nst, A.tol, (long long)A.max_iter);
+  BHIPCHK(h, hipGetLastError());
+  // group after group (one group unless the workspace would pass BATCH_NEWTON_WS_MAX); every launch is bounded by
+  // A.budget applications per problem, and the host reads the group's status words per launch
+  for (int b0 = 0; b0 < B && opts->max_iter > 0; b0 += h->ws_slots) {
+    const int G = std::min(h->ws_slots, B - b0);
+    A.b0 = b0;
+    bool open = true;
+    while (open) {
+      hipLaunchKernelGGL(h->nfn, dim3(G), dim3(h->nt), h->lds_bytes, st, (const BatchDesc*)h->d_dev, A);
+      BHIPCHK(h, hipGetLastError());
+      BHIPCHK(h, hipMemcpyAsync(h->status_host + b0, h->status + b0, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, st));
+      BHIPCHK(h, hipStreamSynchronize(st));
+      open = false;
+      for (int b = b0; b < b0 + G && !open; ++b) open = h->status_host[b] == BATCH_OPEN;
+    }
+  }
+  std::vector<long long> it((size_t)B);
+  std::vector<BatchNewtonState> ns((size_t)B);
+  BHIPCHK(h, hipMemcpyAsync(it.data(), h->it, (size_t)B * sizeof(long long), hipMemcpyDeviceToHost, st));
+  BHIPCHK(h, hipMemcpyAsync(ns.data(), h->nst, (size_t)B * sizeof(BatchNewtonState), hipMemcpyDeviceToHost, st));
+  BHIPCHK(h, hipMemcpyAsync(final_err, h->err, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  BHIPCHK(h, hipMemcpyAsync(h->status_host, h->status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+  BHIPCHK(h, hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b) { n_iter[b] = it[b]; n_apply[b] = ns[b].napply; status[b] = h->status_host[b]; }
+  return 0;
+}
+
 int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap) {
   if (!h || !buf || cap < 1) return SDFS_ERR_ARG;
   std::string s;
@@ -4471,6 +4568,13 @@ int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap) {
   s += line;
   for (int a = 0; a < h->d.ndim; ++a) {
     snprintf(line, sizeof line, "axis %d: extent %d stride %d, lines of fp64 FMAs unrolled to %d\n", a, h->d.n[a], h->d.stride[a], h->d.np[a]);
+    s += line;
+  }
+  if (h->nfn) {
+    const int slots = batch_newton_slots(h);
+    snprintf(line, sizeof line, "newton: w, r, rhat, p, q, x, c_in, c_out %s; workspace 7 x %d doubles per problem, %d problems per group%s; default budget %d applications per launch\n",
+             h->newton_reg ? "in registers (the workspace holds them between launches only)" : "in global memory (w in the caller's buffer, seven in the workspace)",
+             h->d.nwork, slots, slots < h->B ? " (the batch runs group after group)" : "", batch_newton_default_budget(h));
     s += line;
   }
   snprintf(buf, (size_t)cap, "%s", s.c_str());
