@@ -4092,8 +4092,11 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
     s += line;
   }
   if (h->cont) {
+    // cap / ucap / tq (0 = no pre-contraction) and the dynamic LDS are what launch_cont asks for
+    const size_t lds = (size_t)(h->cd.cap + h->cd.ucap) * sizeof(double);
     snprintf(line, sizeof line, "continuous operator: %d-D grid of %lld points x %d nodes, one 256-thread block per point, "
-             "%d-corner multilinear gather + pow per node\n", h->cd.D, h->cd.N, h->cd.M, 1 << h->cd.D);
+             "%d-corner multilinear gather + pow per node, cap %d, ucap %d, tq %d, dynamic LDS %zu B (T) / %zu B (J.v)\n",
+             h->cd.D, h->cd.N, h->cd.M, 1 << h->cd.D, h->cd.cap, h->cd.ucap, h->cd.tq, lds, 2 * lds);
     s += line;
   }
   if (h->fast.ok) {

@@ -1,5 +1,10 @@
 """GPU parity of the continuous-state operator (csrc/cont_kernel.hpp) through the C ABI:
-golden vectors made by the reference's own modules, the numpy oracle, and the solver loops."""
+golden vectors made by the reference's own modules, the numpy oracle, and the solver loops.
+
+Every fixture and grid here is small enough that each block stages its whole box of next states in LDS (at most 840
+grid points, largest box 324 doubles): quadrature always runs the pre-contracted tensor path, Monte Carlo always the
+staged full fold, and the global-gather path is never taken (pinned by tests/test_cont_boxes_cpu.py).  The other
+paths, mixed launches and the large grids are in tests/test_hip_continuous_paths.py."""
 import glob
 import os
 
