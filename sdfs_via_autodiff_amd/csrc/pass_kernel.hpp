@@ -102,12 +102,18 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 // time, the last one gains 3 %, the middle one -- 400 rows of 128 bytes from all over the grid per tile -- LOSES 10 %,
 // and 16^6 (134 MB: the intermediates fit the Infinity Cache) loses 4 % overall.  SDFS_NT is a bit mask: 1 loads,
 // 2 stores of the slice kernels, 4 stores of the middle line pass, 8 stores of the last line pass.
+// SDFS_NT_LD_OFF: the loads' policy per kernel, in the stores' bits -- a kernel named there (the streamed line passes
+// pass NT_MID / NT_LAST) keeps the default policy on its loads although bit 0 of SDFS_NT is set.
 #ifndef SDFS_NT
 #define SDFS_NT 9
 #endif
+#ifndef SDFS_NT_LD_OFF
+#define SDFS_NT_LD_OFF 0
+#endif
 enum { NT_SLICE = 2, NT_MID = 4, NT_LAST = 8 };
+template <int WHO = 0>
 __device__ __forceinline__ v2d ldg_stream(const void* p) {
-  if (SDFS_NT & 1) return __builtin_nontemporal_load(reinterpret_cast<const v2d*>(p));
+  if ((SDFS_NT & 1) && !(SDFS_NT_LD_OFF & WHO)) return __builtin_nontemporal_load(reinterpret_cast<const v2d*>(p));
   return *reinterpret_cast<const v2d*>(p);
 }
 template <int WHO>

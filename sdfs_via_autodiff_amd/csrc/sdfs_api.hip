@@ -951,11 +951,11 @@ int prepare_fast_passes(sdfs_handle* h, std::vector<FastPass>& passes) {
     const int pays = (h->knobs.line_stream & 4) ? 3 : (P.n == 16 ? 2 : (P.n == 32 ? 1 : 3));
     P.stream = (P.line && P.ld.lrest % LINE_R == 0) ? (h->knobs.line_stream & 3 & pays) : 0;
     if (!P.stream) continue;
-    for (int m : {(int)L_MID, (int)L_TLAST, (int)L_TLAST_LIN}) for (int a3f = 0; a3f < 2; ++a3f) {
-      line_fn f = line_stream_variant(P.n, m, a3f != 0);
+    for (int m : {(int)L_MID, (int)L_TLAST, (int)L_TLAST_LIN}) for (int a3f = 0; a3f < 2; ++a3f) for (int early = 0; early < 2; ++early) {
+      line_fn f = line_stream_variant(P.n, m, a3f != 0, early != 0);
       if (!f) return 1;
       hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)line_lds_bytes(P.n));
-      if (line_fn f32 = line_stream_t32_variant(P.n, m, a3f != 0))
+      if (line_fn f32 = line_stream_t32_variant(P.n, m, a3f != 0, early != 0))
         hipFuncSetAttribute((const void*)f32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)line_lds_bytes(P.n));
     }
   }
@@ -1330,7 +1330,7 @@ PassLaunch select_pass(const sdfs_handle* h, const FastPlan& fp, int i, long lon
     L.bytes -= last ? 0.5 * n8 : n8;
     // ... on the streamed forms where the fp64 passes run them (stream_kernels.hpp, IN32 / OUT32)
     if ((P.stream & (last ? 2 : 1)) && h->knobs.no_f32_stream == 0) {
-      if (line_fn sf = line_stream_t32_variant(P.n, last ? L_TLAST : L_MID, a3f)) {
+      if (line_fn sf = line_stream_t32_variant(P.n, last ? L_TLAST : L_MID, a3f, last && a.resid != nullptr && a.old != nullptr)) {
         fn = sf;
         if (!last) {
           long long g = std::min<long long>(P.ld.ntiles, (long long)line_stream_wpc_mid32(P.n) * h->num_cus);
@@ -1341,12 +1341,13 @@ PassLaunch select_pass(const sdfs_handle* h, const FastPlan& fp, int i, long lon
     }
   } else if (!lf32 && ((lm == L_MID && (P.stream & 1)) || ((lm == L_TLAST || lm == L_TLAST_LIN) && (P.stream & 2)))) {
     // stream_kernels.hpp: persistent middle pass with the next tile in flight; last pass with its side stream loaded early
-    fn = line_stream_variant(P.n, lm, a3f);
     if (lm == L_MID) grid = stream_mid_grid(h, P);
     if (lm == L_TLAST && a.push.r != nullptr && a.old != nullptr && P.ld.ntiles <= (long long)MAX_PARTIAL_BLOCKS * AND_MAX_M) {
       L.push = true;
       L.bytes += 3 * n8;                                   // x read, y and r written
     }
+    // (the side stream travels with the tile only in a launch that reads it: the residual's w, the push's x)
+    fn = line_stream_variant(P.n, lm, a3f, lm == L_TLAST && a.old != nullptr && (a.resid != nullptr || L.push));
   }
   if (lm == L_JLAST && !lf32 && bicg) {
     // fused BiCGSTAB iteration: the streamed last pass, one workgroup per tile (the partial sums are counted per tile)
@@ -4123,9 +4124,11 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)line_variant(P.n, L_MID, P.ld.lrest % LINE_R == 0), line_block(P.n), line_lds_bytes(P.n));
         snprintf(line, sizeof line, "pair plan pass %zu: %s lds %zu B block %d tiles %lld (outer %lld x %d chunks of 128 B) %s grid %u blocks/CU %d\n", i,
                  P.label.c_str(), line_lds_bytes(P.n), line_block(P.n), P.ld.ntiles, P.ld.nouter, P.ld.nchunks,
-                 P.stream == 3 ? "streamed (middle pass: persistent, next tile in flight; T's last pass: side stream loaded early)" :
+                 P.stream == 3 ? (line_stream_early_side(P.n) ? "streamed (middle pass: persistent, next tile in flight; T's last pass: side stream in flight with the tile where it is read)"
+                                                              : "streamed (middle pass: persistent, next tile in flight; T's last pass: side stream loaded early)") :
                  P.stream == 1 ? "streamed as a middle pass (persistent, next tile in flight)" :
-                 P.stream == 2 ? "streamed as T's last pass (side stream loaded early)" : "one tile per workgroup",
+                 P.stream == 2 ? (line_stream_early_side(P.n) ? "streamed as T's last pass (side stream in flight with the tile where it is read)"
+                                                              : "streamed as T's last pass (side stream loaded early)") : "one tile per workgroup",
                  (unsigned)P.ld.ntiles, occ);
       }
       s += line;

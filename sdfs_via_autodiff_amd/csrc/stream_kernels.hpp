@@ -11,6 +11,10 @@
 //            would wait for all of it).  Pays for the middle pass (two contractions between load and store).
 //   OLDPF    the last pass's HBM side stream (w for the residual) is loaded for the whole tile before the
 //            contractions instead of a window of four units ahead of the power.
+//   EARLY    (with OLDPF, one tile per workgroup) the side stream's loads are issued right behind the tile's own, in
+//            front of the park, instead of behind it: the order behind the park comes from the persistent form, where
+//            v[] is refilled there.  Taken by the 16- and 20-wide L_TLAST kernels (StreamGeo<N>::EARLY_SIDE: register
+//            counts), in launches that read the side stream.
 // Measured one kernel at a time by tools/probes/kernel_bench.hip (profiles/round3_kernel_bench.txt).  The same
 // treatment of the slice kernel (one wave walking wave tiles, next tile in registers) lost 5 %: that pass is bound
 // by the issue of its power routine, and the 52 extra live registers cost more than the prefetch gains.
@@ -78,13 +82,14 @@ __device__ __forceinline__ long long line_tile_base(const LineDesc& P, const lon
   return (long long)o * nn * P.lrest + (long long)chunk * LINE_R;
 }
 // all loads of one line tile (whole chunks): unit u = tid + k B at byte offset b0 + k bstep of the tile's base
-template <int EPT, int B, int UNITS>
+// (WHO: whose load policy, pass_kernel.hpp SDFS_NT_LD_OFF)
+template <int EPT, int B, int UNITS, int WHO = 0>
 __device__ __forceinline__ void line_tile_load(v2d (&v)[EPT], const double* base, const int tid, const unsigned b0, const unsigned bstep) {
   const char* const inb = reinterpret_cast<const char*>(base);
 #pragma unroll
   for (int k = 0; k < EPT; ++k) {
     const bool rowok = UNITS % B == 0 || tid + k * B < UNITS;
-    v[k] = ldg_stream(inb + (rowok ? b0 + k * bstep : b0));
+    v[k] = ldg_stream<WHO>(inb + (rowok ? b0 + k * bstep : b0));
   }
 }
 
@@ -234,22 +239,27 @@ slice_walk_kernel(const SliceDesc P, const SliceIO io) {
 // B = threads per workgroup (a multiple of 64; the column tiles of a contraction go round the B / 64 waves).
 // PERSIST = false: one tile per workgroup (grid = ntiles, XCD-contiguous order), no next-tile prefetch, one Q fragment
 // set at a time -- the OLDPF side-stream load on its own, at a register budget that admits three workgroups per CU.
+// EARLY (OLDPF, one tile per workgroup; launched only where the side stream is read): wv[] is requested right behind
+// v[], tile first, then side stream (loads return in order: the tile is not delayed), with the Q fragments and the A3F
+// tables in front of both; the park waits for the tile alone and the side stream has the park and both contractions to land.
 // A3F (one tile per workgroup): the aggregator's scale from the two small tables of LineDesc::f1 / f2 -- 20 doubles per
 // tile through LDS and one 16-byte piece per thread -- instead of two gathers and their index arithmetic per unit.
 // IN32 / OUT32 (round 4, opts.t_f32): the tile arrives as / leaves as scaled floats -- 16-byte units of four, row u >> 2,
 // float4 u & 3 of its 16 positions -- and is converted at the park / at the store; everything between (fp64 LDS tile,
 // contractions, epilogue) is the fp64 form's.  IN32 in the last pass of T multiplies by 2^-k (t32_scale_of) at the park.
 template <int N, int MODE, int WPC, bool OLDPF = false, int B = LineGeo<N>::B, bool PERSIST = true, bool A3F = false, bool IN32 = false,
-          bool OUT32 = false>
+          bool OUT32 = false, bool EARLY = false>
 __global__ void __launch_bounds__(B, WPC * B / 256)
 line_stream_kernel(const LineDesc P, const LineIO io) {
   using Geo = LineGeo<N>;
+  static_assert(!EARLY || (OLDPF && !PERSIST && MODE == L_TLAST), "side stream with the tile: the one-tile-per-workgroup last pass of a plain T");
   constexpr int NW = B / 64;
   constexpr int EPT = (Geo::UNITS + B - 1) / B;
   constexpr bool CES = MODE == L_TLAST || MODE == L_TLAST_LIN;
   constexpr bool LINE = MODE == L_TLAST_LIN;
   constexpr bool MULE = MODE == L_JLAST;
   constexpr bool PARTIAL = Geo::UNITS % B != 0;
+  constexpr int WHO = MODE == L_MID ? NT_MID : NT_LAST;       // load policy of the grid streams
   static_assert(MODE != L_TFUSED, "the fused end + start form stays with line_kernel");
   static_assert(!OUT32 || MODE == L_MID, "fp32 output: the middle pass");
   static_assert(!IN32 || MODE == L_MID || MODE == L_TLAST, "fp32 input: the passes of a plain T application");
@@ -270,7 +280,9 @@ line_stream_kernel(const LineDesc P, const LineIO io) {
   const unsigned b0 = ((unsigned)(tid >> 3) * (unsigned)P.lrest + 2u * c2) * 8u;
   const unsigned bstep = (unsigned)(B / 8) * (unsigned)P.lrest * 8u;
   const bool andp = CES && !LINE && io.and_r != nullptr;     // uniform: Anderson's push rides on this pass
-  const bool need_old = CES ? (io.resid != nullptr || andp) : (MULE && P.minus_identity);
+  // (EARLY: the host launches this form only where the side stream is read, so no branch joins a path without its
+  // loads in front of the park -- the wait counts of the park would have to cover both paths, i.e. wait for wv[] too)
+  const bool need_old = EARLY || (CES ? (io.resid != nullptr || andp) : (MULE && P.minus_identity));
   const char* const a3b = reinterpret_cast<const char*>(P.a3);
   const unsigned a3x = (unsigned)P.a3x, a3y = (unsigned)P.a3y;
   const TicketWalk W(P.ntiles, blockIdx.x, io.sched);
@@ -312,12 +324,24 @@ line_stream_kernel(const LineDesc P, const LineIO io) {
   double unscale32 = 1.0;
   if (IN32 && CES) { const PowLane PL0 = pow_lane_init(lane); unscale32 = t32_scale_of(P.t32_ref > 0.0 ? P.t32_ref : io.old[P.ref_off], P.theta, PL0, true); }
   v2d wv[OLDPF ? EPT : 1];
+  v2d f2e = (v2d){1.0, 1.0};
+  double f1e = 1.0;
   if (cur != NO_TILE) {
     {
       unsigned o0; int ch0;
       const long long base0 = line_tile_base(P, cur, N * N, o0, ch0);
+      if constexpr (A3F && EARLY) {
+        // (the two-table scale in front of both streams, like the Q fragments: behind them it would wait for all of them)
+        if (tid < N) f1e = P.f1[(long long)o0 * N + tid];
+        f2e = *reinterpret_cast<const v2d*>(P.f2 + (long long)o0 * P.lrest + (long long)ch0 * LINE_R + 2 * c2);
+      }
       if constexpr (IN32) load32(base0);
-      else line_tile_load<EPT, B, Geo::UNITS>(v, io.in + base0, tid, b0, bstep);
+      else line_tile_load<EPT, B, Geo::UNITS, WHO>(v, io.in + base0, tid, b0, bstep);
+      if constexpr (EARLY) {
+        // (left alone the scheduler interleaves the two streams unit by unit: 0.311 against 0.305 ms in the probe)
+        __builtin_amdgcn_sched_barrier(0);
+        line_tile_load<EPT, B, Geo::UNITS, WHO>(wv, io.old + base0, tid, b0, bstep);
+      }
     }
     for (;;) {
       SDFS_STREAM_STAMP(0);
@@ -340,16 +364,19 @@ line_stream_kernel(const LineDesc P, const LineIO io) {
       unsigned o; int chunk;
       const long long tbase = line_tile_base(P, cur, N * N, o, chunk);
       v2d f2v = (v2d){1.0, 1.0};
-      if constexpr (A3F) {
+      if constexpr (A3F && EARLY) {
+        if (tid < N) sF1[32 * par + tid] = f1e;
+        f2v = f2e;
+      } else if constexpr (A3F) {
         if (tid < N) sF1[32 * par + tid] = P.f1[(long long)o * N + tid];      // (read behind this tile's barriers)
         f2v = *reinterpret_cast<const v2d*>(P.f2 + (long long)o * P.lrest + (long long)chunk * LINE_R + 2 * c2);
       }
-      if constexpr (OLDPF) { if (need_old) line_tile_load<EPT, B, Geo::UNITS>(wv, io.old + tbase, tid, b0, bstep); }
+      if constexpr (OLDPF && !EARLY) { if (need_old) line_tile_load<EPT, B, Geo::UNITS, WHO>(wv, io.old + tbase, tid, b0, bstep); }
       unsigned o1; int ch1;
       const long long nbase = line_tile_base(P, has_next ? nxt : cur, N * N, o1, ch1);
       if (has_next) {
         if constexpr (IN32) load32(nbase);
-        else line_tile_load<EPT, B, Geo::UNITS>(v, io.in + nbase, tid, b0, bstep);
+        else line_tile_load<EPT, B, Geo::UNITS, WHO>(v, io.in + nbase, tid, b0, bstep);
       }
       unsigned nn = NO_TILE;                                         // (published before the third barrier: by then it has returned)
       if (PERSIST && tid == 0 && has_next) nn = W.draw();
@@ -678,58 +705,85 @@ template <int N> struct StreamGeo {
   static constexpr int WPC_MID = N == 32 ? 1 : 2;                       // persistent middle pass: workgroups per CU launched
   static constexpr int WPC_MID32 = N <= 20 ? 3 : WPC_MID;               // ... with fp32 streams: the tile is in flight in half the registers
   static constexpr int WPC_LAST = N == 16 ? 3 : LineGeo<N>::BPC;        // one tile per workgroup: register budget of the last pass
+  // the last pass's side stream issued with the tile (EARLY) where it costs neither scratch nor a wave per SIMD:
+  // VGPRs today -> EARLY of <TLAST a3f | TLAST | TLAST a3f fp32 in | TLAST fp32 in>
+  //   16: 108 -> 108 | 110 -> 112 | 104 -> 108 | 108 -> 112      (4 waves per SIMD)
+  //   20: 139 -> 156 | 144 -> 156 | 126 -> 128 | 134 -> 138      (3, the budget is 168)
+  //   24: 182 -> 163 | 182 -> 192 | 162 -> 168 | 160 -> 199      (fp32 in: 3 -> 2; kept on the old order as a whole)
+  //   32: 160 -> 155 | 162 -> 178 | 154 -> 155 | 152 -> 184      (3 -> 2)
+  // L_TLAST_LIN keeps the old order on every extent: no caller asks a linearising T for a residual, so it has no side
+  // stream to request early (and its 20-wide forms would sit at 166 / 168 VGPRs).
+  static constexpr bool EARLY_SIDE = N <= 20;
 };
-template <int N> inline line_fn line_stream_variant_a3f_n(int mode) {
+// early: the launch is a plain T that reads the side stream (a residual or Anderson's push is asked for); without one
+// the form that never touches io.old runs
+template <int N> inline line_fn line_stream_variant_a3f_n(int mode, bool early) {
   using G = StreamGeo<N>;
+  constexpr bool E = G::EARLY_SIDE;
   switch (mode) {
-    case L_TLAST: return (line_fn)line_stream_kernel<N, L_TLAST, G::WPC_LAST, true, G::B, false, true>;
+    case L_TLAST: return early && E ? (line_fn)line_stream_kernel<N, L_TLAST, G::WPC_LAST, true, G::B, false, true, false, false, E>
+                                    : (line_fn)line_stream_kernel<N, L_TLAST, G::WPC_LAST, true, G::B, false, true>;
     case L_TLAST_LIN: return (line_fn)line_stream_kernel<N, L_TLAST_LIN, G::WPC_LAST, true, G::B, false, true>;
     default: return nullptr;
   }
 }
-template <int N> inline line_fn line_stream_variant_n(int mode) {
+template <int N> inline line_fn line_stream_variant_n(int mode, bool early) {
   using G = StreamGeo<N>;
+  constexpr bool E = G::EARLY_SIDE;
   switch (mode) {
     case L_JLAST: return (line_fn)line_stream_kernel<N, L_JLAST, LineGeo<N>::BPC, false, G::B, false>;      // (krylov_kernels.hpp: with <out, dot_with>)
     case L_MID: return (line_fn)line_stream_kernel<N, L_MID, G::WPC_MID, false, G::B, true>;
-    case L_TLAST: return (line_fn)line_stream_kernel<N, L_TLAST, G::WPC_LAST, true, G::B, false>;
+    case L_TLAST: return early && E ? (line_fn)line_stream_kernel<N, L_TLAST, G::WPC_LAST, true, G::B, false, false, false, false, E>
+                                    : (line_fn)line_stream_kernel<N, L_TLAST, G::WPC_LAST, true, G::B, false>;
     case L_TLAST_LIN: return (line_fn)line_stream_kernel<N, L_TLAST_LIN, G::WPC_LAST, true, G::B, false>;
     default: return nullptr;
   }
 }
 // a3f: LineDesc::f1 / f2 are set (the aggregator's scale factorises for this pass)
-inline line_fn line_stream_variant(int n, int mode, bool a3f = false) {
+inline line_fn line_stream_variant(int n, int mode, bool a3f = false, bool early = false) {
   if (a3f && (mode == L_TLAST || mode == L_TLAST_LIN)) {
     switch (n) {
-      case 16: return line_stream_variant_a3f_n<16>(mode);
-      case 20: return line_stream_variant_a3f_n<20>(mode);
-      case 24: return line_stream_variant_a3f_n<24>(mode);
-      case 32: return line_stream_variant_a3f_n<32>(mode);
+      case 16: return line_stream_variant_a3f_n<16>(mode, early);
+      case 20: return line_stream_variant_a3f_n<20>(mode, early);
+      case 24: return line_stream_variant_a3f_n<24>(mode, early);
+      case 32: return line_stream_variant_a3f_n<32>(mode, early);
       default: return nullptr;
     }
   }
   switch (n) {
-    case 16: return line_stream_variant_n<16>(mode);
-    case 20: return line_stream_variant_n<20>(mode);
-    case 24: return line_stream_variant_n<24>(mode);
-    case 32: return line_stream_variant_n<32>(mode);
+    case 16: return line_stream_variant_n<16>(mode, early);
+    case 20: return line_stream_variant_n<20>(mode, early);
+    case 24: return line_stream_variant_n<24>(mode, early);
+    case 32: return line_stream_variant_n<32>(mode, early);
     default: return nullptr;
   }
 }
+inline bool line_stream_early_side(int n) {
+  switch (n) {
+    case 16: return StreamGeo<16>::EARLY_SIDE;
+    case 20: return StreamGeo<20>::EARLY_SIDE;
+    case 24: return StreamGeo<24>::EARLY_SIDE;
+    case 32: return StreamGeo<32>::EARLY_SIDE;
+    default: return false;
+  }
+}
 // opts.t_f32: the streamed forms on fp32 intermediates (middle pass: floats in, floats out; last pass of T: floats in)
-template <int N> inline line_fn line_stream_t32_variant_n(int mode, bool a3f) {
+template <int N> inline line_fn line_stream_t32_variant_n(int mode, bool a3f, bool early) {
   using G = StreamGeo<N>;
+  constexpr bool E = G::EARLY_SIDE;
   if (mode == L_MID) return (line_fn)line_stream_kernel<N, L_MID, G::WPC_MID32, false, G::B, true, false, true, true>;
+  if (mode == L_TLAST && early && E) return a3f ? (line_fn)line_stream_kernel<N, L_TLAST, G::WPC_LAST, true, G::B, false, true, true, false, E>
+                                                : (line_fn)line_stream_kernel<N, L_TLAST, G::WPC_LAST, true, G::B, false, false, true, false, E>;
   if (mode == L_TLAST) return a3f ? (line_fn)line_stream_kernel<N, L_TLAST, G::WPC_LAST, true, G::B, false, true, true, false>
                                   : (line_fn)line_stream_kernel<N, L_TLAST, G::WPC_LAST, true, G::B, false, false, true, false>;
   return nullptr;
 }
-inline line_fn line_stream_t32_variant(int n, int mode, bool a3f) {
+inline line_fn line_stream_t32_variant(int n, int mode, bool a3f, bool early = false) {
   switch (n) {
-    case 16: return line_stream_t32_variant_n<16>(mode, a3f);
-    case 20: return line_stream_t32_variant_n<20>(mode, a3f);
-    case 24: return line_stream_t32_variant_n<24>(mode, a3f);
-    case 32: return line_stream_t32_variant_n<32>(mode, a3f);
+    case 16: return line_stream_t32_variant_n<16>(mode, a3f, early);
+    case 20: return line_stream_t32_variant_n<20>(mode, a3f, early);
+    case 24: return line_stream_t32_variant_n<24>(mode, a3f, early);
+    case 32: return line_stream_t32_variant_n<32>(mode, a3f, early);
     default: return nullptr;
   }
 }

@@ -32,13 +32,18 @@ __device__ int g_stamp_it;
 #ifndef KB_OLD_NT
 #define KB_OLD_NT 3
 #endif
+#ifndef KB_OLD_NT_LD_OFF
+#define KB_OLD_NT_LD_OFF 0
+#endif
 #define SDFS_POWY KB_OLD_POWY
 #define SDFS_NT KB_OLD_NT
+#define SDFS_NT_LD_OFF KB_OLD_NT_LD_OFF
 #define sdfs sdfs_old
 #include "kb_oldpow/stream_kernels.hpp"
 #undef sdfs
 #undef SDFS_POWY
 #undef SDFS_NT
+#undef SDFS_NT_LD_OFF
 #endif
 #include "../../sdfs_via_autodiff_amd/csrc/stream_kernels.hpp"
 
@@ -228,7 +233,8 @@ int main(int argc, char** argv) {
   const unsigned C = (unsigned)ncu;
   printf("power routine: %s; non-temporal hint on the grid streams: %d (bit 0 loads, bit 1 stores)\n", SDFS_POWY ? "powy (pre-scaled tables, round 4)" : "pow_fast_try (general, rounds 1-3)", SDFS_NT);
 #ifdef KB_OLD_POW
-  printf("sdfs_old:: kernels: power routine %s, non-temporal hint %d\n", KB_OLD_POWY ? "powy" : "general (rounds 1-3)", KB_OLD_NT);
+  printf("sdfs_old:: kernels: power routine %s, non-temporal hint %d, loads kept temporal in %d (4 middle, 8 last line pass)\n", KB_OLD_POWY ? "powy" : "general (rounds 1-3)",
+         KB_OLD_NT, KB_OLD_NT_LD_OFF);
 #endif
   // ---- round 4 (a): what a streaming copy of one grid reaches on this box (the ceiling of a 16 B/point pass) ----
   {
@@ -344,13 +350,24 @@ int main(int argc, char** argv) {
       add("sdfs_old::line_stream<20,TLAST,3,OLDPF,A3F,nonpersist>", [=]() { hipLaunchKernelGGL(fn, dim3(grid), dim3(256), llds, 0, lo, io); }, b3, outB, base, outA);
     }
 #endif
+    // the side stream issued right behind the tile's loads (EARLY) against the library's order (side stream behind the
+    // park); outputs compared with the library kernel's: the arithmetic is the same, maxrel must be 0
+    {
+      Launch libA = line_launch((line_fn)line_stream_kernel<20, L_TLAST, 3, true, 256, false, true>, L3, (unsigned)L3.ntiles, tmpA, outA, w, true);
+      add("line_stream<20,TLAST,3,OLDPF,A3F,nonpersist,EARLY> side stream with the tile", line_launch((line_fn)line_stream_kernel<20, L_TLAST, 3, true, 256, false, true, false, false, true>, L3, (unsigned)L3.ntiles, tmpA, outB, w, true), b3, outB, libA, outA);
+      Launch gatA = line_launch((line_fn)line_stream_kernel<20, L_TLAST, 3, true, 256, false>, L3, (unsigned)L3.ntiles, tmpA, outA, w, true);
+      add("line_stream<20,TLAST,3,OLDPF,256,nonpersist,EARLY> (a3 gathers) side stream with the tile", line_launch((line_fn)line_stream_kernel<20, L_TLAST, 3, true, 256, false, false, false, false, true>, L3, (unsigned)L3.ntiles, tmpA, outB, w, true), b3, outB, gatA, outA);
+    }
     add("line_stream<20,TLAST,3,OLDPF,256,nonpersist> pair (c,d) (a3 gathers)", line_launch((line_fn)line_stream_kernel<20, L_TLAST, 3, true, 256, false>, L3, (unsigned)L3.ntiles, tmpA, outB, w, true), b3, outB, base, outA);
     add("line_stream<20,TLAST,2,OLDPF,A3F,persistent> pair (c,d) wgs " + std::to_string(2 * C), line_launch((line_fn)line_stream_kernel<20, L_TLAST, 2, true, 256, true, true>, L3, 2 * C, tmpA, outB, w, true), b3, outB, base, outA);
     add("line_stream<20,TLAST,2,OLDPF,A3F,512thr,nonpersist> pair (c,d)", line_launch((line_fn)line_stream_kernel<20, L_TLAST, 2, true, 512, false, true>, L3, (unsigned)L3.ntiles, tmpA, outB, w, true, 512), b3, outB, base, outA);
     add("line_stream<20,TLAST,3,OLDPF,A3F,512thr,nonpersist> pair (c,d)", line_launch((line_fn)line_stream_kernel<20, L_TLAST, 3, true, 512, false, true>, L3, (unsigned)L3.ntiles, tmpA, outB, w, true, 512), b3, outB, base, outA);
     add("line_kernel<20,TLAST> pair (c,d), no residual", line_launch((line_fn)line_kernel<20, L_TLAST, false, true, false>, L3, (unsigned)L3.ntiles, tmpA, outA, w, false), b2, nullptr, nullptr, nullptr);
     run_all(rounds);
-    dump_stamps("line_stream<20,TLAST,3,OLDPF,A3F,nonpersist>", line_launch((line_fn)line_stream_kernel<20, L_TLAST, 3, true, 256, false, true>, L3, (unsigned)L3.ntiles, tmpA, outB, w, true));
+    for (int rep = 0; rep < 3; ++rep) {      // (one tile per launch: alternately, three launches each)
+      dump_stamps("line_stream<20,TLAST,3,OLDPF,A3F,nonpersist>", line_launch((line_fn)line_stream_kernel<20, L_TLAST, 3, true, 256, false, true>, L3, (unsigned)L3.ntiles, tmpA, outB, w, true));
+      dump_stamps("line_stream<20,TLAST,3,OLDPF,A3F,nonpersist,EARLY> side stream with the tile", line_launch((line_fn)line_stream_kernel<20, L_TLAST, 3, true, 256, false, true, false, false, true>, L3, (unsigned)L3.ntiles, tmpA, outB, w, true));
+    }
   }
   return 0;
 }
