@@ -190,9 +190,22 @@ int sdfs_apply_vjp_dev(sdfs_handle* h, const double* u_dev, double* out_dev, int
  * sigma_c)^2), a3 = exp((1-gamma)(mu_c + z)).  Linearises at w (one linearising application of T, T w into Tw_dev when not
  * NULL) and leaves that linearisation cached for sdfs_apply_jvp_dev / sdfs_solve_linear_dev.  The J.v term is skipped for
  * directions with dtheta = 0 and dln a1 = 0.  SDFS_ERR_UNSUPPORTED: a non-zero tangent of a transition array (SSY arrays
- * 1, 3, 5, 7; GCY 1, 3, 5, 8, 11, 14 -- the persistence parameters move those), or a continuous, dense or sharded handle. */
+ * 1, 3, 5, 7; GCY 1, 3, 5, 8, 11, 14 -- the persistence parameters move those; see sdfs_param_tangent_gen_dev), or a
+ * continuous, dense or sharded handle. */
 int sdfs_param_tangent_dev(sdfs_handle* h, const double* w_dev, const double* dparams, const double* const* darrays,
                            double* out_dev, double* Tw_dev);
+/* The same with transition matrices that move: `dgen` is NULL (then the call is sdfs_param_tangent_dev) or has ndim entries,
+ * each NULL or 3 n_a HOST doubles (sub-, main, super-diagonal by row; sub[0] and super[n_a - 1] are ignored) of a tridiagonal
+ * left generator G_a by which the caller states dQ_a = G_a Q_a for every matrix of axis a.  A Rouwenhorst matrix has
+ * dTheta_n/drho = G_n Theta_n with G_n[i, i-1] = -i/(2 rho), G_n[i, i] = (n-1)/(2 rho), G_n[i, i+1] = -(n-1-i)/(2 rho), so the
+ * persistence parameters are such directions.  With E = ((T w - 1)/beta)^theta / (a2 a3) each generator adds
+ *   (T w - 1)/theta . sum_j G_a[i_a, j] E(x with i_a -> j) / E(x)
+ * to `out`, one streaming pass per axis after the passes of sdfs_param_tangent_dev.  The transition entries of `darrays` stay
+ * NULL or zero (SDFS_ERR_UNSUPPORTED otherwise, as above).  A generator needs every transition tensor of the handle to be
+ * unconditional (slice-identical, the condition of sdfs_apply_vjp_dev): SDFS_ERR_UNSUPPORTED otherwise, since the stencil
+ * commutes with the other axes' contractions only then.  A non-finite generator entry is SDFS_ERR_ARG. */
+int sdfs_param_tangent_gen_dev(sdfs_handle* h, const double* w_dev, const double* dparams, const double* const* darrays,
+                               const double* const* dgen, double* out_dev, double* Tw_dev);
 /* x = (I - J)^{-1} rhs, or (I - J^T)^{-1} rhs when `transpose` != 0, at the cached linearisation (sdfs_linearize_dev or
  * sdfs_param_tangent_dev): forward sensitivities dw* / dp = (I - J(w*))^{-1} dT/dp, adjoints lambda = (I - J(w*)^T)^{-1} g.
  * BiCGSTAB on the device (x0 = 0, stop when |r|_2 <= max(opts.inner_rtol |rhs|_2, opts.inner_atol), at most

@@ -25,7 +25,8 @@ from .continuous import (ContinuousOperator, build_grid, T_fun_factory, wc_ratio
 from .single_index import (DenseOperator, compute_H_single_index, discretize_single_index, single_index_T,
                            single_to_multi, multi_to_single)
 from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_ratio_sensitivities,
-                          wc_ratio_gradient)
+                          wc_ratio_gradient, rouwenhorst_generator, discretize_ssy_persistence_tangent,
+                          discretize_gcy_persistence_tangent, SSY_PERSISTENCE, GCY_PERSISTENCE)
 from .pricing import stationary_weights, sdf_moments, term_structure, claim_prices
 from .simulation import simulate
 from .batch import BatchOperator, BatchResult, solve_batch, batch_lds_bytes
@@ -42,6 +43,8 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "DenseOperator", "compute_H_single_index", "discretize_single_index", "single_index_T",
            "single_to_multi", "multi_to_single",
            "discretize_ssy_tangent", "discretize_gcy_tangent", "wc_ratio_sensitivities", "wc_ratio_gradient",
+           "rouwenhorst_generator", "discretize_ssy_persistence_tangent", "discretize_gcy_persistence_tangent",
+           "SSY_PERSISTENCE", "GCY_PERSISTENCE",
            "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate",
            "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes",
            "SdfsError", "LIB_PATH"]

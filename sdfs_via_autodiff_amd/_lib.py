@@ -79,6 +79,7 @@ SYMBOLS = {
     "sdfs_apply_vjp": (C.c_int, [_P, _P, _P, _P]),
     "sdfs_apply_vjp_dev": (C.c_int, [_P, _P, _P, C.c_int]),
     "sdfs_param_tangent_dev": (C.c_int, [_P, _P, _D, C.POINTER(_D), _P, _P]),
+    "sdfs_param_tangent_gen_dev": (C.c_int, [_P, _P, _D, C.POINTER(_D), C.POINTER(_D), _P, _P]),
     "sdfs_solve_linear_dev": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _P, _I64, _D]),
     "sdfs_set_tilt_dev": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double]),
     "sdfs_apply_tilted_dev": (C.c_int, [_P, _P, _P]),

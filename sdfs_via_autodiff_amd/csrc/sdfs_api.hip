@@ -185,6 +185,7 @@ struct sdfs_handle {
     std::vector<double> dla3_host;                            // staging of the dln a3 table (kept alive across the async copy)
     double* dla3 = nullptr;                                   // device copy
     double* v = nullptr;                                      // J.v direction of the tangent
+    double* la3 = nullptr;                                    // ln a3 table (k_sens_generator), built on first use
   } sens;
 
   // tilted expectation K (sdfs_set_tilt_dev): its scalings d1 / d2 stand in for c1 / c2 in the J.v kernels; they never
@@ -2683,8 +2684,8 @@ int setup_model(sdfs_handle* h, int model, int ndim, const int64_t* shapes, cons
 //   a3 = exp((1 - gamma) (mu_c + z)),
 // so  dln a1 = dtheta h_lam + theta dh_lam,  dln a2 = (1 - gamma) sigma_c ((1 - gamma) dsigma_c - dgamma sigma_c),
 //     dln a3 = (1 - gamma) (dmu_c + dz) - dgamma (mu_c + z).
-// dln a3 lands in h->sens.dla3_host.  A non-zero tangent of a transition array is SDFS_ERR_UNSUPPORTED: the expectation
-// with a differentiated matrix is not among the kernels.  *need_jv: the J.v term is present (dtheta or dln a1 non-zero).
+// dln a3 lands in h->sens.dla3_host.  A non-zero tangent of a transition array is SDFS_ERR_UNSUPPORTED: a moving matrix
+// is stated as a left generator instead (sdfs_param_tangent_gen_dev).  *need_jv: the J.v term is present (dtheta or dln a1 non-zero).
 int sens_tables(sdfs_handle* h, const double* dparams, const double* const* darrays, double* dtheta, double* dbeta,
                 SensTab& dla1, SensTab& dla2, bool* need_jv, bool* any_a3) {
   auto& S = h->sens;
@@ -2694,7 +2695,7 @@ int sens_tables(sdfs_handle* h, const double* dparams, const double* const* darr
     if (!d) continue;
     for (long long k = 0; k < S.sizes[i]; ++k)
       if (d[k] != 0.0) return fail(h, SDFS_ERR_UNSUPPORTED, "arrays[%d] is a transition array: its tangent must be zero "
-                                   "(persistence parameters are not supported)", i);
+                                   "(a persistence parameter states dQ = G Q through sdfs_param_tangent_gen_dev)", i);
   }
   const double g = S.gamma, psi = S.psi, th = h->theta;
   const double dg = dparams[S.ip_gamma], dpsi = dparams[S.ip_psi], dmu = dparams[S.ip_mu_c];
@@ -3281,6 +3282,11 @@ int sdfs_apply_vjp(sdfs_handle* h, const double* w_host, const double* u_host, d
 
 int sdfs_param_tangent_dev(sdfs_handle* h, const double* w, const double* dparams, const double* const* darrays,
                            double* out, double* Tw) {
+  return sdfs_param_tangent_gen_dev(h, w, dparams, darrays, nullptr, out, Tw);
+}
+
+int sdfs_param_tangent_gen_dev(sdfs_handle* h, const double* w, const double* dparams, const double* const* darrays,
+                               const double* const* dgen, double* out, double* Tw) {
   int rc = check(h); if (rc) return rc;
   if (!w || !out || !dparams) return fail(h, SDFS_ERR_ARG, "NULL argument");
   if (h->cont || h->dense || h->sharded)
@@ -3289,6 +3295,30 @@ int sdfs_param_tangent_dev(sdfs_handle* h, const double* w, const double* dparam
   SensTab dla1, dla2;
   bool need_jv = false, any_a3 = false;
   if ((rc = sens_tables(h, dparams, darrays, &dtheta, &dbeta, dla1, dla2, &need_jv, &any_a3))) return rc;
+  bool any_gen = false;
+  if (dgen) {
+    for (int a = 0; a < h->ndim; ++a) {
+      if (!dgen[a]) continue;
+      any_gen = true;
+      for (int k = 0; k < 3 * h->shape[a]; ++k) {
+        if (k == 0 || k == 3 * h->shape[a] - 1) continue;        // sub[0], super[n - 1]: ignored
+        if (!std::isfinite(dgen[a][k])) return fail(h, SDFS_ERR_ARG, "dgen[%d][%d] is not finite", a, k);
+      }
+    }
+  }
+  if (any_gen) {
+    // dQ_a = G_a Q_a becomes a stencil on E along axis a only when no other axis' matrix depends on the state of a
+    for (int a = 0; a < h->ndim; ++a)
+      if (h->ax[a].qcount != 1)
+        return fail(h, SDFS_ERR_UNSUPPORTED, "a generator tangent needs unconditional transition tensors "
+                                             "(axis %s is conditional)", h->ax[a].name);
+    if (!h->sens.la3) {
+      const auto& S = h->sens;
+      std::vector<double> la3(S.z.size());
+      for (size_t i = 0; i < la3.size(); ++i) la3[i] = (1.0 - S.gamma) * (S.mu_c + S.z[i]);
+      if ((rc = upload(h, &h->sens.la3, la3.data(), la3.size()))) return rc;
+    }
+  }
   if (!Tw) { if ((rc = ensure_buf(h, &h->hostio3))) return rc; Tw = h->hostio3; }
   if (need_jv && (rc = ensure_buf(h, &h->sens.v))) return rc;
   if (any_a3) {
@@ -3323,6 +3353,31 @@ int sdfs_param_tangent_dev(sdfs_handle* h, const double* w, const double* dparam
                        1.0 / h->beta, 1.0 / h->theta, (const double*)Tw, need_jv ? (const double*)out : nullptr,
                        any_a3 ? (const double*)h->sens.dla3 : nullptr, out);
     HIPCHK(h, hipGetLastError());
+  }
+  if (any_gen) {
+    SensTab la2;
+    for (int i = 0; i < SENS_MAXN; ++i) la2.t[i] = 0.0;
+    for (size_t k = 0; k < h->sens.sigc.size(); ++k) {
+      const double s = (1.0 - h->sens.gamma) * h->sens.sigc[k];
+      la2.t[k] = 0.5 * s * s;
+    }
+    for (int a = 0; a < h->ndim; ++a) {
+      if (!dgen[a]) continue;
+      const int n = h->shape[a];
+      SensGen G;
+      memset(&G, 0, sizeof G);
+      for (int i = 0; i < n; ++i) {
+        G.sub[i] = i > 0 ? dgen[a][i] : 0.0;
+        G.diag[i] = dgen[a][n + i];
+        G.sup[i] = i < n - 1 ? dgen[a][2 * n + i] : 0.0;
+      }
+      // Tw, out read and out written; the two neighbours along the axis come from lines the sweep fetches anyway
+      const int cid = h->profiling ? counter_id(h, "sens:generator", 3 * n8, 0) : -1;
+      ProfScope ps(h, cid);
+      hipLaunchKernelGGL(k_sens_generator, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, g, G, la2, a, h->theta, 1.0 / h->theta,
+                         (const double*)Tw, (const double*)h->sens.la3, out);
+      HIPCHK(h, hipGetLastError());
+    }
   }
   return 0;
 }

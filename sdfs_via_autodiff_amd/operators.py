@@ -180,11 +180,42 @@ class KoopmansOperator:
             raise ValueError(f"dparams has {len(dparams)} entries, the operator has {len(self.params)} parameters")
         return (C.c_double * len(dparams))(*dparams)
 
-    def param_tangent_dev(self, w_ptr, dparams, darrays, out_ptr, Tw_ptr=None):
-        """out = dT(w)[dparams, darrays] on device pointers (sdfs_param_tangent_dev); linearises at w."""
+    _TRANSITION_ARRAYS = {"ssy": (1, 3, 5, 7), "gcy": (1, 3, 5, 8, 11, 14)}
+
+    def _dgen(self, dgen):
+        """ctypes array of the per-axis generator pointers (None -> NULL), each 3 n_a doubles: sub, diag, super."""
+        if len(dgen) != len(self.shapes):
+            raise ValueError(f"dgen has {len(dgen)} entries, the grid has {len(self.shapes)} axes")
+        keep = []
+        for a, (g, n) in enumerate(zip(dgen, self.shapes)):
+            if g is None:
+                keep.append(None)
+                continue
+            g = _as_f64(g)
+            if g.shape != (3, n):
+                raise ValueError(f"dgen[{a}] has shape {g.shape}, axis {a} needs (3, {n})")
+            keep.append(g)
+        ptrs = (C.POINTER(C.c_double) * len(keep))(
+            *[g.ctypes.data_as(C.POINTER(C.c_double)) if g is not None else None for g in keep])
+        return ptrs, keep
+
+    def param_tangent_dev(self, w_ptr, dparams, darrays, out_ptr, Tw_ptr=None, dgen=None):
+        """out = dT(w)[dparams, darrays] on device pointers (sdfs_param_tangent_dev); linearises at w.  ``dgen``: one
+        entry per axis, None or the (3, n) sub-, main and super-diagonal of a left generator G with dQ = G Q
+        (sdfs_param_tangent_gen_dev); the transition entries of ``darrays`` are then what the generators state and are
+        not passed on."""
         dp = self._dparams(dparams)
-        ptrs, keep = self._darrays(darrays)
-        check(lib.sdfs_param_tangent_dev(self._h, w_ptr, dp, ptrs, out_ptr, Tw_ptr), self._h)
+        if dgen is None:
+            ptrs, keep = self._darrays(darrays)
+            check(lib.sdfs_param_tangent_dev(self._h, w_ptr, dp, ptrs, out_ptr, Tw_ptr), self._h)
+        else:
+            if darrays is not None:
+                trans = self._TRANSITION_ARRAYS.get(getattr(self, "model_name", None), ())
+                darrays = [None if i in trans else d for i, d in enumerate(darrays)]
+            ptrs, keep = self._darrays(darrays)
+            gptrs, gkeep = self._dgen(dgen)
+            check(lib.sdfs_param_tangent_gen_dev(self._h, w_ptr, dp, ptrs, gptrs, out_ptr, Tw_ptr), self._h)
+            del gkeep
         del keep
 
     def solve_linear_dev(self, rhs_ptr, x_ptr, transpose=False, rtol=1e-10, atol=0.0, max_iter=0):
@@ -276,13 +307,14 @@ class KoopmansOperator:
         torch.cuda.current_stream(dev).synchronize()       # (the library runs on its own stream)
         return out
 
-    def param_tangent(self, w, dparams, darrays):
+    def param_tangent(self, w, dparams, darrays, dgen=None):
         """dT(w)[dparams, darrays]: the tangent of T at a fixed w along one direction of (params, arrays), host
-        ndarrays in and out (``sensitivity.discretize_ssy_tangent`` / ``discretize_gcy_tangent`` make directions)."""
+        ndarrays in and out (``sensitivity.discretize_ssy_tangent`` / ``discretize_gcy_tangent`` make directions;
+        the ``*_persistence_tangent`` twins add the generators ``dgen`` of the transition matrices)."""
         import torch
         (wd,) = self._to_dev(self._host_in(w))
         out = torch.empty_like(wd)
-        self.param_tangent_dev(wd.data_ptr(), dparams, darrays, out.data_ptr())
+        self.param_tangent_dev(wd.data_ptr(), dparams, darrays, out.data_ptr(), dgen=dgen)
         self.synchronize()
         return out.cpu().numpy()
 

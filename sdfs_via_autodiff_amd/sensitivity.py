@@ -14,8 +14,16 @@ vectors stay on the device.
 A direction is given in the reference's own terms, (dparams, darrays): ``discretize_ssy_tangent`` /
 ``discretize_gcy_tangent`` differentiate ``discretize_ssy`` / ``discretize_gcy`` analytically (Rouwenhorst grids are
 linear in the innovation scale and the drift; sigma = phi exp(h)).  A Rouwenhorst matrix depends on the persistence
-only, so every parameter but the persistences leaves the transition matrices alone; the persistence parameters (SSY ρ,
-ρ_z, ρ_c, ρ_λ; GCY ρ_λ, ρ, ρ_c, ρ_z, ρ_ππ, ρ_zπ) would need expectations with a differentiated matrix and are rejected.
+only, so every parameter but the persistences leaves the transition matrices alone, and those two functions refuse
+the persistence parameters (SSY ρ, ρ_z, ρ_c, ρ_λ; GCY ρ_λ, ρ, ρ_c, ρ_z, ρ_ππ, ρ_zπ).
+
+The persistences are differentiated by ``discretize_ssy_persistence_tangent`` / ``discretize_gcy_persistence_tangent``.
+The Rouwenhorst matrix is Θ_n(ρ) = exp(-½ ln ρ · L_n) with L_n the Ehrenfest generator (L[i, i-1] = i, L[i, i+1] =
+n-1-i, L[i, i] = -(n-1)), hence dΘ_n/dρ = G_n Θ_n = Θ_n G_n with the tridiagonal G_n = -L_n / (2ρ)
+(``rouwenhorst_generator``).  The library takes the direction of a matrix as that generator (``dgen``) and turns it
+into a three-point stencil along the axis on a field the linearising pass already produces; the persistence also moves
+its own grid (ψ ∝ 1/√(1-ρ²)) and the drift μ/(1-ρ), which are ordinary state-array tangents.  ``persistence=True``
+opens them to ``wc_ratio_sensitivities`` / ``wc_ratio_gradient``.
 """
 import numpy as np
 
@@ -28,6 +36,13 @@ GCY_PARAMS = ("β", "ψ", "γ", "ρ_λ", "s_λ", "μ_c", "φ_c", "ρ", "ρ_π", 
               "ρ_ππ", "φ_zπ", "ρ_zπ", "s_zπ")
 SSY_SUPPORTED = ("β", "γ", "ψ", "μ_c", "φ_z", "φ_c", "s_z", "s_c", "s_λ")
 GCY_SUPPORTED = ("β", "ψ", "γ", "s_λ", "μ_c", "φ_c", "ρ_π", "φ_z", "s_c", "s_z", "φ_zπ", "s_zπ")
+SSY_PERSISTENCE = ("ρ", "ρ_z", "ρ_c", "ρ_λ")
+GCY_PERSISTENCE = ("ρ_λ", "ρ", "ρ_c", "ρ_z", "ρ_ππ", "ρ_zπ")
+# grid axis whose transition matrix a persistence moves: SSY (h_λ, h_c, h_z, z), GCY (z, z_π, h_z, h_c, h_zπ, h_λ)
+_SSY_AXIS = {"ρ_λ": 0, "ρ_c": 1, "ρ_z": 2, "ρ": 3}
+_GCY_AXIS = {"ρ": 0, "ρ_ππ": 1, "ρ_z": 2, "ρ_c": 3, "ρ_zπ": 4, "ρ_λ": 5}
+_SSY_TRANS = (1, 3, 5, 7)                      # transition array of each axis
+_GCY_TRANS = (1, 3, 5, 8, 11, 14)
 
 
 def _check(names, supported, name, method, model):
@@ -37,7 +52,45 @@ def _check(names, supported, name, method, model):
         raise ValueError(f"unknown {model} parameter {name!r} (one of {', '.join(names)})")
     if name not in supported:
         raise ValueError(f"{model} parameter {name!r} is a persistence parameter: it moves the transition matrices, "
-                         f"which the sensitivities do not differentiate (supported: {', '.join(supported)})")
+                         f"which the sensitivities differentiate only with persistence=True (the "
+                         f"discretize_*_persistence_tangent functions; supported here: {', '.join(supported)})")
+
+
+def _check_persistence(names, persistence, name, method, model):
+    if method != "rouwenhorst":
+        raise ValueError(f"parameter tangents are implemented for Rouwenhorst grids only, not {method!r}")
+    if name not in names:
+        raise ValueError(f"unknown {model} parameter {name!r} (one of {', '.join(names)})")
+    if name not in persistence:
+        raise ValueError(f"{model} parameter {name!r} is not a persistence parameter "
+                         f"(one of {', '.join(persistence)}); use discretize_{model.lower()}_tangent")
+
+
+def rouwenhorst_generator(n, rho):
+    """(3, n): the sub-, main and super-diagonal, by row, of the tridiagonal G_n with dΘ_n/dρ = G_n Θ_n = Θ_n G_n for
+    the Rouwenhorst matrix Θ_n(ρ) (p = q = (1 + ρ) / 2):  G_n[i, i-1] = -i / (2ρ), G_n[i, i] = (n-1) / (2ρ),
+    G_n[i, i+1] = -(n-1-i) / (2ρ).  (sub[0] and super[n-1] lie outside the matrix and are zero.)"""
+    n, rho = int(n), float(rho)
+    if n < 2:
+        raise ValueError("rouwenhorst_generator: n must be >= 2")
+    if rho == 0.0 or not abs(rho) < 1.0:
+        raise ValueError(f"rouwenhorst_generator: rho = {rho!r} must satisfy 0 < |rho| < 1 "
+                         "(the generator is -L / (2 rho))")
+    i = np.arange(n, dtype=np.float64)
+    return np.stack([-i, np.full(n, n - 1.0), -(n - 1.0 - i)]) / (2.0 * rho)
+
+
+def _apply_generator(gen, Q):
+    """G Q over the last two axes of Q (every slice), G given by its three diagonals."""
+    out = gen[1][:, None] * Q
+    out[..., 1:, :] += gen[0][1:, None] * Q[..., :-1, :]
+    out[..., :-1, :] += gen[2][:-1, None] * Q[..., 1:, :]
+    return out
+
+
+def _grid_drho(rho):
+    """d ln(centred Rouwenhorst grid) / d rho: the grid scales with 1 / sqrt(1 - rho^2)."""
+    return rho / (1.0 - rho * rho)
 
 
 def _unit_grid(n, rho):
@@ -84,6 +137,46 @@ def _ssy_tangent(ssy, shapes, name, arr):
         d[9] = dσ_z
         d[6] = dσ_z[:, None] * g_z[None, :]
     return dparams, d
+
+
+def discretize_ssy_persistence_tangent(ssy, shapes, name, method="rouwenhorst"):
+    """(dparams, darrays, dgen): the derivative of (ssy.params, discretize_ssy(ssy, shapes)) with respect to the
+    persistence parameter `name`.  ``darrays`` is the true derivative of every array, transition arrays included
+    (dQ = G Q in every slice); ``dgen`` has one entry per grid axis, None or the (3, n) ``rouwenhorst_generator`` of the
+    axis the parameter moves.  ValueError for any other parameter or a Tauchen grid."""
+    _check_persistence(SSY_PARAMS, SSY_PERSISTENCE, name, method, "SSY")
+    arr = discretize_ssy(ssy, shapes)
+    dparams, d, dgen = _ssy_persistence(ssy, shapes, name, arr)
+    ax = _SSY_AXIS[name]
+    d[_SSY_TRANS[ax]] = _apply_generator(dgen[ax], arr[_SSY_TRANS[ax]])
+    return dparams, _zeros_for_none(d, arr), dgen
+
+
+def _ssy_persistence(ssy, shapes, name, arr):
+    """(dparams, state-array tangents with None for zero and for the transition arrays, dgen)."""
+    n_h_λ, n_h_c, n_h_z, n_z = (int(s) for s in shapes)
+    β, γ, ψ, μ_c, ρ, φ_z, φ_c, ρ_z, ρ_c, ρ_λ, s_z, s_c, s_λ = ssy.params
+    d = [None] * len(arr)
+    dparams = np.zeros(len(SSY_PARAMS))
+    dparams[SSY_PARAMS.index(name)] = 1.0
+    dgen = [None] * 4
+    ax = _SSY_AXIS[name]
+    if name == "ρ_λ":
+        d[0] = arr[0] * _grid_drho(ρ_λ)
+        dgen[ax] = rouwenhorst_generator(n_h_λ, ρ_λ)
+    elif name == "ρ_c":
+        d[2] = arr[2] * _grid_drho(ρ_c)
+        d[8] = arr[8] * d[2]
+        dgen[ax] = rouwenhorst_generator(n_h_c, ρ_c)
+    elif name == "ρ_z":                                  # h_z -> σ_z -> z
+        d[4] = arr[4] * _grid_drho(ρ_z)
+        d[9] = arr[9] * d[4]
+        d[6] = d[9][:, None] * _unit_grid(n_z, ρ)[None, :]
+        dgen[ax] = rouwenhorst_generator(n_h_z, ρ_z)
+    else:                                                # ρ: the z grids (zero drift)
+        d[6] = arr[6] * _grid_drho(ρ)
+        dgen[ax] = rouwenhorst_generator(n_z, ρ)
+    return dparams, d, dgen
 
 
 def discretize_gcy_tangent(gcy, shapes, name, method="rouwenhorst"):
@@ -137,6 +230,63 @@ def _gcy_tangent(gcy, shapes, name, arr):
     return dparams, d
 
 
+def discretize_gcy_persistence_tangent(gcy, shapes, name, method="rouwenhorst"):
+    """(dparams, darrays, dgen): the derivative of (gcy.params, discretize_gcy(gcy, shapes)) with respect to the
+    persistence parameter `name`; see ``discretize_ssy_persistence_tangent``."""
+    _check_persistence(GCY_PARAMS, GCY_PERSISTENCE, name, method, "GCY")
+    arr = discretize_gcy(gcy, shapes)
+    dparams, d, dgen = _gcy_persistence(gcy, shapes, name, arr)
+    ax = _GCY_AXIS[name]
+    d[_GCY_TRANS[ax]] = _apply_generator(dgen[ax], arr[_GCY_TRANS[ax]])
+    return dparams, _zeros_for_none(d, arr), dgen
+
+
+def _gcy_persistence(gcy, shapes, name, arr):
+    """(dparams, state-array tangents with None for zero and for the transition arrays, dgen)."""
+    n_z, n_z_π, n_h_z, n_h_c, n_h_zπ, n_h_λ = (int(s) for s in shapes)
+    (β, ψ, γ, ρ_λ, s_λ, μ_c, φ_c, ρ, ρ_π, φ_z, ρ_c, s_c, ρ_z, s_z,
+     ρ_ππ, φ_zπ, ρ_zπ, s_zπ) = gcy.params
+    z_shape = arr[0].shape
+    d = [None] * len(arr)
+    dparams = np.zeros(len(GCY_PARAMS))
+    dparams[GCY_PARAMS.index(name)] = 1.0
+    dgen = [None] * 6
+    ax = _GCY_AXIS[name]
+    z_π, σ_z, σ_zπ = arr[2], arr[6], arr[12]
+    g_z = _unit_grid(n_z, ρ)                   # z_states[b, c, e, a] = σ_z[c] g_z[a] + ρ_π z_π[e, b] / (1 - ρ)
+    g_zπ = _unit_grid(n_z_π, ρ_ππ)             # z_π_states[e, b] = σ_zπ[e] g_zπ[b]
+
+    def z_from_drift(dz_π):                    # d z_states through its drift ρ_π z_π / (1 - ρ)
+        return np.broadcast_to((ρ_π * dz_π.T / (1.0 - ρ))[:, None, :, None], z_shape).copy()
+    if name == "ρ_λ":
+        d[13] = arr[13] * _grid_drho(ρ_λ)
+        dgen[ax] = rouwenhorst_generator(n_h_λ, ρ_λ)
+    elif name == "ρ_c":
+        d[7] = arr[7] * _grid_drho(ρ_c)
+        d[9] = arr[9] * d[7]
+        dgen[ax] = rouwenhorst_generator(n_h_c, ρ_c)
+    elif name == "ρ_z":                                  # h_z -> σ_z -> z
+        d[4] = arr[4] * _grid_drho(ρ_z)
+        d[6] = σ_z * d[4]
+        d[0] = np.broadcast_to(d[6][None, :, None, None] * g_z[None, None, None, :], z_shape).copy()
+        dgen[ax] = rouwenhorst_generator(n_h_z, ρ_z)
+    elif name == "ρ_zπ":                                 # h_zπ -> σ_zπ -> z_π -> z
+        d[10] = arr[10] * _grid_drho(ρ_zπ)
+        d[12] = σ_zπ * d[10]
+        d[2] = d[12][:, None] * g_zπ[None, :]
+        d[0] = z_from_drift(d[2])
+        dgen[ax] = rouwenhorst_generator(n_h_zπ, ρ_zπ)
+    elif name == "ρ_ππ":                                 # z_π -> z
+        d[2] = z_π * _grid_drho(ρ_ππ)
+        d[0] = z_from_drift(d[2])
+        dgen[ax] = rouwenhorst_generator(n_z_π, ρ_ππ)
+    else:                                                # ρ: the centred z grid and the drift ρ_π z_π / (1 - ρ)
+        centred = np.broadcast_to(σ_z[None, :, None, None] * g_z[None, None, None, :], z_shape)
+        d[0] = centred * _grid_drho(ρ) + z_from_drift(z_π) / (1.0 - ρ)
+        dgen[ax] = rouwenhorst_generator(n_z, ρ)
+    return dparams, d, dgen
+
+
 # -- fixed-point sensitivities ---------------------------------------------------------------------------------------
 def _kind(model):
     if isinstance(model, SSY):
@@ -144,6 +294,10 @@ def _kind(model):
     if isinstance(model, GCY):
         return "gcy", GCY_SUPPORTED, discretize_gcy, _gcy_tangent, GCY_PARAMS
     raise TypeError(f"model must be an SSY or a GCY instance, not {type(model).__name__}")
+
+
+def _persistence_kind(model):
+    return (SSY_PERSISTENCE, _ssy_persistence) if isinstance(model, SSY) else (GCY_PERSISTENCE, _gcy_persistence)
 
 
 _ops = {}
@@ -167,11 +321,18 @@ def _operator(model, shapes):
     return op, arr
 
 
-def _directions(model, shapes, names, arr):
+def _directions(model, shapes, names, arr, persistence=False):
+    """[(dparams, darrays, dgen)] of the named parameters; dgen is None for all but the persistences."""
     kind, supported, _, tangent, allp = _kind(model)
+    pers, ptangent = _persistence_kind(model)
+    out = []
     for nm in names:
-        _check(allp, supported, nm, "rouwenhorst", kind.upper())
-    return [tangent(model, shapes, nm, arr) for nm in names]
+        if persistence and nm in pers:
+            out.append(ptangent(model, shapes, nm, arr))
+        else:
+            _check(allp, supported, nm, "rouwenhorst", kind.upper())
+            out.append(tangent(model, shapes, nm, arr) + (None,))
+    return out
 
 
 def _device_grid(op, x, what):
@@ -186,34 +347,41 @@ def _device_grid(op, x, what):
     return t
 
 
-def wc_ratio_sensitivities(model, shapes, w_star, wrt=None, rtol=1e-10, atol=0.0):
+def wc_ratio_sensitivities(model, shapes, w_star, wrt=None, rtol=1e-10, atol=0.0, persistence=False):
     """{name: dw*/dp_name} (host arrays of the grid's shape) at a converged fixed point ``w_star`` of
     (model, shapes): one tangent of T and one BiCGSTAB solve of (I - J(w*)) x = dT/dp per parameter.  ``wrt``: the
-    Greek parameter names (default: every supported one).  rtol / atol: the solve's stopping rule on |r|_2."""
+    Greek parameter names (default: every supported one).  rtol / atol: the solve's stopping rule on |r|_2.
+    ``persistence=True`` admits the persistence parameters (``SSY_PERSISTENCE`` / ``GCY_PERSISTENCE``) in ``wrt``
+    and makes the default every parameter of the model."""
     import torch
     _, supported, _, _, allp = _kind(model)
-    names = supported if wrt is None else tuple([wrt] if isinstance(wrt, str) else wrt)
+    pers = _persistence_kind(model)[0] if persistence else ()
+    default = allp if persistence else supported
+    names = default if wrt is None else tuple([wrt] if isinstance(wrt, str) else wrt)
     for nm in names:                                               # (ValueError before any device work)
-        _check(allp, supported, nm, "rouwenhorst", type(model).__name__)
+        if nm not in pers:
+            _check(allp, supported, nm, "rouwenhorst", type(model).__name__)
     op, arr = _operator(model, shapes)
-    dirs = _directions(model, shapes, names, arr)
+    dirs = _directions(model, shapes, names, arr, persistence)
     w = _device_grid(op, w_star, "w_star")
     rhs, x, tw = torch.empty_like(w), torch.empty_like(w), torch.empty_like(w)
     out = {}
-    for nm, (dp, da) in zip(names, dirs):
-        op.param_tangent_dev(w.data_ptr(), dp, da, rhs.data_ptr(), tw.data_ptr())
+    for nm, (dp, da, dg) in zip(names, dirs):
+        op.param_tangent_dev(w.data_ptr(), dp, da, rhs.data_ptr(), tw.data_ptr(), dgen=dg)
         op.solve_linear_dev(rhs.data_ptr(), x.data_ptr(), False, rtol, atol)
         out[nm] = x.cpu().numpy()
     return out
 
 
-def wc_ratio_gradient(model, shapes, w_star, g, rtol=1e-10, atol=0.0):
+def wc_ratio_gradient(model, shapes, w_star, g, rtol=1e-10, atol=0.0, persistence=False):
     """{name: d<g, w*>/dp_name} for every supported parameter at a converged ``w_star``: one transposed solve
-    lambda = (I - J(w*)^T)^{-1} g, then <lambda, dT/dp_k> per parameter (a tangent of T each, no further solve)."""
+    lambda = (I - J(w*)^T)^{-1} g, then <lambda, dT/dp_k> per parameter (a tangent of T each, no further solve).
+    ``persistence=True``: every parameter of the model, the persistences included."""
     import torch
-    _, supported, _, _, _ = _kind(model)
+    _, supported, _, _, allp = _kind(model)
+    names = allp if persistence else supported
     op, arr = _operator(model, shapes)
-    dirs = _directions(model, shapes, supported, arr)
+    dirs = _directions(model, shapes, names, arr, persistence)
     w = _device_grid(op, w_star, "w_star")
     gd = _device_grid(op, g, "g")
     lam, rhs, tw = torch.empty_like(w), torch.empty_like(w), torch.empty_like(w)
@@ -221,7 +389,7 @@ def wc_ratio_gradient(model, shapes, w_star, g, rtol=1e-10, atol=0.0):
     op.solve_linear_dev(gd.data_ptr(), lam.data_ptr(), True, rtol, atol)
     lv = lam.view(-1)
     out = {}
-    for nm, (dp, da) in zip(supported, dirs):
-        op.param_tangent_dev(w.data_ptr(), dp, da, rhs.data_ptr(), tw.data_ptr())
+    for nm, (dp, da, dg) in zip(names, dirs):
+        op.param_tangent_dev(w.data_ptr(), dp, da, rhs.data_ptr(), tw.data_ptr(), dgen=dg)
         out[nm] = float(torch.dot(lv, rhs.view(-1)))
     return out

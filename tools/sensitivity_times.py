@@ -6,7 +6,12 @@ Per grid: a Newton solve to the fixed point (the library's default options, for 
 the 12-parameter adjoint gradient (one transposed solve + 12 tangents); the two tangent kernels (HIP-event counters)
 as a fraction of the streaming-copy rate measured in the same process.
 
-    python tools/sensitivity_times.py [16 20]
+``--persistence`` measures the persistence parameters instead (-> profiles/sensitivity_persistence_times.txt): per grid
+k_sens_generator's time and its fraction of the copy rate, one forward d w*/d rho with its J.v count, the 18-parameter
+gradient next to the 12-parameter one and, at 16^6, the device tangent along rho against a Richardson central
+difference of the C oracle's T.
+
+    python tools/sensitivity_times.py [--persistence] [16 20]
 """
 import os
 import sys
@@ -50,7 +55,7 @@ def main(extents):
         print(f"  Newton solve (defaults: tol 1e-7, inner rtol 1e-5, atol 1e-4): {1e3 * t_newton:8.2f} ms, "
               f"{info['n_apply']} applications of T / J.v")
         print(f"  streaming copy: {1e3 * t_copy:.3f} ms = {copy_gbs:.0f} GB/s")
-        dirs = dict(zip(sens.GCY_SUPPORTED, sens._directions(m, shapes, sens.GCY_SUPPORTED, arr)))
+        dirs = {nm: d[:2] for nm, d in zip(sens.GCY_SUPPORTED, sens._directions(m, shapes, sens.GCY_SUPPORTED, arr))}
         rhs, x, tw = torch.empty_like(w), torch.empty_like(w), torch.empty_like(w)
         for name in ("β", "γ"):
             dp, da = dirs[name]
@@ -86,5 +91,82 @@ def main(extents):
         torch.cuda.empty_cache()
 
 
+def richardson_tangent_c_oracle(shapes, name, w):
+    """dT(w)/dp by Richardson-extrapolated central differences (step 1e-4 |p|) of the C oracle's T."""
+    from oracle.c_oracle import COperator
+    p0 = dict(zip(sens.GCY_PARAMS, S.GCY().params))
+
+    def T_at(value):
+        m = S.GCY(**{**p0, name: value})
+        return COperator("gcy", shapes, m.params, S.discretize_gcy(m, shapes))(w)
+
+    def cd(step):
+        return (T_at(p0[name] + step) - T_at(p0[name] - step)) / (2.0 * step)
+    h = 1e-4 * abs(p0[name])
+    return (4.0 * cd(h / 2) - cd(h)) / 3.0
+
+
+def main_persistence(extents):
+    dev = torch.device("cuda", 0)
+    print(f"# {torch.cuda.get_device_name(0)}; times are means over repeated calls after one warm-up call")
+    for n in extents:
+        shapes = (n,) * 6
+        m = S.GCY()
+        op, arr = sens._operator(m, shapes)
+        N = op.size
+        w = torch.full(shapes, 800.0, dtype=torch.float64, device=dev)
+        op.solve_dev(w.data_ptr(), "newton", tol=1e-10, inner_rtol=1e-12, inner_atol=0.0)
+        a = torch.empty_like(w)
+        op.stream_copy_dev(w.data_ptr(), a.data_ptr(), N)
+        t_copy, _ = timed(lambda: op.stream_copy_dev(w.data_ptr(), a.data_ptr(), N), 20)
+        copy_gbs = 16.0 * N / t_copy / 1e9
+        print(f"GCY {n}^6  N = {N}")
+        print(f"  streaming copy: {1e3 * t_copy:.3f} ms = {copy_gbs:.0f} GB/s")
+        dirs = dict(zip(sens.GCY_PERSISTENCE, sens._directions(m, shapes, sens.GCY_PERSISTENCE, arr, True)))
+        rhs, x, tw = torch.empty_like(w), torch.empty_like(w), torch.empty_like(w)
+        dp, da, dg = dirs["ρ"]
+
+        def one():
+            op.param_tangent_dev(w.data_ptr(), dp, da, rhs.data_ptr(), tw.data_ptr(), dgen=dg)
+            return op.solve_linear_dev(rhs.data_ptr(), x.data_ptr(), False, 1e-10, 0.0)
+        one()
+        t, (its, rel) = timed(one, 3)
+        t_tan, _ = timed(lambda: op.param_tangent_dev(w.data_ptr(), dp, da, rhs.data_ptr(), tw.data_ptr(), dgen=dg), 5)
+        print(f"  forward sensitivity d w*/d ρ (rtol 1e-10): {1e3 * t:8.2f} ms  (tangent {1e3 * t_tan:.2f} ms), "
+              f"BiCGSTAB {its} iterations = {2 * its} J.v, final rel. residual {rel:.1e}")
+        g = torch.rand(shapes, dtype=torch.float64, device=dev)
+        S.wc_ratio_gradient(m, shapes, w, g)
+        t12, _ = timed(lambda: S.wc_ratio_gradient(m, shapes, w, g), 2)
+        S.wc_ratio_gradient(m, shapes, w, g, persistence=True)
+        t18, _ = timed(lambda: S.wc_ratio_gradient(m, shapes, w, g, persistence=True), 2)
+        print(f"  adjoint gradient (rtol 1e-10): 12 parameters {1e3 * t12:8.2f} ms, all 18 parameters {1e3 * t18:8.2f} ms")
+        # the generator pass alone, by the axis it runs along (axis 5 is the fastest)
+        for name in sens.GCY_PERSISTENCE:
+            dp_, da_, dg_ = dirs[name]
+            axis = [i for i, gen in enumerate(dg_) if gen is not None][0]
+            op.set_profiling(True)
+            op.reset_counters()
+            for _ in range(10):
+                op.param_tangent_dev(w.data_ptr(), dp_, da_, rhs.data_ptr(), tw.data_ptr(), dgen=dg_)
+            for k in op.counters():
+                if k["name"] == "sens:generator":
+                    tk = k["total_ms"] / k["launches"]
+                    gbs = k["alg_bytes"] / (tk * 1e-3) / 1e9
+                    print(f"  sens:generator, {name:<5s} (axis {axis}) {1e3 * tk:8.1f} us  {gbs:6.0f} GB/s = "
+                          f"{gbs / copy_gbs:.2f} of the copy rate")
+            op.set_profiling(False)
+        if n == 16:
+            wh = 500.0 + 200.0 * np.random.default_rng(96).random(shapes)
+            got = op.param_tangent(wh, dp, da, dgen=dg)
+            want = richardson_tangent_c_oracle(shapes, "ρ", wh)
+            print(f"  device dT/dρ at a non-constant w vs Richardson central difference of the C oracle's T: "
+                  f"{np.max(np.abs(got - want)) / np.max(np.abs(want)):.3e} of max|dT/dρ| = {np.max(np.abs(want)):.3e}")
+        del a, rhs, x, tw, w, g
+        sens._ops.clear()
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
-    main([int(a) for a in sys.argv[1:]] or [16, 20])
+    args = [a for a in sys.argv[1:] if a != "--persistence"]
+    run = main_persistence if "--persistence" in sys.argv[1:] else main
+    run([int(a) for a in args] or [16, 20])
