@@ -470,6 +470,36 @@ int sdfs_batch_solve_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_d
 int sdfs_batch_newton_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_dev, int64_t* n_iter, int64_t* n_apply,
                           double* final_err, int32_t* status);
 
+/* Doubles per problem of the moment block of sdfs_batch_adjoint_dev.  Layout, with n_lam, n_c the extents of the h_lam
+ * and h_c axes (SSY axes 0 and 1, GCY axes 5 and 3) and na3 the entries of the a3 table (SSY [h_z, z]; GCY [z_pi, h_z,
+ * h_zpi, z], C order):   s0 s1 s2 | R[ndim] | M1[n_lam] | M2[n_c] | M3[na3]. */
+int64_t sdfs_batch_adjoint_words(const sdfs_batch* h);
+
+/* Adjoint moments for all B problems at w_dev (B x N, normally the batch's w*): lambda = (I - J(w)^T)^(-1) g by BiCGSTAB
+ * from x0 = 0 with the stopping rule of the Newton kernel's inner solve (|r|^2 <= max(inner_rtol^2 |g|^2, inner_atol^2),
+ * the early exit on |s|^2, the breakdown exits, inner_max_iter with 0 -> 10 N), one workgroup per problem
+ * (csrc/batch_adjoint.hpp), then with m = lambda (T w - 1), mu = (J^T lambda) w and E = H0(a1 w^theta):
+ *   s0 = sum m, s1 = sum m ln((T w - 1) / beta), s2 = sum mu ln w, M1[i_lam] = sum mu over the other axes, M2[i_c] the
+ *   same of m, M3[ia3] = sum m over (h_c, h_lam), R[k] = sum m (i_k (E(i_k - 1) / E(i_k) - 1) + (n_k - 1 - i_k)
+ *   (E(i_k + 1) / E(i_k) - 1)) per grid axis k,
+ * from which  d<g, w*>/dp = dbeta/beta s0 - dtheta/theta s1 + (<M2, dln a2> + <M3, dln a3>)/theta + (dtheta s2 + <M1,
+ * dln a1>)/theta - [p = rho_k] R[k] / (2 rho_k theta)  for every parameter (dtheta, dln a1, dln a2, dln a3 as
+ * sdfs_param_tangent_dev forms them).  g_dev: B x N with g_stride = N, or one grid for all with g_stride = 0.  lam_dev
+ * (B x N) may be NULL.  moments_dev: B x sdfs_batch_adjoint_words(h).  Read from opts: inner_rtol, inner_atol,
+ * inner_max_iter and check_every (most applications of one launch per problem; 0 = the library's choice);
+ * krylov_f32 != 0 is SDFS_ERR_ARG.  Host outputs, B entries each: n_iter (BiCGSTAB iterations), n_apply (applications:
+ * the linearising T, two per full iteration, those of the moment phase), rel_resid (the true |g - lambda + J^T lambda|_2
+ * / |g|_2 at the final lambda; where it is above the tolerance after the recurrence's residual has converged, the solve
+ * restarts from it, lambda kept, at most twice),
+ * resid_T (max|T w - w| at w_dev) and status: 0 converged; 1 stopped above the tolerance (inner_max_iter or a breakdown;
+ * the moments are those of lambda where it stopped); 2 a non-finite inner product, w, T w or lambda (the problem's lambda
+ * and moments are NaN; no other problem is touched).  g = 0 gives lambda = 0, zero moments, status 0 and n_iter 0.  The
+ * vectors live as those of the Newton solve, in its workspace; a problem's lambda, moments and counts depend on its own
+ * inputs only: not on B, its position in the batch or check_every. */
+int sdfs_batch_adjoint_dev(sdfs_batch* h, const sdfs_opts* opts, const double* w_dev, const double* g_dev, int64_t g_stride,
+                           double* lam_dev, double* moments_dev, int64_t* n_iter, int64_t* n_apply, double* rel_resid,
+                           double* resid_T, int32_t* status);
+
 /* Human-readable description of the batch plan. */
 int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap);
 

@@ -26,10 +26,11 @@ from .single_index import (DenseOperator, compute_H_single_index, discretize_sin
                            single_to_multi, multi_to_single)
 from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_ratio_sensitivities,
                           wc_ratio_gradient, rouwenhorst_generator, discretize_ssy_persistence_tangent,
-                          discretize_gcy_persistence_tangent, SSY_PERSISTENCE, GCY_PERSISTENCE)
+                          discretize_gcy_persistence_tangent, SSY_PERSISTENCE, GCY_PERSISTENCE,
+                          adjoint_moments_to_gradient)
 from .pricing import stationary_weights, sdf_moments, term_structure, claim_prices
 from .simulation import simulate
-from .batch import BatchOperator, BatchResult, solve_batch, batch_lds_bytes
+from .batch import BatchOperator, BatchResult, solve_batch, batch_lds_bytes, BatchGradient, gradient_batch
 from ._lib import SdfsError, LIB_PATH
 
 __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize_gcy",
@@ -44,7 +45,7 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "single_to_multi", "multi_to_single",
            "discretize_ssy_tangent", "discretize_gcy_tangent", "wc_ratio_sensitivities", "wc_ratio_gradient",
            "rouwenhorst_generator", "discretize_ssy_persistence_tangent", "discretize_gcy_persistence_tangent",
-           "SSY_PERSISTENCE", "GCY_PERSISTENCE",
+           "SSY_PERSISTENCE", "GCY_PERSISTENCE", "adjoint_moments_to_gradient",
            "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate",
-           "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes",
+           "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes", "BatchGradient", "gradient_batch",
            "SdfsError", "LIB_PATH"]

@@ -122,6 +122,9 @@ SYMBOLS = {
     "sdfs_batch_apply_T_dev": (C.c_int, [_P, _P, _P, _P]),
     "sdfs_batch_solve_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _I64, _D, C.POINTER(C.c_int32)]),
     "sdfs_batch_newton_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _I64, _I64, _D, C.POINTER(C.c_int32)]),
+    "sdfs_batch_adjoint_words": (C.c_int64, [_P]),
+    "sdfs_batch_adjoint_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _P, C.c_int64, _P, _P, _I64, _I64, _D, _D,
+                                         C.POINTER(C.c_int32)]),
     "sdfs_batch_describe": (C.c_int, [_P, C.c_char_p, C.c_int64]),
 }
 

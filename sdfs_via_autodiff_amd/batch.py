@@ -160,6 +160,34 @@ class BatchOperator:
                                              status.ctypes.data_as(C.POINTER(C.c_int32))))
         return n_iter, err, status
 
+    def adjoint_words(self):
+        """Doubles per problem of the moment block: s0 s1 s2 | R[ndim] | M1[n_λ] | M2[n_c] | M3[a3 table]."""
+        n = lib.sdfs_batch_adjoint_words(self._h)
+        if n < 0:
+            self._check(int(n))
+        return int(n)
+
+    def adjoint_dev(self, w_ptr, g_ptr, g_stride, lam_ptr, moments_ptr, rtol=1e-10, atol=0.0, inner_max_iter=None,
+                    check_every=0):
+        """λ[b] = (I - J_b(w[b])ᵀ)⁻¹ g[b] and the adjoint moments of every problem (sdfs_batch_adjoint_dev): ``g_stride``
+        0 (one grid for all) or N; ``lam_ptr`` may be None.  Returns host arrays (n_iter, n_apply, rel_resid, resid_T,
+        status) of length B."""
+        o = _lib.default_opts()
+        o.inner_rtol, o.inner_atol, o.check_every = float(rtol), float(atol), int(check_every)
+        o.inner_max_iter = 0 if inner_max_iter is None else int(inner_max_iter)
+        n_iter = np.zeros(self.B, dtype=np.int64)
+        n_apply = np.zeros(self.B, dtype=np.int64)
+        rel = np.zeros(self.B, dtype=np.float64)
+        res_T = np.zeros(self.B, dtype=np.float64)
+        status = np.zeros(self.B, dtype=np.int32)
+        self._check(lib.sdfs_batch_adjoint_dev(self._h, C.byref(o), w_ptr, g_ptr, int(g_stride), lam_ptr, moments_ptr,
+                                               n_iter.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               n_apply.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               rel.ctypes.data_as(C.POINTER(C.c_double)),
+                                               res_T.ctypes.data_as(C.POINTER(C.c_double)),
+                                               status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return n_iter, n_apply, rel, res_T, status
+
     # -- host forms ------------------------------------------------------------------------------------------
     def _to_dev(self, a):
         import torch
@@ -195,6 +223,29 @@ class BatchOperator:
         out = self.solve_dev(wd.data_ptr(), tol, max_iter, check_every, algorithm, inner_rtol, inner_atol, inner_max_iter,
                              **opts)
         return (wd.cpu().numpy(),) + tuple(out)
+
+
+    def adjoint(self, w, g, rtol=1e-10, atol=0.0, inner_max_iter=None, check_every=0, return_adjoint=False):
+        """Host ``w`` (B, *shapes) and ``g`` (one grid or (B, *shapes)) in; returns (moments (B, words), n_iter, n_apply,
+        rel_resid, resid_T, status, λ or None)."""
+        import torch
+        g = _grid_or_batch(g, self.B, self.shapes, "g")
+        wd = self._to_dev(self._host_in(w))
+        gd = self._to_dev(g)
+        mom = torch.empty((self.B, self.adjoint_words()), dtype=torch.float64, device=wd.device)
+        lam = torch.empty_like(wd) if return_adjoint else None
+        torch.cuda.current_stream(wd.device).synchronize()
+        out = self.adjoint_dev(wd.data_ptr(), gd.data_ptr(), 0 if g.ndim == len(self.shapes) else self.size,
+                               None if lam is None else lam.data_ptr(), mom.data_ptr(), rtol, atol, inner_max_iter,
+                               check_every)
+        return (mom.cpu().numpy(),) + tuple(out) + (None if lam is None else lam.cpu().numpy(),)
+
+
+def _grid_or_batch(x, B, shapes, what):
+    x = _as_f64(x)
+    if x.shape != shapes and x.shape != (B,) + shapes:
+        raise ValueError(f"{what} has shape {x.shape}: expected {shapes} or {(B,) + shapes}")
+    return x
 
 
 def _kind_of(models):
@@ -267,3 +318,54 @@ def solve_batch(models, shapes, w0=None, tol=1e-7, max_iter=10**6, method="rouwe
         else:
             status[b] = _lib.SDFS_BATCH_CONVERGED if err[b] <= tol else _lib.SDFS_BATCH_MAX_ITER
     return BatchResult(w, n_iter, err, status, "loop", n_apply)
+
+
+BatchGradient = namedtuple("BatchGradient", ["grad", "names", "n_iter", "n_apply", "rel_resid", "resid_T", "status",
+                                             "plan", "lam"])
+BatchGradient.__doc__ = """grad: (B, P) with grad[b, k] = d<g_b, w*_b>/d names[k]; n_iter (BiCGSTAB iterations), n_apply
+(operator applications), rel_resid (|r|_2 / |g|_2 of the transposed solve), resid_T (max|T w* - w*|), status (0
+converged, 1 stopped above the tolerance, 2 non-finite): length B; plan: "batch" or "loop" (the counts are -1 and the
+residuals NaN there: the single-problem path does not report them); lam: (B, *shapes) or None."""
+
+
+def gradient_batch(models, shapes, w_star, g, rtol=1e-10, atol=0.0, persistence=True, inner_max_iter=None, check_every=0,
+                   method="rouwenhorst", device=0, return_adjoint=False):
+    """Gradients of φ_b = <g_b, w*_b> with respect to the parameters of every member of ``models`` at its fixed point
+    ``w_star[b]`` (normally ``solve_batch(...).w``): one transposed solve λ = (I - J(w*)ᵀ)⁻¹ g and a handful of adjoint
+    moments per member, one workgroup per member (csrc/batch_adjoint.hpp), then
+    ``sensitivity.adjoint_moments_to_gradient`` on the host.  ``g``: one grid for all or (B, *shapes); it is ∂L/∂w of the
+    caller's objective and is treated as constant.  ``persistence=True``: all 13 / 18 parameters, else the 9 / 12 that
+    leave the transition matrices alone.  Shapes beyond one CU run ``wc_ratio_gradient`` member by member
+    (``plan == "loop"``).  Returns a BatchGradient."""
+    from . import sensitivity as sens
+    if method != "rouwenhorst":
+        raise ValueError(f"parameter tangents are implemented for Rouwenhorst grids only, not {method!r}")
+    models, kind = _kind_of(models)
+    shapes = tuple(int(s) for s in shapes)
+    ndim = _KINDS[kind][1]
+    if len(shapes) != ndim:
+        raise ValueError(f"{kind} grids have {ndim} axes, got shapes {shapes}")
+    B = len(models)
+    w = _as_f64(w_star)
+    if w.shape != (B,) + shapes:
+        raise ValueError(f"w_star has shape {w.shape}, the batch is {(B,) + shapes}")
+    g = _grid_or_batch(g, B, shapes, "g")
+    _, supported, _, _, allp = sens._kind(models[0])
+    names = tuple(allp if persistence else supported)
+    grad = np.zeros((B, len(names)))
+    if batch_lds_bytes(kind, shapes) is not None:
+        op = BatchOperator.from_models(models, shapes, method, device)
+        try:
+            mom, n_iter, n_apply, rel, res_T, status, lam = op.adjoint(w, g, rtol, atol, inner_max_iter, check_every,
+                                                                       return_adjoint)
+        finally:
+            op.close()
+        for b, m in enumerate(models):
+            d = sens.adjoint_moments_to_gradient(m, shapes, mom[b], persistence, method)
+            grad[b] = [d[nm] for nm in names]
+        return BatchGradient(grad, names, n_iter, n_apply, rel, res_T, status, "batch", lam)
+    for b, m in enumerate(models):
+        d = sens.wc_ratio_gradient(m, shapes, w[b], g if g.ndim == ndim else g[b], rtol, atol, persistence)
+        grad[b] = [d[nm] for nm in names]
+    return BatchGradient(grad, names, np.full(B, -1, dtype=np.int64), np.full(B, -1, dtype=np.int64), np.full(B, np.nan),
+                         np.full(B, np.nan), np.zeros(B, dtype=np.int32), "loop", None)

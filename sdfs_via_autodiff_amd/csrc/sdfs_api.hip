@@ -36,6 +36,7 @@
 #include "sim_kernels.hpp"
 #include "batch_kernels.hpp"
 #include "batch_newton.hpp"
+#include "batch_adjoint.hpp"
 
 using namespace sdfs;
 
@@ -4269,6 +4270,13 @@ struct sdfs_batch {
   int ws_slots = 0;              // problems per group: the workspace holds this many
   double* ws = nullptr;          // [ws_slots][7][nwork]
   BatchNewtonState* nst = nullptr;   // [B]
+  // adjoint moments (batch_adjoint.hpp): the Newton workspace, its own state; a2 is uploaded at the first gradient call
+  batch_adjoint_fn afn = nullptr;
+  int adjoint_reg = 0;
+  int ax_lam = 0, ax_c = 0, na3 = 0;
+  std::vector<double> a2_host;   // [B][n_c]: a2 = exp((1/2) ((1 - gamma) sigma_c)^2), as fill_model folds it into Q_c
+  double* a2 = nullptr;          // [B][n_c]
+  BatchAdjointState* ast = nullptr;  // [B]
   std::string errmsg;
 };
 
@@ -4399,6 +4407,33 @@ int batch_newton_prepare(sdfs_batch* h) {
   return 0;
 }
 
+int batch_adjoint_words(const sdfs_batch* h) { return 3 + h->d.ndim + h->d.n[h->ax_lam] + h->d.n[h->ax_c] + h->na3; }
+
+// the Newton workspace (the same seven vectors), the state, the a2 table and the LDS attribute of the adjoint kernel, at
+// the first gradient call of the handle
+int batch_adjoint_prepare(sdfs_batch* h) {
+  if (h->ast) return 0;
+  if (!h->afn) return bfail(h, SDFS_ERR_UNSUPPORTED, "no adjoint kernel for %d points", h->d.N);
+  int rc = batch_newton_prepare(h);
+  if (rc) return rc;
+  {
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> allowed;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = allowed[{(const void*)h->afn, h->device}];
+    if (h->lds_bytes > have) {
+      BHIPCHK(h, hipFuncSetAttribute((const void*)h->afn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+      have = h->lds_bytes;
+    }
+  }
+  if (!h->a2) {
+    BHIPCHK(h, hipMalloc((void**)&h->a2, h->a2_host.size() * 8));
+    BHIPCHK(h, hipMemcpy(h->a2, h->a2_host.data(), h->a2_host.size() * 8, hipMemcpyHostToDevice));
+  }
+  BHIPCHK(h, hipMalloc((void**)&h->ast, (size_t)h->B * sizeof(BatchAdjointState)));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4425,6 +4460,8 @@ void sdfs_batch_destroy(sdfs_batch* h) {
   if (h->status_host) hipHostFree(h->status_host);
   if (h->ws) hipFree(h->ws);
   if (h->nst) hipFree(h->nst);
+  if (h->a2) hipFree(h->a2);
+  if (h->ast) hipFree(h->ast);
   if (h->own_stream) hipStreamDestroy(h->own_stream);
   delete h;
 }
@@ -4445,6 +4482,8 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
   if (rc) return bfail(nullptr, rc, "%s", why.c_str());
   // the tables of every problem, by the host code of sdfs_create (fill_model), packed into the kernel's layout
   std::vector<double> tab((size_t)B * d.tabwords, 0.0), scal((size_t)B * 4, 0.0);
+  const int ax_c = model == SDFS_MODEL_SSY ? 1 : 3, ax_lam = model == SDFS_MODEL_SSY ? 0 : 5;
+  std::vector<double> a2h((size_t)B * d.n[ax_c], 0.0);
   for (int64_t b = 0; b < B; ++b) {
     sdfs_handle hh;                        // host fields only: fill_model touches no device
     hh.knobs = read_knobs();
@@ -4466,6 +4505,10 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
     if ((long long)M.a3.size() + d.a3off > d.tabwords) return bfail(nullptr, SDFS_ERR_ARG, "a3 table of %zu entries", M.a3.size());
     std::copy(M.a3.begin(), M.a3.end(), t + d.a3off);
     scal[4 * b] = hh.beta; scal[4 * b + 1] = hh.theta; scal[4 * b + 2] = 1.0 / hh.theta;
+    for (int k = 0; k < d.n[ax_c]; ++k) {                // a2 as fill_model forms it
+      const double s = (1 - hh.sens.gamma) * hh.sens.sigc[k];
+      a2h[(size_t)b * d.n[ax_c] + k] = std::exp(0.5 * s * s);
+    }
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -4477,7 +4520,15 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
   {
     int nt = 0, k = 0;
     h->nfn = batch_newton_kernel_for(d.N, &nt, &k, &h->newton_reg);     // the threads and points of h->fn
+    h->afn = batch_adjoint_kernel_for(d.N, &nt, &k, &h->adjoint_reg);
   }
+  h->ax_lam = ax_lam; h->ax_c = ax_c;
+  {
+    int na3 = 1;
+    for (int a = 0; a < ndim; ++a) if (d.a3s[a] != 0) na3 *= d.n[a];
+    h->na3 = na3;
+  }
+  h->a2_host.swap(a2h);
   auto bail = [&](int rc_) { g_create_error = h->errmsg; sdfs_batch_destroy(h); return rc_; };
   auto hip = [&](hipError_t e, const char* what) { return e == hipSuccess ? 0 : bfail(h, SDFS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
   if ((rc = hip(hipSetDevice(device_id), "hipSetDevice"))) return bail(rc);
@@ -4617,6 +4668,61 @@ int sdfs_batch_newton_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_
   return 0;
 }
 
+int64_t sdfs_batch_adjoint_words(const sdfs_batch* h) {
+  if (!h) return SDFS_ERR_ARG;
+  return batch_adjoint_words(h);
+}
+
+int sdfs_batch_adjoint_dev(sdfs_batch* h, const sdfs_opts* opts, const double* w_dev, const double* g_dev, int64_t g_stride,
+                           double* lam_dev, double* moments_dev, int64_t* n_iter, int64_t* n_apply, double* rel_resid,
+                           double* resid_T, int32_t* status) {
+  int rc = bcheck(h); if (rc) return rc;
+  if (!opts || !w_dev || !g_dev || !moments_dev || !n_iter || !n_apply || !rel_resid || !resid_T || !status)
+    return bfail(h, SDFS_ERR_ARG, "NULL argument");
+  if (g_stride != 0 && g_stride != h->d.N) return bfail(h, SDFS_ERR_ARG, "g_stride %lld: 0 (one g for all) or %d", (long long)g_stride, h->d.N);
+  if (!(opts->inner_rtol >= 0.0) || !(opts->inner_atol >= 0.0)) return bfail(h, SDFS_ERR_ARG, "inner_rtol and inner_atol must be >= 0");
+  if (opts->inner_max_iter < 0) return bfail(h, SDFS_ERR_ARG, "inner_max_iter must be >= 0");
+  if (opts->krylov_f32 != 0) return bfail(h, SDFS_ERR_ARG, "the batch adjoint solve keeps its Krylov vectors in fp64: krylov_f32 must be 0");
+  if ((rc = batch_adjoint_prepare(h))) return rc;
+  const int B = h->B;
+  hipStream_t st = h->stream;
+  BatchAdjointArgs A;
+  memset(&A, 0, sizeof A);
+  A.tab = h->tab; A.scal = h->scal; A.w = w_dev; A.g = g_dev; A.a2 = h->a2; A.lam = lam_dev; A.mom = moments_dev;
+  A.ws = h->ws; A.st = h->ast; A.status = h->status;
+  A.rtol2 = opts->inner_rtol * opts->inner_rtol; A.atol2 = opts->inner_atol * opts->inner_atol;
+  A.inner_max = opts->inner_max_iter > 0 ? (long long)opts->inner_max_iter : 10LL * h->d.N;
+  A.g_stride = g_stride;
+  A.budget = opts->check_every > 0 ? (int)opts->check_every : batch_newton_default_budget(h);
+  A.ax_lam = h->ax_lam; A.ax_c = h->ax_c; A.na3 = h->na3; A.words = batch_adjoint_words(h);
+  hipLaunchKernelGGL(batch_adjoint_init_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, h->status, h->ast);
+  BHIPCHK(h, hipGetLastError());
+  // group after group, as the Newton solve; every launch is bounded by A.budget applications per problem
+  for (int b0 = 0; b0 < B; b0 += h->ws_slots) {
+    const int G = std::min(h->ws_slots, B - b0);
+    A.b0 = b0;
+    bool open = true;
+    while (open) {
+      hipLaunchKernelGGL(h->afn, dim3(G), dim3(h->nt), h->lds_bytes, st, (const BatchDesc*)h->d_dev, A);
+      BHIPCHK(h, hipGetLastError());
+      BHIPCHK(h, hipMemcpyAsync(h->status_host + b0, h->status + b0, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, st));
+      BHIPCHK(h, hipStreamSynchronize(st));
+      open = false;
+      for (int b = b0; b < b0 + G && !open; ++b) open = h->status_host[b] == BATCH_OPEN;
+    }
+  }
+  std::vector<BatchAdjointState> as((size_t)B);
+  BHIPCHK(h, hipMemcpyAsync(as.data(), h->ast, (size_t)B * sizeof(BatchAdjointState), hipMemcpyDeviceToHost, st));
+  BHIPCHK(h, hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b) {
+    n_iter[b] = as[b].k; n_apply[b] = as[b].napply; status[b] = h->status_host[b];
+    resid_T[b] = as[b].resid_T;
+    rel_resid[b] = as[b].gg > 0.0 ? std::sqrt(as[b].tr / as[b].gg) : (as[b].gg == 0.0 ? 0.0 : as[b].gg);
+    if (status[b] == BATCH_NONFINITE) rel_resid[b] = std::numeric_limits<double>::quiet_NaN();
+  }
+  return 0;
+}
+
 int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap) {
   if (!h || !buf || cap < 1) return SDFS_ERR_ARG;
   std::string s;
@@ -4636,6 +4742,12 @@ int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap) {
     snprintf(line, sizeof line, "newton: w, r, rhat, p, q, x, c_in, c_out %s; workspace 7 x %d doubles per problem, %d problems per group%s; default budget %d applications per launch\n",
              h->newton_reg ? "in registers (the workspace holds them between launches only)" : "in global memory (w in the caller's buffer, seven in the workspace)",
              h->d.nwork, slots, slots < h->B ? " (the batch runs group after group)" : "", batch_newton_default_budget(h));
+    s += line;
+  }
+  if (h->afn) {
+    snprintf(line, sizeof line, "adjoint: lambda with r, rhat, p, q, c_in, c_out and w %s; %d moments per problem (s0 s1 s2 | R[%d] | M1[%d] | M2[%d] | M3[%d]); default budget %d applications per launch\n",
+             h->adjoint_reg ? "in registers (the Newton workspace holds them between launches only)" : "in global memory (w in the caller's buffer, seven in the Newton workspace)",
+             batch_adjoint_words(h), h->d.ndim, h->d.n[h->ax_lam], h->d.n[h->ax_c], h->na3, batch_newton_default_budget(h));
     s += line;
   }
   snprintf(buf, (size_t)cap, "%s", s.c_str());

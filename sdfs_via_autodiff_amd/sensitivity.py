@@ -393,3 +393,58 @@ def wc_ratio_gradient(model, shapes, w_star, g, rtol=1e-10, atol=0.0, persistenc
         op.param_tangent_dev(w.data_ptr(), dp, da, rhs.data_ptr(), tw.data_ptr(), dgen=dg)
         out[nm] = float(torch.dot(lv, rhs.view(-1)))
     return out
+
+
+# -- gradients from adjoint moments (the batch path: csrc/batch_adjoint.hpp) -------------------------------------------
+# (ip_beta, ip_gamma, ip_psi, ip_mu_c), (ia_hlam, ia_sigc, ia_z), (axis of h_lam, axis of h_c): the places `sens_tables`
+# of csrc/sdfs_api.hip reads
+_MOMENT_PLACES = {"ssy": ((0, 1, 2, 3), (0, 8, 6), (0, 1)), "gcy": ((0, 2, 1, 5), (13, 9, 0), (5, 3))}
+
+
+def adjoint_moments_to_gradient(model, shapes, moments, persistence=True, method="rouwenhorst"):
+    """{name: d<g, w*>/dp_name} of one model from its adjoint moment block (``BatchOperator.adjoint``; layout
+    s0 s1 s2 | R[ndim] | M1[n_λ] | M2[n_c] | M3[a3 table]).  Pure numpy: the directions are those of
+    ``wc_ratio_gradient`` and the log-tangents restate ``sens_tables`` of the library,
+
+        dθ = -dγ / (1 - 1/ψ) - dψ θ / (ψ (ψ - 1)),   d ln a1 = dθ h_λ + θ dh_λ,
+        d ln a2 = (1 - γ) σ_c ((1 - γ) dσ_c - dγ σ_c),   d ln a3 = (1 - γ) (dμ_c + dz) - dγ (μ_c + z),
+
+    so that  dφ/dp = dβ/β s0 - dθ/θ s1 + (<M2, d ln a2> + <M3, d ln a3>)/θ + (dθ s2 + <M1, d ln a1>)/θ
+    - [p is the persistence ρ_k of axis k] R[k] / (2 ρ_k θ).  The 9 / 12 supported parameters, or all 13 / 18 with
+    ``persistence=True``.  ValueError for a Tauchen grid."""
+    if method != "rouwenhorst":
+        raise ValueError(f"parameter tangents are implemented for Rouwenhorst grids only, not {method!r}")
+    kind, supported, disc, _, allp = _kind(model)
+    shapes = tuple(int(s) for s in shapes)
+    (ib, ig, ips, imu), (ia_hl, ia_sc, ia_z), (ax_l, ax_c) = _MOMENT_PLACES[kind]
+    ndim = len(shapes)
+    arr = disc(model, shapes)
+    n_l, n_c, na3 = shapes[ax_l], shapes[ax_c], int(np.asarray(arr[ia_z]).size)
+    mom = np.asarray(moments, dtype=np.float64).ravel()
+    if mom.size != 3 + ndim + n_l + n_c + na3:
+        raise ValueError(f"moments has {mom.size} entries, the block of {kind} {shapes} has {3 + ndim + n_l + n_c + na3}")
+    s0, s1, s2 = mom[:3]
+    R = mom[3:3 + ndim]
+    M1 = mom[3 + ndim:3 + ndim + n_l]
+    M2 = mom[3 + ndim + n_l:3 + ndim + n_l + n_c]
+    M3 = mom[3 + ndim + n_l + n_c:]
+    params = np.asarray(model.params, dtype=np.float64)
+    β, γ, ψ, μ_c = params[ib], params[ig], params[ips], params[imu]
+    θ = (1.0 - γ) / (1.0 - 1.0 / ψ)
+    h_λ, σ_c, z = (np.asarray(arr[i], dtype=np.float64).ravel() for i in (ia_hl, ia_sc, ia_z))
+    names = allp if persistence else supported
+    axis_of = _SSY_AXIS if kind == "ssy" else _GCY_AXIS
+    out = {}
+    for nm, (dp, da, dgen) in zip(names, _directions(model, shapes, names, arr, persistence)):
+        def d(i):
+            return 0.0 if da[i] is None else np.asarray(da[i], dtype=np.float64).ravel()
+        dγ, dψ, dμ = dp[ig], dp[ips], dp[imu]
+        dθ = -dγ / (1.0 - 1.0 / ψ) - dψ * θ / (ψ * (ψ - 1.0))
+        dla1 = dθ * h_λ + θ * d(ia_hl)
+        dla2 = (1.0 - γ) * σ_c * ((1.0 - γ) * d(ia_sc) - dγ * σ_c)
+        dla3 = (1.0 - γ) * (dμ + d(ia_z)) - dγ * (μ_c + z)
+        val = dp[ib] / β * s0 - dθ / θ * s1 + (M2 @ dla2 + M3 @ dla3) / θ + (dθ * s2 + M1 @ dla1) / θ
+        if dgen is not None:
+            val -= R[axis_of[nm]] / (2.0 * params[allp.index(nm)] * θ)
+        out[nm] = float(val)
+    return out
