@@ -500,6 +500,36 @@ int sdfs_batch_adjoint_dev(sdfs_batch* h, const sdfs_opts* opts, const double* w
                            double* lam_dev, double* moments_dev, int64_t* n_iter, int64_t* n_apply, double* rel_resid,
                            double* resid_T, int32_t* status);
 
+/* Asset prices for all B problems at w_dev (B x N, normally the batch's w*), one workgroup per problem
+ * (csrc/batch_price.hpp).  With K(p, kl, kc) the tilted operator of sdfs_set_tilt_dev, per problem b:
+ *   E_M = K(1, theta, -gamma) 1, log_rf = -ln E_M;  E_M2 = K(2, 2 theta, -2 gamma) 1, hj = sqrt(max(E_M2 / E_M^2 - 1, 0));
+ *   v = (I - K)^(-1) K 1 with K = K(1, theta, kappa[b] - gamma) by BiCGSTAB (the price-dividend ratio of the claim on
+ *   G_c^kappa);  ER = K(0, 0, kappa[b])(1 + v) / v, lp = ln ER + ln E_M;
+ *   P_n = K(1, theta, kappa_ts[b] - gamma) P_(n-1), P_0 = 1, n = 1 .. n_max.
+ * kappa (host, B entries) may be NULL: no claim.  kappa_ts (host, B entries) is read when n_max > 0.  weights (host,
+ * B x sum n_a): the per-axis weight vectors g_a of every problem, axis-major; the weight of a point is prod_a g_a[i_a].
+ * EM_dev, EM2_dev, pd_dev, ER_dev (B x N each) may be NULL.  moments_dev: B x SDFS_BATCH_PRICE_WORDS,
+ *   0 sum g | 1 <g,log_rf> 2 <g,log_rf^2> | 3 <g,hj> | 4 <g,ln v> 5 <g,(ln v)^2> | 6 <g,ln ER> | 7 <g,lp> 8 <g,lp^2> |
+ *   9 min v 10 max v | 11 number of points with v <= 0;  words 4-11 are NaN without a claim.
+ * horizons_dev: B x n_max x 4 (<g,P_n>, <g,-ln P_n> / n, min and max of P_n / P_(n-1)); may be NULL when n_max == 0.  A
+ * horizon whose P_n has a non-positive or non-finite point ends that problem's loop: n_horizons[b] rows were written and
+ * the later ones are NaN.  Read from opts: inner_rtol, inner_atol, inner_max_iter (0 -> 10 N), check_every (applications
+ * per launch, 0 = the library's choice); krylov_f32 != 0 is SDFS_ERR_ARG, and so are non-finite kappa, kappa_ts or
+ * weights and n_max < 0 or > 2^24, before any device work.  Host outputs of length B: n_iter (BiCGSTAB iterations),
+ * n_apply (operator applications), n_horizons, rel_resid (the true |K1 - v + K v|_2 / |K1|_2; NaN without a claim),
+ * resid_T (max|T w - w|) and status: SDFS_BATCH_CONVERGED done, SDFS_BATCH_MAX_ITER the claim solve stopped above its
+ * tolerance (the words are those of v where it stopped), SDFS_BATCH_NONFINITE (the problem's outputs are NaN),
+ * SDFS_BATCH_NO_PRICE the solve converged but v is not strictly positive: r(K) >= 1, words 4-8 are NaN, 9-11 kept, E_M
+ * and the horizons delivered.  The call uses the Newton workspace (allocated on first use) and leaves the handle's solve,
+ * Newton and adjoint state alone.  A problem's results depend on its own inputs only: not on B, its position in the batch
+ * or check_every. */
+enum { SDFS_BATCH_NO_PRICE = 3 };
+#define SDFS_BATCH_PRICE_WORDS 12
+int sdfs_batch_price_dev(sdfs_batch* h, const sdfs_opts* opts, const double* w_dev, const double* kappa, const double* kappa_ts,
+                         const double* weights, int64_t n_max, double* EM_dev, double* EM2_dev, double* pd_dev, double* ER_dev,
+                         double* moments_dev, double* horizons_dev, int64_t* n_iter, int64_t* n_apply, int64_t* n_horizons,
+                         double* rel_resid, double* resid_T, int32_t* status);
+
 /* Human-readable description of the batch plan. */
 int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap);
 

@@ -30,7 +30,8 @@ from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_rat
                           adjoint_moments_to_gradient)
 from .pricing import stationary_weights, sdf_moments, term_structure, claim_prices
 from .simulation import simulate
-from .batch import BatchOperator, BatchResult, solve_batch, batch_lds_bytes, BatchGradient, gradient_batch
+from .batch import (BatchOperator, BatchResult, solve_batch, batch_lds_bytes, BatchGradient, gradient_batch, BatchPrices,
+                    price_batch, price_words_to_stats)
 from ._lib import SdfsError, LIB_PATH
 
 __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize_gcy",
@@ -47,5 +48,5 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "rouwenhorst_generator", "discretize_ssy_persistence_tangent", "discretize_gcy_persistence_tangent",
            "SSY_PERSISTENCE", "GCY_PERSISTENCE", "adjoint_moments_to_gradient",
            "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate",
-           "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes", "BatchGradient", "gradient_batch",
+           "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes", "BatchGradient", "gradient_batch", "BatchPrices", "price_batch", "price_words_to_stats",
            "SdfsError", "LIB_PATH"]

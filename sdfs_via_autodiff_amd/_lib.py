@@ -17,6 +17,8 @@ SDFS_ERR_UNSUPPORTED = -3
 SDFS_ERR_NUMERIC = -4
 SDFS_MAX_KERNELS = 16
 SDFS_BATCH_CONVERGED, SDFS_BATCH_MAX_ITER, SDFS_BATCH_NONFINITE = 0, 1, 2
+SDFS_BATCH_NO_PRICE = 3
+SDFS_BATCH_PRICE_WORDS = 12
 
 
 class SdfsError(RuntimeError):
@@ -125,6 +127,8 @@ SYMBOLS = {
     "sdfs_batch_adjoint_words": (C.c_int64, [_P]),
     "sdfs_batch_adjoint_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _P, C.c_int64, _P, _P, _I64, _I64, _D, _D,
                                          C.POINTER(C.c_int32)]),
+    "sdfs_batch_price_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _D, _D, _D, C.c_int64, _P, _P, _P, _P, _P, _P, _I64, _I64,
+                                       _I64, _D, _D, C.POINTER(C.c_int32)]),
     "sdfs_batch_describe": (C.c_int, [_P, C.c_char_p, C.c_int64]),
 }
 

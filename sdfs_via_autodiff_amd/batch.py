@@ -240,6 +240,69 @@ class BatchOperator:
                                check_every)
         return (mom.cpu().numpy(),) + tuple(out) + (None if lam is None else lam.cpu().numpy(),)
 
+    def _stationary_weights(self):
+        """(B, Σ n_a): the stationary marginals of every member's chain, axis-major (as ``pricing.stationary_weights``)."""
+        from . import pricing
+        rows = []
+        for b in range(self.B):                            # (a batch handle's tensors are unconditional: one matrix per axis)
+            rows.append(np.concatenate([pricing._perron_left(self._arrays[qi][b].reshape(-1, n, n)[0])
+                                        for qi, n in zip(pricing._AXIS_Q[self.kind], self.shapes)]))
+        return np.ascontiguousarray(np.stack(rows))
+
+    def price_dev(self, w_ptr, kappa, kappa_ts, weights, n_max, EM_ptr, EM2_ptr, pd_ptr, ER_ptr, moments_ptr, horizons_ptr,
+                  rtol=1e-10, atol=0.0, inner_max_iter=None, check_every=0):
+        """sdfs_batch_price_dev: ``kappa`` (B,) or None, ``kappa_ts`` (B,) (read when n_max > 0), ``weights`` (B, Σ n_a) host
+        arrays; the grid pointers may be None.  Returns host arrays (n_iter, n_apply, n_horizons, rel_resid, resid_T, status)
+        of length B."""
+        o = _lib.default_opts()
+        o.inner_rtol, o.inner_atol, o.check_every = float(rtol), float(atol), int(check_every)
+        o.inner_max_iter = 0 if inner_max_iter is None else int(inner_max_iter)
+        dp = C.POINTER(C.c_double)
+        kap = None if kappa is None else np.ascontiguousarray(kappa, dtype=np.float64)
+        kts = None if kappa_ts is None else np.ascontiguousarray(kappa_ts, dtype=np.float64)
+        g = np.ascontiguousarray(weights, dtype=np.float64)
+        if (kap is not None and kap.shape != (self.B,)) or (kts is not None and kts.shape != (self.B,)):
+            raise ValueError(f"kappa and kappa_ts need {self.B} entries")
+        if g.shape != (self.B, int(sum(self.shapes))):
+            raise ValueError(f"weights has shape {g.shape}: expected {(self.B, int(sum(self.shapes)))}")
+        n_iter = np.zeros(self.B, dtype=np.int64)
+        n_apply = np.zeros(self.B, dtype=np.int64)
+        n_hor = np.zeros(self.B, dtype=np.int64)
+        rel = np.zeros(self.B, dtype=np.float64)
+        res_T = np.zeros(self.B, dtype=np.float64)
+        status = np.zeros(self.B, dtype=np.int32)
+        i64 = C.POINTER(C.c_int64)
+        self._check(lib.sdfs_batch_price_dev(self._h, C.byref(o), w_ptr, None if kap is None else kap.ctypes.data_as(dp),
+                                             None if kts is None else kts.ctypes.data_as(dp), g.ctypes.data_as(dp), int(n_max),
+                                             EM_ptr, EM2_ptr, pd_ptr, ER_ptr, moments_ptr, horizons_ptr,
+                                             n_iter.ctypes.data_as(i64), n_apply.ctypes.data_as(i64), n_hor.ctypes.data_as(i64),
+                                             rel.ctypes.data_as(dp), res_T.ctypes.data_as(dp),
+                                             status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return n_iter, n_apply, n_hor, rel, res_T, status
+
+    def price(self, w, kappa=None, n_max=0, kappa_ts=0.0, weights=None, rtol=1e-10, atol=0.0, inner_max_iter=None,
+              check_every=0, return_grids=False):
+        """Host ``w`` (B, *shapes) in.  ``kappa``: None (no claim), a scalar or B entries; ``kappa_ts`` likewise (read when
+        n_max > 0); ``weights``: None (every member's stationary marginals), (B, Σ n_a) or a list of B per-axis lists of
+        vectors.  Returns (moments (B, 12), horizons (B, n_max, 4), grids dict or None, n_iter, n_apply, n_horizons,
+        rel_resid, resid_T, status)."""
+        import torch
+        n_max = _check_n_max(n_max)
+        rtol, atol = _check_rtol(rtol, atol)
+        kap = _per_member(kappa, self.B, "kappa", optional=True)
+        kts = _per_member(kappa_ts, self.B, "kappa_ts")
+        g = self._stationary_weights() if weights is None else _axis_weights_array(weights, self.B, self.shapes)
+        wd = self._to_dev(self._host_in(w))
+        dev = wd.device
+        mom = torch.empty((self.B, _lib.SDFS_BATCH_PRICE_WORDS), dtype=torch.float64, device=dev)
+        hz = torch.empty((self.B, n_max, 4), dtype=torch.float64, device=dev) if n_max > 0 else None
+        grids = [torch.empty_like(wd) for _ in range(4)] if return_grids else [None] * 4
+        torch.cuda.current_stream(dev).synchronize()
+        out = self.price_dev(wd.data_ptr(), kap, kts, g, n_max, *[None if t is None else t.data_ptr() for t in grids],
+                             mom.data_ptr(), None if hz is None else hz.data_ptr(), rtol, atol, inner_max_iter, check_every)
+        gd = dict(zip(("E_M", "E_M2", "pd", "expected_return"), (t.cpu().numpy() for t in grids))) if return_grids else None
+        return (mom.cpu().numpy(), hz.cpu().numpy() if hz is not None else np.zeros((self.B, 0, 4)), gd) + tuple(out)
+
 
 def _grid_or_batch(x, B, shapes, what):
     x = _as_f64(x)
@@ -369,3 +432,201 @@ def gradient_batch(models, shapes, w_star, g, rtol=1e-10, atol=0.0, persistence=
         grad[b] = [d[nm] for nm in names]
     return BatchGradient(grad, names, np.full(B, -1, dtype=np.int64), np.full(B, -1, dtype=np.int64), np.full(B, np.nan),
                          np.full(B, np.nan), np.zeros(B, dtype=np.int32), "loop", None)
+
+
+BatchPrices = namedtuple("BatchPrices", ["stats", "moments", "price", "yield_", "bracket", "n_horizons", "grids", "n_iter",
+                                         "n_apply", "rel_resid", "resid_T", "status", "plan"])
+BatchPrices.__doc__ = """stats: dict of length-B arrays (``price_words_to_stats``); moments: (B, 12), the words of
+sdfs_batch_price_dev; price ⟨g, P_n⟩, yield_ ⟨g, −ln P_n⟩ / n: (B, n_max); bracket: (B, n_max, 2), min and max of
+P_n / P_{n−1}; n_horizons: rows written per member (later rows are NaN); grids: {"E_M", "E_M2", "pd", "expected_return"}
+of (B, *shapes) or None; n_iter (BiCGSTAB iterations of the claim solve), n_apply (operator applications), rel_resid (the
+true ‖K1 − v + K v‖₂ / ‖K1‖₂), resid_T (max|T w* − w*|): length B; status: 0 done, 1 the claim solve stopped above its
+tolerance, 2 non-finite, 3 no finite price (r(K) ≥ 1); plan: "batch" or "loop" (the counts are −1 and the residuals NaN
+there: the single-problem path does not report them)."""
+
+PRICE_STATS = ("log_rf_mean", "log_rf_std", "max_sharpe_mean", "log_pd_mean", "log_pd_std", "log_expected_return_mean",
+               "log_premium_mean", "log_premium_std", "pd_min", "pd_max")
+
+
+def price_words_to_stats(moments):
+    """The statistics of the (B, 12) moment words of sdfs_batch_price_dev (host only): every sum divided by Σg (word 0),
+    std = √max(m2 − m1², 0)."""
+    m = np.asarray(moments, dtype=np.float64)
+    if m.ndim != 2 or m.shape[1] != _lib.SDFS_BATCH_PRICE_WORDS:
+        raise ValueError(f"moments must be (B, {_lib.SDFS_BATCH_PRICE_WORDS}), got {m.shape}")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = m[:, 1:9] / m[:, :1]
+
+        def std(m1, m2):
+            return np.sqrt(np.maximum(m2 - m1 * m1, 0.0))
+        return {"log_rf_mean": mean[:, 0], "log_rf_std": std(mean[:, 0], mean[:, 1]), "max_sharpe_mean": mean[:, 2],
+                "log_pd_mean": mean[:, 3], "log_pd_std": std(mean[:, 3], mean[:, 4]), "log_expected_return_mean": mean[:, 5],
+                "log_premium_mean": mean[:, 6], "log_premium_std": std(mean[:, 6], mean[:, 7]),
+                "pd_min": m[:, 9].copy(), "pd_max": m[:, 10].copy()}
+
+
+def _per_member(x, B, what, optional=False):
+    """A scalar or length-B sequence of finite reals as a length-B array (None stays None where ``optional``)."""
+    if x is None:
+        if optional:
+            return None
+        raise ValueError(f"{what} must be a real number or {B} of them, got None")
+    try:
+        a = np.asarray(x, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a real number or {B} of them, got {x!r}") from None
+    if a.ndim == 0:
+        a = np.full(B, float(a))
+    if a.shape != (B,):
+        raise ValueError(f"{what} has shape {a.shape}: a scalar or {B} entries")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{what} must be finite, got {x!r}")
+    return np.ascontiguousarray(a)
+
+
+def _check_n_max(n_max):
+    if isinstance(n_max, bool) or not isinstance(n_max, (int, np.integer)) or not 0 <= int(n_max) <= 1 << 24:
+        raise ValueError(f"n_max must be an integer in 0 ... 2^24, got {n_max!r}")
+    return int(n_max)
+
+
+def _check_rtol(rtol, atol):
+    rtol, atol = float(rtol), float(atol)
+    if not (rtol >= 0.0 and np.isfinite(rtol)) or not (atol >= 0.0 and np.isfinite(atol)):
+        raise ValueError(f"rtol and atol must be finite and >= 0, got {rtol!r}, {atol!r}")
+    return rtol, atol
+
+
+def _axis_weights_array(weights, B, shapes):
+    """(B, Σ n_a) from a (B, Σ n_a) array or a list of B per-axis lists of vectors."""
+    total = int(sum(shapes))
+    if isinstance(weights, np.ndarray) and weights.ndim == 2:
+        g = _as_f64(weights)
+    else:
+        if len(weights) != B:
+            raise ValueError(f"weights needs one per-axis list per member ({B}), got {len(weights)}")
+        rows = []
+        for b, per_axis in enumerate(weights):
+            if len(per_axis) != len(shapes):
+                raise ValueError(f"weights[{b}] needs one vector per axis ({len(shapes)}), got {len(per_axis)}")
+            vs = [np.asarray(v, dtype=np.float64).ravel() for v in per_axis]
+            for a, (v, n) in enumerate(zip(vs, shapes)):
+                if v.size != n:
+                    raise ValueError(f"weights[{b}][{a}] has {v.size} entries, axis {a} has {n} states")
+            rows.append(np.concatenate(vs))
+        g = np.ascontiguousarray(np.stack(rows))
+    if g.shape != (B, total):
+        raise ValueError(f"weights has shape {g.shape}: expected {(B, total)}")
+    if not np.all(np.isfinite(g)):
+        raise ValueError("weights are not finite")
+    return g
+
+
+def _member_weights(models, kind, shapes, weights, method):
+    """The per-axis weight vectors of every member as (B, Σ n_a): None -> the stationary marginals of each member's
+    chain; one per-axis list (entries as ``pricing._weights`` takes them: a state index or a vector) for all; or a list
+    of B such lists."""
+    from . import pricing
+    B = len(models)
+    disc = discretize_ssy if kind == "ssy" else discretize_gcy
+    if weights is None:
+        per = [pricing.stationary_weights(m, shapes, disc(m, shapes, method)) for m in models]
+    else:
+        weights = list(weights)
+        nested = len(weights) == B and all(isinstance(x, (list, tuple)) for x in weights)
+        if not nested:
+            if len(weights) != len(shapes):
+                raise ValueError(f"weights needs one entry per axis ({len(shapes)}) or one per-axis list per member ({B}), "
+                                 f"got {len(weights)} entries")
+            weights = [weights] * B
+        per = [pricing._weights(kind, shapes, g, m) for g, m in zip(weights, models)]
+    return np.ascontiguousarray(np.stack([np.concatenate(p) for p in per])), per
+
+
+def price_batch(models, shapes, w_star, kappa=None, n_max=0, kappa_ts=0.0, weights=None, rtol=1e-10, atol=0.0,
+                inner_max_iter=None, check_every=0, method="rouwenhorst", device=0, return_grids=False):
+    """Asset prices of every member of ``models`` at its fixed point ``w_star[b]`` (normally ``solve_batch(...).w``), one
+    workgroup per member (csrc/batch_price.hpp): the risk-free rate and the maximal Sharpe ratio from E[M] and E[M²], the
+    price–dividend ratio, expected return and premium of the perpetual claim on G_c^κ (``kappa``: None for no claim, a
+    scalar or B entries), and prices and yields of zero-coupon claims on G_c^κ_ts for horizons 1 … ``n_max``
+    (``kappa_ts``: a scalar or B entries), each averaged with product-form weights (``weights``: None for every member's
+    stationary marginals, one per-axis list for all, or a list of B such lists; an entry is a state index or a vector).
+    Shapes beyond one CU run ``sdf_moments``, ``claim_prices`` and ``term_structure`` member by member
+    (``plan == "loop"``).  Returns a BatchPrices."""
+    from . import pricing
+    models, kind = _kind_of(models)
+    shapes = tuple(int(s) for s in shapes)
+    ndim = _KINDS[kind][1]
+    if len(shapes) != ndim:
+        raise ValueError(f"{kind} grids have {ndim} axes, got shapes {shapes}")
+    B = len(models)
+    w = _as_f64(w_star)
+    if w.shape != (B,) + shapes:
+        raise ValueError(f"w_star has shape {w.shape}, the batch is {(B,) + shapes}")
+    n_max = _check_n_max(n_max)
+    rtol, atol = _check_rtol(rtol, atol)
+    kap = _per_member(kappa, B, "kappa", optional=True)
+    kts = _per_member(kappa_ts, B, "kappa_ts")
+    lds = batch_lds_bytes(kind, shapes)
+    g, per_axis = _member_weights(models, kind, shapes, weights, method)
+    if lds is not None:
+        op = BatchOperator.from_models(models, shapes, method, device)
+        try:
+            mom, hz, grids, n_iter, n_apply, n_hor, rel, res_T, status = op.price(
+                w, kap, n_max, kts, g, rtol, atol, inner_max_iter, check_every, return_grids)
+        finally:
+            op.close()
+        return BatchPrices(price_words_to_stats(mom), mom, hz[:, :, 0].copy(), hz[:, :, 1].copy(), hz[:, :, 2:4].copy(), n_hor,
+                           grids, n_iter, n_apply, rel, res_T, status, "batch")
+    if method != "rouwenhorst":
+        raise ValueError(f"shapes beyond one CU are priced by the single-problem functions, which discretise by Rouwenhorst's "
+                         f"method, not {method!r}")
+    if rtol <= 0.0:
+        raise ValueError("the single-problem claim solve needs rtol > 0")
+    # member by member through the single-problem functions, reduced on the host
+    mom = np.full((B, _lib.SDFS_BATCH_PRICE_WORDS), np.nan)
+    hz = np.full((B, n_max, 4), np.nan)
+    n_hor = np.zeros(B, dtype=np.int64)
+    status = np.zeros(B, dtype=np.int32)
+    names = ("E_M", "E_M2", "pd", "expected_return")
+    grids = {k: np.full((B,) + shapes, np.nan) for k in names} if return_grids else None
+    for b, m in enumerate(models):
+        gw = per_axis[b][0]
+        for v in per_axis[b][1:]:
+            gw = np.multiply.outer(gw, v)
+        sm = pricing.sdf_moments(m, shapes, w[b])
+        E_M = sm["E_M"]
+        if not np.all(np.isfinite(E_M)) or not np.all(E_M > 0):
+            status[b] = _lib.SDFS_BATCH_NONFINITE
+            continue
+        lr = sm["log_rf"]
+        mom[b, 0:4] = gw.sum(), np.sum(gw * lr), np.sum(gw * lr * lr), np.sum(gw * sm["max_sharpe"])
+        if grids is not None:
+            grids["E_M"][b] = E_M
+            grids["E_M2"][b] = (sm["max_sharpe"] ** 2 + 1.0) * E_M ** 2
+        if kap is not None:
+            try:
+                cp = pricing.claim_prices(m, shapes, w[b], kap[b], rtol)
+            except ValueError as e:
+                if "no finite price" not in str(e):
+                    raise
+                status[b] = _lib.SDFS_BATCH_NO_PRICE
+            else:
+                v, ER, lp = cp["pd"], cp["expected_return"], cp["log_premium"]
+                lv, le = np.log(v), np.log(ER)
+                mom[b, 4:12] = (np.sum(gw * lv), np.sum(gw * lv * lv), np.sum(gw * le), np.sum(gw * lp), np.sum(gw * lp * lp),
+                                v.min(), v.max(), 0.0)
+                if grids is not None:
+                    grids["pd"][b], grids["expected_return"][b] = v, ER
+        if n_max > 0:
+            try:
+                ts = pricing.term_structure(m, shapes, w[b], n_max, kts[b], per_axis[b])
+            except ValueError as e:
+                if "left the positive numbers" not in str(e):
+                    raise
+            else:
+                hz[b, :, 0], hz[b, :, 1], hz[b, :, 2:4] = ts["price"], ts["yield"], ts["bracket"]
+                n_hor[b] = n_max
+    return BatchPrices(price_words_to_stats(mom), mom, hz[:, :, 0].copy(), hz[:, :, 1].copy(), hz[:, :, 2:4].copy(), n_hor,
+                       grids, np.full(B, -1, dtype=np.int64), np.full(B, -1, dtype=np.int64), np.full(B, np.nan),
+                       np.full(B, np.nan), status, "loop")

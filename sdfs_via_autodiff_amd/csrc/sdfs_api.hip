@@ -37,6 +37,7 @@
 #include "batch_kernels.hpp"
 #include "batch_newton.hpp"
 #include "batch_adjoint.hpp"
+#include "batch_price.hpp"
 
 using namespace sdfs;
 
@@ -4277,6 +4278,14 @@ struct sdfs_batch {
   std::vector<double> a2_host;   // [B][n_c]: a2 = exp((1/2) ((1 - gamma) sigma_c)^2), as fill_model folds it into Q_c
   double* a2 = nullptr;          // [B][n_c]
   BatchAdjointState* ast = nullptr;  // [B]
+  // pricing (batch_price.hpp): the Newton workspace, its own state; host copies of what the tilt tables are built from
+  batch_price_fn pfn = nullptr;
+  int price_reg = 0;
+  std::vector<double> hlam_host;  // [B][n_lam]: h_lambda
+  std::vector<double> sigc_host;  // [B][n_c]: sigma_c
+  std::vector<double> muz_host;   // [B][na3]: mu_c + z in the a3 layout
+  std::vector<double> gam_host, theta_host;   // [B]
+  BatchPriceState* pst = nullptr;    // [B]
   std::string errmsg;
 };
 
@@ -4434,6 +4443,32 @@ int batch_adjoint_prepare(sdfs_batch* h) {
   return 0;
 }
 
+// the Newton workspace (the same seven vectors), the state and the LDS attribute of the pricing kernel, at the first
+// pricing call of the handle
+int batch_price_prepare(sdfs_batch* h) {
+  if (h->pst) return 0;
+  if (!h->pfn) return bfail(h, SDFS_ERR_UNSUPPORTED, "no pricing kernel for %d points", h->d.N);
+  int rc = batch_newton_prepare(h);
+  if (rc) return rc;
+  {
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> allowed;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = allowed[{(const void*)h->pfn, h->device}];
+    if (h->lds_bytes > have) {
+      BHIPCHK(h, hipFuncSetAttribute((const void*)h->pfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+      have = h->lds_bytes;
+    }
+  }
+  BHIPCHK(h, hipMalloc((void**)&h->pst, (size_t)h->B * sizeof(BatchPriceState)));
+  return 0;
+}
+
+struct BatchDevBuf {                 // device memory of one call
+  double* p = nullptr;
+  ~BatchDevBuf() { if (p) hipFree(p); }
+};
+
 }  // namespace
 
 extern "C" {
@@ -4462,6 +4497,7 @@ void sdfs_batch_destroy(sdfs_batch* h) {
   if (h->nst) hipFree(h->nst);
   if (h->a2) hipFree(h->a2);
   if (h->ast) hipFree(h->ast);
+  if (h->pst) hipFree(h->pst);
   if (h->own_stream) hipStreamDestroy(h->own_stream);
   delete h;
 }
@@ -4484,6 +4520,10 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
   std::vector<double> tab((size_t)B * d.tabwords, 0.0), scal((size_t)B * 4, 0.0);
   const int ax_c = model == SDFS_MODEL_SSY ? 1 : 3, ax_lam = model == SDFS_MODEL_SSY ? 0 : 5;
   std::vector<double> a2h((size_t)B * d.n[ax_c], 0.0);
+  int na3_tab = 1;
+  for (int a = 0; a < ndim; ++a) if (d.a3s[a] != 0) na3_tab *= d.n[a];
+  std::vector<double> hlh((size_t)B * d.n[ax_lam], 0.0), sch((size_t)B * d.n[ax_c], 0.0), muzh((size_t)B * na3_tab, 0.0);
+  std::vector<double> gamh((size_t)B, 0.0), thh((size_t)B, 0.0);
   for (int64_t b = 0; b < B; ++b) {
     sdfs_handle hh;                        // host fields only: fill_model touches no device
     hh.knobs = read_knobs();
@@ -4509,6 +4549,14 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
       const double s = (1 - hh.sens.gamma) * hh.sens.sigc[k];
       a2h[(size_t)b * d.n[ax_c] + k] = std::exp(0.5 * s * s);
     }
+    // what the pricing tilts are built from (sdfs_set_tilt_dev reads the same fields of a single-problem handle)
+    if ((int)hh.sens.hlam.size() != d.n[ax_lam] || (int)hh.sens.sigc.size() != d.n[ax_c] || (int)hh.sens.z.size() != na3_tab)
+      return bfail(nullptr, SDFS_ERR_ARG, "problem %lld: state arrays of %zu, %zu and %zu entries", (long long)b, hh.sens.hlam.size(),
+                   hh.sens.sigc.size(), hh.sens.z.size());
+    std::copy(hh.sens.hlam.begin(), hh.sens.hlam.end(), hlh.begin() + (size_t)b * d.n[ax_lam]);
+    std::copy(hh.sens.sigc.begin(), hh.sens.sigc.end(), sch.begin() + (size_t)b * d.n[ax_c]);
+    for (int i = 0; i < na3_tab; ++i) muzh[(size_t)b * na3_tab + i] = hh.sens.mu_c + hh.sens.z[i];
+    gamh[b] = hh.sens.gamma; thh[b] = hh.theta;
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -4521,6 +4569,7 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
     int nt = 0, k = 0;
     h->nfn = batch_newton_kernel_for(d.N, &nt, &k, &h->newton_reg);     // the threads and points of h->fn
     h->afn = batch_adjoint_kernel_for(d.N, &nt, &k, &h->adjoint_reg);
+    h->pfn = batch_price_kernel_for(d.N, &nt, &k, &h->price_reg);
   }
   h->ax_lam = ax_lam; h->ax_c = ax_c;
   {
@@ -4529,6 +4578,7 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
     h->na3 = na3;
   }
   h->a2_host.swap(a2h);
+  h->hlam_host.swap(hlh); h->sigc_host.swap(sch); h->muz_host.swap(muzh); h->gam_host.swap(gamh); h->theta_host.swap(thh);
   auto bail = [&](int rc_) { g_create_error = h->errmsg; sdfs_batch_destroy(h); return rc_; };
   auto hip = [&](hipError_t e, const char* what) { return e == hipSuccess ? 0 : bfail(h, SDFS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
   if ((rc = hip(hipSetDevice(device_id), "hipSetDevice"))) return bail(rc);
@@ -4723,6 +4773,103 @@ int sdfs_batch_adjoint_dev(sdfs_batch* h, const sdfs_opts* opts, const double* w
   return 0;
 }
 
+int sdfs_batch_price_dev(sdfs_batch* h, const sdfs_opts* opts, const double* w_dev, const double* kappa, const double* kappa_ts,
+                         const double* weights, int64_t n_max, double* EM_dev, double* EM2_dev, double* pd_dev, double* ER_dev,
+                         double* moments_dev, double* horizons_dev, int64_t* n_iter, int64_t* n_apply, int64_t* n_horizons,
+                         double* rel_resid, double* resid_T, int32_t* status) {
+  int rc = bcheck(h); if (rc) return rc;
+  if (!opts || !w_dev || !weights || !moments_dev || !n_iter || !n_apply || !n_horizons || !rel_resid || !resid_T || !status)
+    return bfail(h, SDFS_ERR_ARG, "NULL argument");
+  if (n_max < 0 || n_max > (1LL << 24)) return bfail(h, SDFS_ERR_ARG, "n_max = %lld: 0 .. 2^24", (long long)n_max);
+  if (n_max > 0 && (!kappa_ts || !horizons_dev)) return bfail(h, SDFS_ERR_ARG, "n_max > 0 needs kappa_ts and horizons_dev");
+  if (!(opts->inner_rtol >= 0.0) || !(opts->inner_atol >= 0.0)) return bfail(h, SDFS_ERR_ARG, "inner_rtol and inner_atol must be >= 0");
+  if (opts->inner_max_iter < 0) return bfail(h, SDFS_ERR_ARG, "inner_max_iter must be >= 0");
+  if (opts->krylov_f32 != 0) return bfail(h, SDFS_ERR_ARG, "the batch pricing solve keeps its Krylov vectors in fp64: krylov_f32 must be 0");
+  const int B = h->B, nl = h->d.n[h->ax_lam], nc = h->d.n[h->ax_c], na3 = h->na3;
+  int gwords = 0;
+  for (int a = 0; a < h->d.ndim; ++a) gwords += h->d.n[a];
+  for (int b = 0; b < B; ++b) {
+    if (kappa && !std::isfinite(kappa[b])) return bfail(h, SDFS_ERR_ARG, "kappa[%d] is not finite", b);
+    if (n_max > 0 && !std::isfinite(kappa_ts[b])) return bfail(h, SDFS_ERR_ARG, "kappa_ts[%d] is not finite", b);
+    for (int i = 0; i < gwords; ++i)
+      if (!std::isfinite(weights[(size_t)b * gwords + i])) return bfail(h, SDFS_ERR_ARG, "weights of problem %d are not finite", b);
+  }
+  // the tilt tables of every stage (batch_price.hpp): t1[n_lam] t2[n_c] t3[na3], fp64 on the host; a stage that does
+  // not run keeps 1
+  const int tw = nl + nc + na3;
+  std::vector<double> tilt((size_t)B * BP_STAGES * tw, 1.0);
+  for (int b = 0; b < B; ++b) {
+    const double th = h->theta_host[b], ga = h->gam_host[b], og = 1.0 - ga;
+    const double* const hl = h->hlam_host.data() + (size_t)b * nl;
+    const double* const sc = h->sigc_host.data() + (size_t)b * nc;
+    const double* const mz = h->muz_host.data() + (size_t)b * na3;
+    auto fill = [&](int stage, int p, double kl, double kc) {
+      double* const t = tilt.data() + ((size_t)b * BP_STAGES + stage) * tw;
+      const double xl = kl - th, xc = 0.5 * (kc * kc - og * og), xz = kc - p * og;
+      for (int i = 0; i < nl; ++i) t[i] = std::exp(xl * hl[i]);
+      for (int i = 0; i < nc; ++i) t[nl + i] = std::exp(xc * sc[i] * sc[i]);
+      for (int i = 0; i < na3; ++i) t[nl + nc + i] = std::exp(xz * mz[i]);
+    };
+    if (kappa) { fill(0, 1, th, kappa[b] - ga); fill(3, 0, 0.0, kappa[b]); }
+    fill(1, 1, th, -ga);
+    fill(2, 2, 2.0 * th, -2.0 * ga);
+    if (n_max > 0) fill(4, 1, th, kappa_ts[b] - ga);
+  }
+  if ((rc = batch_price_prepare(h))) return rc;
+  hipStream_t st = h->stream;
+  BatchDevBuf tiltd, gaxd;
+  BHIPCHK(h, hipMalloc((void**)&tiltd.p, tilt.size() * 8));
+  BHIPCHK(h, hipMalloc((void**)&gaxd.p, (size_t)B * gwords * 8));
+  BHIPCHK(h, hipMemcpyAsync(tiltd.p, tilt.data(), tilt.size() * 8, hipMemcpyHostToDevice, st));
+  BHIPCHK(h, hipMemcpyAsync(gaxd.p, weights, (size_t)B * gwords * 8, hipMemcpyHostToDevice, st));
+  BatchPriceArgs A;
+  memset(&A, 0, sizeof A);
+  A.tab = h->tab; A.scal = h->scal; A.w = w_dev; A.tilt = tiltd.p; A.gax = gaxd.p;
+  A.EM = EM_dev; A.EM2 = EM2_dev; A.pd = pd_dev; A.ER = ER_dev; A.mom = moments_dev; A.hz = n_max > 0 ? horizons_dev : nullptr;
+  A.ws = h->ws; A.st = h->pst; A.status = h->status;
+  A.rtol2 = opts->inner_rtol * opts->inner_rtol; A.atol2 = opts->inner_atol * opts->inner_atol;
+  A.inner_max = opts->inner_max_iter > 0 ? (long long)opts->inner_max_iter : 10LL * h->d.N;
+  A.n_max = n_max;
+  A.budget = opts->check_every > 0 ? (int)opts->check_every : batch_newton_default_budget(h);
+  A.ax_lam = h->ax_lam; A.ax_c = h->ax_c; A.na3 = na3; A.tiltwords = tw; A.gwords = gwords;
+  A.claim = kappa ? 1 : 0;
+  {
+    const long long work = std::max<long long>((long long)B * std::max<long long>(BP_WORDS, 4 * n_max), (ER_dev || pd_dev) ? (long long)B * h->d.N : 0);
+    const int blocks = (int)std::min<long long>((work + 255) / 256, (long long)h->num_cus * 8);
+    hipLaunchKernelGGL(batch_price_init_kernel, dim3(std::max(1, blocks)), dim3(256), 0, st, B, h->d.N, h->status, h->pst, moments_dev,
+                       A.hz, ER_dev, kappa ? (double*)nullptr : pd_dev, (long long)n_max, kappa ? 0 : 1);
+    BHIPCHK(h, hipGetLastError());
+  }
+  // group after group, as the Newton solve; every launch is bounded by A.budget >= 1 applications per problem, and every
+  // application moves its problem on within the finite counts of batch_price.hpp, so the loop ends
+  for (int b0 = 0; b0 < B; b0 += h->ws_slots) {
+    const int G = std::min(h->ws_slots, B - b0);
+    A.b0 = b0;
+    bool open = true;
+    while (open) {
+      hipLaunchKernelGGL(h->pfn, dim3(G), dim3(h->nt), h->lds_bytes, st, (const BatchDesc*)h->d_dev, A);
+      BHIPCHK(h, hipGetLastError());
+      BHIPCHK(h, hipMemcpyAsync(h->status_host + b0, h->status + b0, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, st));
+      BHIPCHK(h, hipStreamSynchronize(st));
+      open = false;
+      for (int b = b0; b < b0 + G && !open; ++b) open = h->status_host[b] == BATCH_OPEN;
+    }
+  }
+  std::vector<BatchPriceState> ps((size_t)B);
+  BHIPCHK(h, hipMemcpyAsync(ps.data(), h->pst, (size_t)B * sizeof(BatchPriceState), hipMemcpyDeviceToHost, st));
+  BHIPCHK(h, hipStreamSynchronize(st));
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int b = 0; b < B; ++b) {
+    n_iter[b] = ps[b].k; n_apply[b] = ps[b].napply; n_horizons[b] = ps[b].nh;
+    // (BATCH_OPEN is 3 on the device, so the kernel reports "no finite price" as BATCH_NO_PRICE_DEV)
+    status[b] = h->status_host[b] == BATCH_NO_PRICE_DEV ? (int)SDFS_BATCH_NO_PRICE : h->status_host[b];
+    resid_T[b] = ps[b].resid_T;
+    rel_resid[b] = !kappa ? nan : (ps[b].gg > 0.0 ? std::sqrt(ps[b].tr / ps[b].gg) : (ps[b].gg == 0.0 ? 0.0 : ps[b].gg));
+    if (status[b] == BATCH_NONFINITE) rel_resid[b] = nan;
+  }
+  return 0;
+}
+
 int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap) {
   if (!h || !buf || cap < 1) return SDFS_ERR_ARG;
   std::string s;
@@ -4748,6 +4895,12 @@ int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap) {
     snprintf(line, sizeof line, "adjoint: lambda with r, rhat, p, q, c_in, c_out and w %s; %d moments per problem (s0 s1 s2 | R[%d] | M1[%d] | M2[%d] | M3[%d]); default budget %d applications per launch\n",
              h->adjoint_reg ? "in registers (the Newton workspace holds them between launches only)" : "in global memory (w in the caller's buffer, seven in the Newton workspace)",
              batch_adjoint_words(h), h->d.ndim, h->d.n[h->ax_lam], h->d.n[h->ax_c], h->na3, batch_newton_default_budget(h));
+    s += line;
+  }
+  if (h->pfn) {
+    snprintf(line, sizeof line, "pricing: v, E_M, the point weights, P_n with c_in, c_out (rescaled per stage) and w %s; %d words per problem, tilt tables of %d + %d + %d doubles per stage; at most 2 inner_max + n_max + %d applications per problem\n",
+             h->price_reg ? "in registers (the Newton workspace holds them between launches only)" : "in global memory (w in the caller's buffer, seven in the Newton workspace)",
+             BP_WORDS, h->d.n[h->ax_lam], h->d.n[h->ax_c], h->na3, 2 * BP_RESTARTS + 11);
     s += line;
   }
   snprintf(buf, (size_t)cap, "%s", s.c_str());
