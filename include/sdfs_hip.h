@@ -530,6 +530,59 @@ int sdfs_batch_price_dev(sdfs_batch* h, const sdfs_opts* opts, const double* w_d
                          double* moments_dev, double* horizons_dev, int64_t* n_iter, int64_t* n_apply, int64_t* n_horizons,
                          double* rel_resid, double* resid_T, int32_t* status);
 
+/* Simulated paths for all B problems at the batch's w* (csrc/batch_sim.hpp): the chain, the random
+ * numbers, the series and the per-path statistics of sdfs_sim_paths_dev, on a launch grid of (workgroups per member,
+ * members), and the cross-path moments of every statistic reduced on the device.  One seed serves all members (common
+ * random numbers); a path's indices, series and statistics depend only on its number, the seed and its member's inputs,
+ * not on B or the member's place in the batch. */
+typedef struct sdfs_batch_sim_desc {
+  uint64_t seed;
+  int64_t path_offset;      /* number of the first path; path_offset + n_paths <= 2^32 */
+  int64_t n_paths;          /* per member */
+  int64_t burn_in;          /* >= 0 */
+  int64_t n_periods;        /* T >= 2, burn_in + T < 2^32 - 8 */
+  int32_t has_kappa;        /* the records carry ln v and ln(1 + v): the series rd, xd, pd */
+  int32_t start_fixed;      /* 1: x_0 = start[]; 0: x_0 drawn from every member's stationary marginals (cdf0) */
+  int32_t start[6];
+  int32_t records;          /* where a path-step reads its record: 1 LDS, 2 global memory, 0 the default of the shape */
+  int32_t lookahead;        /* global form: record loads in flight per lane, 1, 2 or 4 (0: the default) */
+  int32_t search;           /* inverse-CDF search: 0 or 2 (bisection); 1 (linear) is SDFS_ERR_UNSUPPORTED */
+  int32_t reserved;
+  const double* kappa;      /* HOST: B leverages (read with has_kappa) */
+  const double* cdf;        /* HOST: per member, then per axis in grid order, the n_a x n_a cumulative rows (last entry 2) */
+  const double* cdf0;       /* HOST: per member, then per axis, the n_a cumulative stationary weights (NULL with start_fixed) */
+  const int32_t* skip;      /* HOST: B flags, nonzero = the member runs no path and its outputs are NaN; NULL: none */
+} sdfs_batch_sim_desc;
+/* Dynamic LDS in bytes of the path kernel for this shape with records == 1 (tables + N x 64 B of records + the reduction
+ * slots) or records == 2 (tables + slots); SDFS_ERR_UNSUPPORTED where the shape is beyond the batch plan or, with
+ * records == 1, the records do not fit one CU.  Makes no device call. */
+int64_t sdfs_batch_sim_lds_bytes(int model, int ndim, const int64_t* shapes, int records);
+/* The table blocks sdfs_batch_sim_paths_dev uploads for a request, formed on the host by the code that call and
+ * sdfs_batch_create run (no device call): tab_out B x words, per member the cumulative rows per axis, the cumulative
+ * stationary marginals (2 everywhere with start_fixed), h_lambda and sigma_c, padded to an even count; scal_out B x 4 =
+ * theta, theta ln beta, gamma, kappa (0 without a claim or for a skipped member); zt_out (may be NULL) B x na3 = mu_c + z
+ * in the a3 layout, the table of sdfs_batch_sim_records_dev.  The first eight arguments are those of sdfs_batch_create.
+ * Returns words (also with the three outputs NULL, which only asks for it), or an error code. */
+int64_t sdfs_batch_sim_tables(int model, int ndim, const int64_t* shapes, int64_t B, const double* params,
+                              const double* const* arrays, const int64_t* array_sizes, int narrays,
+                              const sdfs_batch_sim_desc* desc, double* tab_out, double* scal_out, double* zt_out);
+/* One 64-byte record per state and member into records_dev (B x N x 8): the fields of sdfs_sim_records_dev from w_dev,
+ * em_dev (E_x[M], e.g. EM_dev of sdfs_batch_price_dev) and v_dev (pd_dev of that call; NULL: no claim), B x N each.
+ * Asynchronous on the handle's stream. */
+int sdfs_batch_sim_records_dev(sdfs_batch* h, const double* w_dev, const double* em_dev, const double* v_dev,
+                               double* records_dev);
+/* stats_dev: B x (3 nser + 1) x n_paths, rows as sdfs_sim_paths_dev (may be NULL).  moments_dev: B x (3 nser + 1) x 3 =
+ * (n, mean, se) over a member's paths of every statistic: n counts the finite values (a NaN statistic, i.e. a zero
+ * denominator, is left out), se = sqrt(M2 / (n - 1) / n), NaN for n < 2 (may be NULL; not both).  Each workgroup reduces
+ * its 256 paths to (n, mean, M2) in a fixed order and the triples are merged in workgroup order by Chan's pairwise
+ * formula: no atomics, two runs give identical bits, and both record forms give the same bits.  idx_dev (B x n_paths x
+ * (T+1) x ndim bytes) and series_dev (B x nser x n_paths x T) are both NULL or both set (then with the default
+ * lookahead).  A skipped member gets NaN statistics, moments and series and zero indices.  records == 1 on a shape whose
+ * records do not fit LDS is SDFS_ERR_ARG.  The host waits only for the table uploads of the handle's previous call (an
+ * event behind them), never for kernels. */
+int sdfs_batch_sim_paths_dev(sdfs_batch* h, const double* records_dev, const sdfs_batch_sim_desc* desc, double* stats_dev,
+                             double* moments_dev, uint8_t* idx_dev, double* series_dev);
+
 /* Human-readable description of the batch plan. */
 int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap);
 

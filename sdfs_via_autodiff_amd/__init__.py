@@ -31,7 +31,8 @@ from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_rat
 from .pricing import stationary_weights, sdf_moments, term_structure, claim_prices
 from .simulation import simulate
 from .batch import (BatchOperator, BatchResult, solve_batch, batch_lds_bytes, BatchGradient, gradient_batch, BatchPrices,
-                    price_batch, price_words_to_stats)
+                    price_batch, price_words_to_stats, BatchSimulation, simulate_batch, batch_sim_lds_bytes,
+                    batch_cdf_tables, batch_sim_tables)
 from ._lib import SdfsError, LIB_PATH
 
 __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize_gcy",
@@ -49,4 +50,5 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "SSY_PERSISTENCE", "GCY_PERSISTENCE", "adjoint_moments_to_gradient",
            "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate",
            "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes", "BatchGradient", "gradient_batch", "BatchPrices", "price_batch", "price_words_to_stats",
+           "BatchSimulation", "simulate_batch", "batch_sim_lds_bytes", "batch_cdf_tables", "batch_sim_tables",
            "SdfsError", "LIB_PATH"]

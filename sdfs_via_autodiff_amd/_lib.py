@@ -18,6 +18,8 @@ SDFS_ERR_NUMERIC = -4
 SDFS_MAX_KERNELS = 16
 SDFS_BATCH_CONVERGED, SDFS_BATCH_MAX_ITER, SDFS_BATCH_NONFINITE = 0, 1, 2
 SDFS_BATCH_NO_PRICE = 3
+SDFS_BATCH_BAD_W = 4              # simulation: a point of w <= 1 (host-side status, no kernel reports it)
+SDFS_BATCH_SIM_LDS, SDFS_BATCH_SIM_GLOBAL = 1, 2
 SDFS_BATCH_PRICE_WORDS = 12
 
 
@@ -46,6 +48,15 @@ class sdfs_sim_desc(C.Structure):
                 ("has_kappa", C.c_int32), ("start_fixed", C.c_int32), ("kappa", C.c_double),
                 ("start", C.c_int32 * 6), ("lookahead", C.c_int32), ("search", C.c_int32),
                 ("cdf", C.POINTER(C.c_double)), ("cdf0", C.POINTER(C.c_double))]
+
+
+class sdfs_batch_sim_desc(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("path_offset", C.c_int64), ("n_paths", C.c_int64),
+                ("burn_in", C.c_int64), ("n_periods", C.c_int64),
+                ("has_kappa", C.c_int32), ("start_fixed", C.c_int32), ("start", C.c_int32 * 6),
+                ("records", C.c_int32), ("lookahead", C.c_int32), ("search", C.c_int32), ("reserved", C.c_int32),
+                ("kappa", C.POINTER(C.c_double)), ("cdf", C.POINTER(C.c_double)), ("cdf0", C.POINTER(C.c_double)),
+                ("skip", C.POINTER(C.c_int32))]
 
 
 class sdfs_counters(C.Structure):
@@ -129,6 +140,11 @@ SYMBOLS = {
                                          C.POINTER(C.c_int32)]),
     "sdfs_batch_price_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _D, _D, _D, C.c_int64, _P, _P, _P, _P, _P, _P, _I64, _I64,
                                        _I64, _D, _D, C.POINTER(C.c_int32)]),
+    "sdfs_batch_sim_lds_bytes": (C.c_int64, [C.c_int, C.c_int, _I64, C.c_int]),
+    "sdfs_batch_sim_tables": (C.c_int64, [C.c_int, C.c_int, _I64, C.c_int64, _D, C.POINTER(_D), _I64, C.c_int,
+                                          C.POINTER(sdfs_batch_sim_desc), _D, _D, _D]),
+    "sdfs_batch_sim_records_dev": (C.c_int, [_P, _P, _P, _P, _P]),
+    "sdfs_batch_sim_paths_dev": (C.c_int, [_P, _P, C.POINTER(sdfs_batch_sim_desc), _P, _P, _P, _P]),
     "sdfs_batch_describe": (C.c_int, [_P, C.c_char_p, C.c_int64]),
 }
 

@@ -13,6 +13,8 @@ problem after problem, so the call works for every shape the package supports.
     res.w[b], res.n_iter[b], res.error[b], res.status[b], res.plan
     res = solve_batch(models, (10, 10, 10, 10), algorithm="newton", inner_rtol=1e-5, inner_atol=0.0)
     res.n_apply[b]                       # applications of T plus J.v of problem b
+    sim = simulate_batch(models, (10, 10, 10, 10), res.w, 4096, 1200, burn_in=16, kappa=2.0)
+    sim.moments["xd"]["mean"]["mean"][b]  # cross-path mean of member b's per-path mean excess return
 """
 import ctypes as C
 import weakref
@@ -58,6 +60,95 @@ def batch_lds_bytes(kind, shapes):
     if n < 0:
         raise _lib.SdfsError(f"sdfs_batch_lds_bytes failed ({n}): {lib.sdfs_batch_last_error(None).decode()}")
     return int(n)
+
+
+def batch_sim_lds_bytes(kind, shapes, records=1):
+    """Dynamic LDS in bytes of the batch's path kernel for ``shapes`` with the records in LDS (``records=1``) or
+    gathered from global memory (``records=2``), or None where that form does not exist for the shape
+    (sdfs_batch_sim_lds_bytes; no device call)."""
+    model = _KINDS[kind][0]
+    shp = (C.c_int64 * len(shapes))(*[int(s) for s in shapes])
+    n = lib.sdfs_batch_sim_lds_bytes(model, len(shapes), shp, int(records))
+    if n == _lib.SDFS_ERR_UNSUPPORTED:
+        return None
+    if n < 0:
+        raise _lib.SdfsError(f"sdfs_batch_sim_lds_bytes failed ({n}): {lib.sdfs_batch_last_error(None).decode()}")
+    return int(n)
+
+
+def batch_cdf_tables(kind, shapes, arrays):
+    """(cdf (B, Σ n_a²), cdf0 (B, Σ n_a)): per member the tables of ``simulation.cdf_tables``, axis after axis (the
+    cumulative rows row-major), from the batch's stacked arrays (array i: (B, size)).  ValueError when a member's chain
+    does not factorise.  Host only."""
+    from . import pricing
+    shapes = tuple(int(s) for s in shapes)
+    arrays = [np.asarray(a, dtype=np.float64) for a in arrays]
+    B = arrays[0].shape[0]
+    cdf = np.empty((B, int(sum(n * n for n in shapes))))
+    cdf0 = np.empty((B, int(sum(shapes))))
+    for b in range(B):
+        o = o0 = 0
+        for a, (qi, n) in enumerate(zip(pricing._AXIS_Q[kind], shapes)):
+            Q = arrays[qi][b].reshape(-1, n, n)
+            if np.max(np.abs(Q - Q[:1])) > 1e-14:
+                raise ValueError(f"member {b}, axis {a}: the conditional transition tensor differs between its slices, so "
+                                 "the chain does not factorise")
+            c = np.cumsum(Q[0], axis=1)
+            c[:, -1] = 2.0
+            c0 = np.cumsum(pricing._perron_left(Q[0]))
+            c0[-1] = 2.0
+            cdf[b, o:o + n * n] = c.ravel()
+            cdf0[b, o0:o0 + n] = c0
+            o += n * n
+            o0 += n
+    return cdf, cdf0
+
+
+def batch_sim_tables(kind, shapes, params, arrays, cdf, cdf0=None, start=None, kappa=None, skip=None):
+    """(tab (B, words), scal (B, 4), zt (B, na3)): the table blocks ``sdfs_batch_sim_paths_dev`` uploads for a request
+    (per member the cumulative rows per axis, the cumulative stationary marginals, h_λ and σ_c), its scalars θ, θ ln β, γ,
+    κ, and the μ_c + z table of the records kernel in the a3 layout, formed by the library's host code from the batch's
+    ``params`` (B, nparams) and stacked ``arrays`` (sdfs_batch_sim_tables; no device call)."""
+    model, ndim, nparams, narrays = _KINDS[kind]
+    shapes = tuple(int(n) for n in shapes)
+    params = _as_f64(params)
+    B = int(params.shape[0])
+    arrs = [_as_f64(a).reshape(B, -1) for a in arrays]
+    if params.shape != (B, nparams) or len(arrs) != narrays:
+        raise ValueError(f"{kind} needs params (B, {nparams}) and {narrays} arrays")
+    dp = C.POINTER(C.c_double)
+    d = _lib.sdfs_batch_sim_desc()
+    d.n_paths, d.n_periods = 1, 2
+    keep = [np.ascontiguousarray(cdf, dtype=np.float64)]
+    d.cdf = keep[0].ctypes.data_as(dp)
+    if start is not None:
+        d.start_fixed = 1
+        for a, s0 in enumerate(start):
+            d.start[a] = int(s0)
+    else:
+        keep.append(np.ascontiguousarray(cdf0, dtype=np.float64))
+        d.cdf0 = keep[-1].ctypes.data_as(dp)
+    if kappa is not None:
+        keep.append(np.ascontiguousarray(kappa, dtype=np.float64))
+        d.has_kappa, d.kappa = 1, keep[-1].ctypes.data_as(dp)
+    if skip is not None:
+        keep.append(np.ascontiguousarray(skip, dtype=np.int32))
+        d.skip = keep[-1].ctypes.data_as(C.POINTER(C.c_int32))
+    if keep[0].shape != (B, sum(n * n for n in shapes)) or any(k.shape[0] != B for k in keep):
+        raise ValueError("cdf, cdf0, kappa and skip need one row or entry per member")
+    shp = (C.c_int64 * ndim)(*shapes)
+    ptrs = (dp * narrays)(*[a.ctypes.data_as(dp) for a in arrs])
+    sizes = (C.c_int64 * narrays)(*[a.shape[1] for a in arrs])
+    args = (model, ndim, shp, B, params.ctypes.data_as(dp), ptrs, sizes, narrays, C.byref(d))
+    words = lib.sdfs_batch_sim_tables(*args, None, None, None)
+    if words < 0:
+        raise _lib.SdfsError(f"sdfs_batch_sim_tables failed ({words}): {lib.sdfs_batch_last_error(None).decode()}")
+    na3 = shapes[2] * shapes[3] if kind == "ssy" else shapes[1] * shapes[2] * shapes[4] * shapes[0]
+    tab, scal, zt = np.empty((B, words)), np.empty((B, 4)), np.empty((B, na3))
+    rc = lib.sdfs_batch_sim_tables(*args, tab.ctypes.data_as(dp), scal.ctypes.data_as(dp), zt.ctypes.data_as(dp))
+    if rc < 0:
+        raise _lib.SdfsError(f"sdfs_batch_sim_tables failed ({rc}): {lib.sdfs_batch_last_error(None).decode()}")
+    return tab, scal, zt
 
 
 class BatchOperator:
@@ -302,6 +393,108 @@ class BatchOperator:
                              mom.data_ptr(), None if hz is None else hz.data_ptr(), rtol, atol, inner_max_iter, check_every)
         gd = dict(zip(("E_M", "E_M2", "pd", "expected_return"), (t.cpu().numpy() for t in grids))) if return_grids else None
         return (mom.cpu().numpy(), hz.cpu().numpy() if hz is not None else np.zeros((self.B, 0, 4)), gd) + tuple(out)
+
+
+    # -- simulated paths (csrc/batch_sim.hpp) -----------------------------------------------------------------
+    def simulate_dev(self, w_ptr, em_ptr, pd_ptr, records_ptr, cdf, cdf0, n_paths, n_periods, *, burn_in=0, seed=0,
+                     path_offset=0, start=None, kappa=None, skip=None, records=0, lookahead=0, search=0, stats_ptr=None,
+                     moments_ptr=None, idx_ptr=None, series_ptr=None):
+        """sdfs_batch_sim_records_dev, then sdfs_batch_sim_paths_dev, asynchronous on the handle's stream.  Device
+        pointers: ``w_ptr``, ``em_ptr`` (E_x[M]) and ``pd_ptr`` (None without a claim) of B x N doubles, ``records_ptr``
+        (B x N x 8, written), ``stats_ptr`` (B x (3 nser + 1) x P, may be None), ``moments_ptr`` (B x (3 nser + 1) x 3),
+        ``idx_ptr`` and ``series_ptr`` (both or neither).  Host arrays: ``cdf`` (B, Σ n_a²) and ``cdf0`` (B, Σ n_a; None
+        with a fixed ``start``) as ``batch_cdf_tables`` lays them out, ``kappa`` (B,) or None, ``skip`` (B,) flags or
+        None.  ``records``: 0 the shape's default, 1 LDS, 2 global; ``lookahead``: 0, 1, 2 or 4."""
+        dp = C.POINTER(C.c_double)
+        d = _lib.sdfs_batch_sim_desc()
+        d.seed, d.path_offset, d.n_paths, d.burn_in, d.n_periods = int(seed), int(path_offset), int(n_paths), int(burn_in), int(n_periods)
+        d.records, d.lookahead, d.search = int(records), int(lookahead), int(search)
+        keep = []
+
+        def host(x, shape, dtype, what):
+            a = np.ascontiguousarray(x, dtype=dtype)
+            if a.shape != shape:
+                raise ValueError(f"{what} has shape {a.shape}: expected {shape}")
+            keep.append(a)
+            return a
+        if (pd_ptr is None) != (kappa is None):
+            raise ValueError("kappa and pd_ptr go together: both None or neither")
+        if kappa is not None:
+            d.has_kappa = 1
+            d.kappa = host(kappa, (self.B,), np.float64, "kappa").ctypes.data_as(dp)
+        d.cdf = host(cdf, (self.B, int(sum(n * n for n in self.shapes))), np.float64, "cdf").ctypes.data_as(dp)
+        if start is not None:
+            if len(start) != len(self.shapes):
+                raise ValueError(f"start needs one state index per axis ({len(self.shapes)}), got {len(start)}")
+            d.start_fixed = 1
+            for a, s0 in enumerate(start):
+                d.start[a] = int(s0)
+        else:
+            if cdf0 is None:
+                raise ValueError("a stationary start needs cdf0")
+            d.cdf0 = host(cdf0, (self.B, int(sum(self.shapes))), np.float64, "cdf0").ctypes.data_as(dp)
+        if skip is not None:
+            d.skip = host(skip, (self.B,), np.int32, "skip").ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(lib.sdfs_batch_sim_records_dev(self._h, w_ptr, em_ptr, pd_ptr, records_ptr))
+        self._check(lib.sdfs_batch_sim_paths_dev(self._h, records_ptr, C.byref(d), stats_ptr, moments_ptr, idx_ptr, series_ptr))
+
+    def simulate(self, w, n_paths, n_periods, *, burn_in=0, seed=0, path_offset=0, start="stationary", kappa=None,
+                 rtol=1e-10, records=0, return_per_path=False, return_paths=False):
+        """Host ``w`` (B, *shapes) in: ``n_paths`` paths of ``n_periods`` recorded steps per member, all members on one
+        seed (common random numbers).  ``kappa``: None, a scalar or B entries; the claim's price-dividend ratio comes
+        from ``price_dev`` at ``rtol``.  A member with a point of w <= 1 gets status 4, one whose pricing status is not 0
+        keeps that status (3: no finite price); such members run no path and their outputs are NaN.  Returns a dict:
+        "series" (names), "moments" (B, 3 nser + 1, 3) = (n, mean, se) per statistic from the device reduction, "stats"
+        (B, 3 nser + 1, P) or None, "index" (B, P, T+1, d) and "paths" (B, nser, P, T) or None, "status", "n_iter" and
+        "rel_resid" of the claim solve."""
+        import torch
+        from . import simulation as sim
+        P, T, Bn, off, sd, rtol, fixed = sim._request(self.shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol,
+                                                      return_paths, members=self.B)
+        if Bn + T >= (1 << 32) - 8:
+            raise ValueError(f"burn_in + n_periods = {Bn + T} >= 2^32 - 8")
+        records = _check_records(records)
+        w = self._host_in(w)
+        kap = _per_member(kappa, self.B, "kappa", optional=True)
+        if records == _lib.SDFS_BATCH_SIM_LDS and batch_sim_lds_bytes(self.kind, self.shapes, 1) is None:
+            raise ValueError(f"records=1: the {self.size} records of shapes {self.shapes} do not fit the LDS of one CU")
+        names = sim.SERIES_KAPPA if kap is not None else sim.SERIES
+        ns, nd = len(names), len(self.shapes)
+        nstat = 3 * ns + 1
+        bad_w = ~np.all(w.reshape(self.B, -1) > 1.0, axis=1)
+        cdf, cdf0 = batch_cdf_tables(self.kind, self.shapes, self._arrays)
+        want_stats = bool(return_per_path)
+        need = self.B * (self.size * (sim.REC_BYTES + 24) + (nstat * P * 8 if want_stats else 0))
+        if return_paths:
+            need += self.B * (P * T * ns * 8 + P * (T + 1) * nd)
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if need > free:
+            raise ValueError(f"the per-state records and outputs need {need / 2**30:.2f} GiB, {free / 2**30:.2f} GiB of "
+                             "device memory is free")
+        wd = self._to_dev(w)
+        dev = wd.device
+        em = torch.empty_like(wd)
+        pd = torch.empty_like(wd) if kap is not None else None
+        pmom = torch.empty((self.B, _lib.SDFS_BATCH_PRICE_WORDS), dtype=torch.float64, device=dev)
+        rec = torch.empty((self.B, self.size, 8), dtype=torch.float64, device=dev)
+        mom = torch.empty((self.B, nstat, 3), dtype=torch.float64, device=dev)
+        stats = torch.empty((self.B, nstat, P), dtype=torch.float64, device=dev) if want_stats else None
+        idx = torch.empty((self.B, P, T + 1, nd), dtype=torch.uint8, device=dev) if return_paths else None
+        ser = torch.empty((self.B, ns, P, T), dtype=torch.float64, device=dev) if return_paths else None
+        torch.cuda.current_stream(dev).synchronize()
+        n_iter, _, _, rel, _, status = self.price_dev(wd.data_ptr(), kap, None, self._stationary_weights(), 0, em.data_ptr(), None,
+                                                      None if pd is None else pd.data_ptr(), None, pmom.data_ptr(), None, rtol, 0.0)
+        status = status.copy()
+        status[bad_w] = _lib.SDFS_BATCH_BAD_W
+        self.simulate_dev(wd.data_ptr(), em.data_ptr(), None if pd is None else pd.data_ptr(), rec.data_ptr(), cdf,
+                          None if fixed is not None else cdf0, P, T, burn_in=Bn, seed=sd, path_offset=off, start=fixed, kappa=kap,
+                          skip=(status != 0).astype(np.int32), records=records,
+                          stats_ptr=None if stats is None else stats.data_ptr(), moments_ptr=mom.data_ptr(),
+                          idx_ptr=None if idx is None else idx.data_ptr(), series_ptr=None if ser is None else ser.data_ptr())
+        self.synchronize()
+        return {"series": names, "moments": mom.cpu().numpy(), "stats": None if stats is None else stats.cpu().numpy(),
+                "index": None if idx is None else idx.cpu().numpy(), "paths": None if ser is None else ser.cpu().numpy(),
+                "status": status, "n_iter": n_iter, "rel_resid": rel}
 
 
 def _grid_or_batch(x, B, shapes, what):
@@ -630,3 +823,129 @@ def price_batch(models, shapes, w_star, kappa=None, n_max=0, kappa_ts=0.0, weigh
     return BatchPrices(price_words_to_stats(mom), mom, hz[:, :, 0].copy(), hz[:, :, 1].copy(), hz[:, :, 2:4].copy(), n_hor,
                        grids, np.full(B, -1, dtype=np.int64), np.full(B, -1, dtype=np.int64), np.full(B, np.nan),
                        np.full(B, np.nan), status, "loop")
+
+
+BatchSimulation = namedtuple("BatchSimulation", ["series", "moments", "per_path", "paths", "status", "price", "plan"])
+BatchSimulation.__doc__ = """series: the names (dc, m, rf, rc, xc, wc, and rd, xd, pd with a claim); moments: {name: {"mean" |
+"std" | "ac1": {"n", "mean", "se"}}, "slope": {"n", "mean", "se"}}, arrays of length B over a member's paths of every
+per-path statistic (n: its finite values; from the device reduction on the batch plan); per_path: None, or {name: {stat:
+{"values": (B, P), "median", "p05", "p95": (B,)}}, "slope": the same}; paths: None, or {"index": (B, P, T+1, d) uint8, name:
+(B, P, T)}; status per member: 0 simulated, 1 the claim solve stopped above its tolerance, 2 non-finite, 3 no finite price
+(r(K) >= 1), 4 a point of w* <= 1 (members with a status other than 0 ran no path: their entries are NaN, their indices 0);
+price: {"n_iter", "rel_resid"} of the claim solve (-1 and NaN on the loop plan and without a claim); plan: "batch" or
+"loop"."""
+
+
+def _check_records(records):
+    if isinstance(records, bool) or records not in (0, _lib.SDFS_BATCH_SIM_LDS, _lib.SDFS_BATCH_SIM_GLOBAL):
+        raise ValueError(f"records must be 0 (the shape's default), 1 (LDS) or 2 (global memory), got {records!r}")
+    return int(records)
+
+
+def _sim_fields(names, mom, stats, index, paths):
+    """The fields of a BatchSimulation from (B, nstat, 3) moments, (B, nstat, P) statistics or None, and the stored paths."""
+    from . import simulation as sim
+
+    def triple(k):
+        return {"n": mom[:, k, 0].copy(), "mean": mom[:, k, 1].copy(), "se": mom[:, k, 2].copy()}
+    moments = {nm: {s: triple(3 * i + j) for j, s in enumerate(sim.STATS)} for i, nm in enumerate(names)}
+    moments["slope"] = triple(3 * len(names))
+    per_path = None
+    if stats is not None:
+        def entry(k):
+            sm = [sim._summary(row) for row in stats[:, k]]
+            return {"values": stats[:, k], **{q: np.array([x[q] for x in sm]) for q in ("median", "p05", "p95")}}
+        per_path = {nm: {s: entry(3 * i + j) for j, s in enumerate(sim.STATS)} for i, nm in enumerate(names)}
+        per_path["slope"] = entry(3 * len(names))
+    out_paths = None
+    if paths is not None:
+        out_paths = {"index": index}
+        for i, nm in enumerate(names):
+            out_paths[nm] = paths[:, i]
+    return moments, per_path, out_paths
+
+
+def simulate_batch(models, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, path_offset=0, start="stationary",
+                   kappa=None, rtol=1e-10, records=0, return_per_path=False, return_paths=False, method="rouwenhorst",
+                   device=0):
+    """Simulated paths of every member of ``models`` at its fixed point ``w_star[b]`` (normally ``solve_batch(...).w``):
+    ``n_paths`` paths of ``n_periods`` recorded steps after ``burn_in`` per member, one lane per path on a launch grid of
+    (workgroups per member, members), all members on the one ``seed`` (common random numbers, which differences of
+    simulated moments across parameter vectors want), and the cross-path moments (n, mean, se) of every per-path
+    statistic reduced on the device (csrc/batch_sim.hpp).  The arguments are those of ``simulate``; ``kappa``: None, a
+    scalar or B entries; ``records``: where a path-step reads its state record, 0 the shape's default, 1 LDS, 2 global
+    memory (both give the same bits).  ``return_per_path`` adds the (B, P) statistics, ``return_paths`` the indices and
+    series (B·P·T <= 2^25).  Shapes beyond one CU run ``simulate`` member by member (``plan == "loop"``), the moments
+    formed on the host.  Returns a BatchSimulation."""
+    from . import simulation as sim
+    models, kind = _kind_of(models)
+    shapes = tuple(int(s) for s in shapes)
+    ndim = _KINDS[kind][1]
+    if len(shapes) != ndim:
+        raise ValueError(f"{kind} grids have {ndim} axes, got shapes {shapes}")
+    B = len(models)
+    w = _as_f64(w_star)
+    if w.shape != (B,) + shapes:
+        raise ValueError(f"w_star has shape {w.shape}, the batch is {(B,) + shapes}")
+    P, T, Bn, off, sd, rtol, fixed = sim._request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol, return_paths,
+                                                  members=B)
+    records = _check_records(records)
+    kap = _per_member(kappa, B, "kappa", optional=True)
+    names = sim.SERIES_KAPPA if kap is not None else sim.SERIES
+    if batch_lds_bytes(kind, shapes) is not None:
+        op = BatchOperator.from_models(models, shapes, method, device)
+        try:
+            r = op.simulate(w, P, T, burn_in=Bn, seed=sd, path_offset=off, start="stationary" if fixed is None else fixed, kappa=kap,
+                            rtol=rtol, records=records, return_per_path=return_per_path, return_paths=return_paths)
+        finally:
+            op.close()
+        moments, per_path, paths = _sim_fields(names, r["moments"], r["stats"] if return_per_path else None, r["index"], r["paths"])
+        return BatchSimulation(names, moments, per_path, paths, r["status"], {"n_iter": r["n_iter"], "rel_resid": r["rel_resid"]},
+                               "batch")
+    if records == _lib.SDFS_BATCH_SIM_LDS:
+        raise ValueError(f"records=1: shapes {shapes} are beyond the batch plan")
+    if method != "rouwenhorst":
+        raise ValueError(f"shapes beyond one CU are simulated by ``simulate``, which discretises by Rouwenhorst's method, not "
+                         f"{method!r}")
+    # member by member through the single-problem function, the moments formed on the host
+    ns, nd = len(names), ndim
+    nstat = 3 * ns + 1
+    stats = np.full((B, nstat, P), np.nan)
+    index = np.zeros((B, P, T + 1, nd), dtype=np.uint8) if return_paths else None
+    series = np.full((B, ns, P, T), np.nan) if return_paths else None
+    status = np.zeros(B, dtype=np.int32)
+    for b, m in enumerate(models):
+        if not np.all(w[b] > 1.0):
+            status[b] = _lib.SDFS_BATCH_BAD_W
+            continue
+        try:
+            out = sim.simulate(m, shapes, w[b], P, T, burn_in=Bn, seed=sd, path_offset=off,
+                               start="stationary" if fixed is None else fixed, kappa=None if kap is None else kap[b], rtol=rtol,
+                               return_paths=return_paths)
+        except ValueError as e:
+            if "no finite price" not in str(e):
+                raise
+            status[b] = _lib.SDFS_BATCH_NO_PRICE
+            continue
+        for i, nm in enumerate(names):
+            for j, s in enumerate(sim.STATS):
+                stats[b, 3 * i + j] = out["per_path"][nm][s]
+            if return_paths:
+                series[b, i] = out["paths"][nm]
+        stats[b, 3 * ns] = out["per_path"]["slope"]
+        if return_paths:
+            index[b] = out["paths"]["index"]
+    mom = np.full((B, nstat, 3), np.nan)
+    for b in range(B):
+        if status[b] != 0:
+            continue
+        for k in range(nstat):
+            x = stats[b, k][np.isfinite(stats[b, k])]
+            mom[b, k, 0] = x.size
+            if x.size > 0:
+                mom[b, k, 1] = x.mean()
+            if x.size > 1:
+                mom[b, k, 2] = x.std(ddof=1) / np.sqrt(x.size)
+    moments, per_path, paths = _sim_fields(names, mom, stats if return_per_path else None, index, series)
+    return BatchSimulation(names, moments, per_path, paths, status, {"n_iter": np.full(B, -1, dtype=np.int64),
+                                                                     "rel_resid": np.full(B, np.nan)}, "loop")

@@ -38,6 +38,7 @@
 #include "batch_newton.hpp"
 #include "batch_adjoint.hpp"
 #include "batch_price.hpp"
+#include "batch_sim.hpp"
 
 using namespace sdfs;
 
@@ -4286,6 +4287,17 @@ struct sdfs_batch {
   std::vector<double> muz_host;   // [B][na3]: mu_c + z in the a3 layout
   std::vector<double> gam_host, theta_host;   // [B]
   BatchPriceState* pst = nullptr;    // [B]
+  // simulation (batch_sim.hpp): per-call tables staged on the host, device buffers that only grow
+  std::vector<double> beta_host;  // [B]
+  std::vector<double> sim_tab_host, sim_scal_host;
+  std::vector<int> sim_skip_host;
+  double* sim_zt = nullptr;       // [B][na3]: mu_c + z in the a3 layout
+  double* sim_tab = nullptr;      // [B][simwords]
+  double* sim_scal = nullptr;     // [B][4]: theta, theta ln beta, gamma, kappa
+  int* sim_skip = nullptr;        // [B]
+  double* sim_part = nullptr;     // [B][3 nser + 1][workgroups][3]
+  size_t sim_part_cap = 0;        // doubles
+  hipEvent_t sim_staged = nullptr; // recorded behind the uploads of a call: the next call waits for it before it restages
   std::string errmsg;
 };
 
@@ -4498,6 +4510,12 @@ void sdfs_batch_destroy(sdfs_batch* h) {
   if (h->a2) hipFree(h->a2);
   if (h->ast) hipFree(h->ast);
   if (h->pst) hipFree(h->pst);
+  if (h->sim_zt) hipFree(h->sim_zt);
+  if (h->sim_tab) hipFree(h->sim_tab);
+  if (h->sim_scal) hipFree(h->sim_scal);
+  if (h->sim_skip) hipFree(h->sim_skip);
+  if (h->sim_part) hipFree(h->sim_part);
+  if (h->sim_staged) hipEventDestroy(h->sim_staged);
   if (h->own_stream) hipStreamDestroy(h->own_stream);
   delete h;
 }
@@ -4523,7 +4541,7 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
   int na3_tab = 1;
   for (int a = 0; a < ndim; ++a) if (d.a3s[a] != 0) na3_tab *= d.n[a];
   std::vector<double> hlh((size_t)B * d.n[ax_lam], 0.0), sch((size_t)B * d.n[ax_c], 0.0), muzh((size_t)B * na3_tab, 0.0);
-  std::vector<double> gamh((size_t)B, 0.0), thh((size_t)B, 0.0);
+  std::vector<double> gamh((size_t)B, 0.0), thh((size_t)B, 0.0), beth((size_t)B, 0.0);
   for (int64_t b = 0; b < B; ++b) {
     sdfs_handle hh;                        // host fields only: fill_model touches no device
     hh.knobs = read_knobs();
@@ -4556,7 +4574,7 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
     std::copy(hh.sens.hlam.begin(), hh.sens.hlam.end(), hlh.begin() + (size_t)b * d.n[ax_lam]);
     std::copy(hh.sens.sigc.begin(), hh.sens.sigc.end(), sch.begin() + (size_t)b * d.n[ax_c]);
     for (int i = 0; i < na3_tab; ++i) muzh[(size_t)b * na3_tab + i] = hh.sens.mu_c + hh.sens.z[i];
-    gamh[b] = hh.sens.gamma; thh[b] = hh.theta;
+    gamh[b] = hh.sens.gamma; thh[b] = hh.theta; beth[b] = hh.beta;
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -4578,7 +4596,7 @@ int sdfs_batch_create(int model, int ndim, const int64_t* shapes, int64_t B, con
     h->na3 = na3;
   }
   h->a2_host.swap(a2h);
-  h->hlam_host.swap(hlh); h->sigc_host.swap(sch); h->muz_host.swap(muzh); h->gam_host.swap(gamh); h->theta_host.swap(thh);
+  h->hlam_host.swap(hlh); h->sigc_host.swap(sch); h->muz_host.swap(muzh); h->gam_host.swap(gamh); h->theta_host.swap(thh); h->beta_host.swap(beth);
   auto bail = [&](int rc_) { g_create_error = h->errmsg; sdfs_batch_destroy(h); return rc_; };
   auto hip = [&](hipError_t e, const char* what) { return e == hipSuccess ? 0 : bfail(h, SDFS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
   if ((rc = hip(hipSetDevice(device_id), "hipSetDevice"))) return bail(rc);
@@ -4870,6 +4888,260 @@ int sdfs_batch_price_dev(sdfs_batch* h, const sdfs_opts* opts, const double* w_d
   return 0;
 }
 
+// -- simulated paths of the batch (batch_sim.hpp) -----------------------------------------------------------------------
+extern "C++" {
+namespace {
+constexpr int BSIM_K_DEFAULT = 2;            // record loads in flight per lane of the global form (tools/batch_simulation_times.py)
+constexpr int BSIM_RECORDS_DEFAULT = 2;      // the form where both apply: 1 LDS records, 2 global gather (the same A/B: global won by 2.5 % at SSY 5^4)
+
+// doubles of a member's table block: cumulative rows per axis, cumulative stationary marginals, h_lambda, sigma_c (even)
+int batch_sim_words(const BatchDesc& d, int ax_lam, int ax_c) {
+  int n = 0;
+  for (int a = 0; a < d.ndim; ++a) n += d.n[a] * d.n[a] + d.n[a];
+  return (n + d.n[ax_lam] + d.n[ax_c] + 1) & ~1;
+}
+
+// dynamic LDS of k_batch_sim_paths in the form `records` (1 LDS, 2 global)
+long long batch_sim_lds(const BatchDesc& d, int simwords, int records) {
+  return 8LL * ((long long)simwords + (records == 1 ? (long long)d.N * SIM_REC : 0) + BSIM_RED);
+}
+
+template <int ND, bool KAP>
+batch_sim_fn batch_sim_kernel_of(bool ldsrec, bool store, int k) {
+  if (ldsrec) return store ? k_batch_sim_paths<ND, KAP, true, true, 1> : k_batch_sim_paths<ND, KAP, true, false, 1>;
+  if (store) return k_batch_sim_paths<ND, KAP, false, true, BSIM_K_DEFAULT>;
+  return k == 1 ? k_batch_sim_paths<ND, KAP, false, false, 1> : k == 2 ? k_batch_sim_paths<ND, KAP, false, false, 2>
+                                                                       : k_batch_sim_paths<ND, KAP, false, false, 4>;
+}
+
+batch_sim_fn batch_sim_kernel_for(int ndim, bool kap, bool ldsrec, bool store, int k) {
+  if (ndim == 4) return kap ? batch_sim_kernel_of<4, true>(ldsrec, store, k) : batch_sim_kernel_of<4, false>(ldsrec, store, k);
+  return kap ? batch_sim_kernel_of<6, true>(ldsrec, store, k) : batch_sim_kernel_of<6, false>(ldsrec, store, k);
+}
+
+// offsets of a member's table block into `a` (with the request's scalars); *ncdf, *ncdf0: doubles of the cumulative rows
+// and of the cumulative marginals of one member.  Returns the axis of a bad start index, or -1.
+int batch_sim_layout(const BatchDesc& D, int ax_lam, int ax_c, const sdfs_batch_sim_desc* d, SimArgs& a, int* ncdf, int* ncdf0) {
+  int off = 0, bad = -1;
+  for (int ax = 0; ax < D.ndim; ++ax) {
+    a.n[ax] = D.n[ax]; a.stride[ax] = D.stride[ax];
+    a.cdf_off[ax] = off; off += D.n[ax] * D.n[ax];
+    if (d->start_fixed && (d->start[ax] < 0 || d->start[ax] >= D.n[ax]) && bad < 0) bad = ax;
+    a.start[ax] = d->start_fixed ? d->start[ax] : 0;
+  }
+  *ncdf = off;
+  *ncdf0 = 0;
+  for (int ax = 0; ax < D.ndim; ++ax) { a.cdf0_off[ax] = off; off += D.n[ax]; *ncdf0 += D.n[ax]; }
+  a.ax_lam = ax_lam; a.ax_c = ax_c;
+  a.hl_off = off; off += D.n[ax_lam];
+  a.sc_off = off; off += D.n[ax_c];
+  a.lds_n = off;
+  a.start_fixed = d->start_fixed ? 1 : 0;
+  a.key0 = (unsigned)(d->seed & 0xffffffffu); a.key1 = (unsigned)(d->seed >> 32);
+  a.path0 = (unsigned long long)d->path_offset;
+  a.n_paths = d->n_paths;
+  a.burn_in = (unsigned)d->burn_in; a.n_periods = (unsigned)d->n_periods;
+  return bad;
+}
+
+// the table blocks [B][words], the scalars [B][4] = theta, theta ln beta, gamma, kappa and the skip flags [B] of a request,
+// from the members' host fields (h_lambda [B][n_lam], sigma_c [B][n_c], theta, beta, gamma [B]).  Host only.
+void batch_sim_stage(const BatchDesc& D, const SimArgs& a, int ncdf, int ncdf0, int words, int B, const sdfs_batch_sim_desc* d,
+                     const double* hlam, const double* sigc, const double* theta, const double* beta, const double* gam,
+                     double* tb, double* sc, int* sk) {
+  const int nl = D.n[a.ax_lam], nc = D.n[a.ax_c];
+  std::fill(tb, tb + (size_t)B * words, 0.0);
+  for (int b = 0; b < B; ++b) {
+    double* const t = tb + (size_t)b * words;
+    std::copy(d->cdf + (size_t)b * ncdf, d->cdf + (size_t)(b + 1) * ncdf, t);
+    if (d->start_fixed) std::fill(t + ncdf, t + ncdf + ncdf0, 2.0);
+    else std::copy(d->cdf0 + (size_t)b * ncdf0, d->cdf0 + (size_t)(b + 1) * ncdf0, t + ncdf);
+    std::copy(hlam + (size_t)b * nl, hlam + (size_t)(b + 1) * nl, t + a.hl_off);
+    std::copy(sigc + (size_t)b * nc, sigc + (size_t)(b + 1) * nc, t + a.sc_off);
+    const int skip = d->skip && d->skip[b] ? 1 : 0;
+    if (sk) sk[b] = skip;
+    sc[4 * b] = theta[b]; sc[4 * b + 1] = theta[b] * std::log(beta[b]); sc[4 * b + 2] = gam[b];
+    sc[4 * b + 3] = d->has_kappa && !skip ? d->kappa[b] : 0.0;
+  }
+}
+
+template <class T>
+int batch_sim_grow(sdfs_batch* h, T** p, size_t* cap, size_t need) {
+  if (*p && (!cap || *cap >= need)) return 0;
+  if (*p) { BHIPCHK(h, hipStreamSynchronize(h->stream)); BHIPCHK(h, hipFree(*p)); *p = nullptr; }
+  BHIPCHK(h, hipMalloc((void**)p, need * sizeof(T)));
+  if (cap) *cap = need;
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int64_t sdfs_batch_sim_lds_bytes(int model, int ndim, const int64_t* shapes, int records) {
+  BatchDesc d;
+  long long lds = 0;
+  std::string why;
+  const int rc = batch_geometry(model, ndim, shapes, d, &lds, &why);
+  if (rc) { g_create_error = why; return rc; }
+  if (records != 1 && records != 2) { g_create_error = "records: 1 (LDS) or 2 (global)"; return SDFS_ERR_ARG; }
+  const int words = batch_sim_words(d, model == SDFS_MODEL_SSY ? 0 : 5, model == SDFS_MODEL_SSY ? 1 : 3);
+  const long long bytes = batch_sim_lds(d, words, records);
+  if (bytes > BATCH_LDS_MAX) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "tables and %d records need %lld bytes of LDS, one CU has %d", d.N, bytes, BATCH_LDS_MAX);
+    g_create_error = buf;
+    return SDFS_ERR_UNSUPPORTED;
+  }
+  return bytes;
+}
+
+int64_t sdfs_batch_sim_tables(int model, int ndim, const int64_t* shapes, int64_t B, const double* params, const double* const* arrays,
+                              const int64_t* array_sizes, int narrays, const sdfs_batch_sim_desc* d, double* tab_out, double* scal_out,
+                              double* zt_out) {
+  auto no = [](int code, const char* msg) { g_create_error = msg; return (int64_t)code; };
+  BatchDesc D;
+  long long lds = 0;
+  std::string why;
+  const int rc = batch_geometry(model, ndim, shapes, D, &lds, &why);
+  if (rc) { g_create_error = why; return rc; }
+  const int ax_c = model == SDFS_MODEL_SSY ? 1 : 3, ax_lam = model == SDFS_MODEL_SSY ? 0 : 5;
+  const int words = batch_sim_words(D, ax_lam, ax_c);
+  if (!tab_out && !scal_out && !zt_out) return words;
+  if (!params || !arrays || !array_sizes || !d || !tab_out || !scal_out) return no(SDFS_ERR_ARG, "NULL argument");
+  if (B < 1 || narrays < 1 || narrays > 32) return no(SDFS_ERR_ARG, "B or narrays out of range");
+  if (!d->cdf || (!d->start_fixed && !d->cdf0) || (d->has_kappa && !d->kappa)) return no(SDFS_ERR_ARG, "NULL table or kappa in desc");
+  const int nparams = model == SDFS_MODEL_SSY ? 13 : 18;
+  const int nl = D.n[ax_lam], nc = D.n[ax_c];
+  int na3 = 1;
+  for (int a = 0; a < ndim; ++a) if (D.a3s[a] != 0) na3 *= D.n[a];
+  std::vector<double> hl((size_t)B * nl), sg((size_t)B * nc), th((size_t)B), be((size_t)B), ga((size_t)B);
+  for (int64_t b = 0; b < B; ++b) {          // the host fields sdfs_batch_create keeps, by the same code
+    sdfs_handle hh;
+    hh.knobs = read_knobs();
+    const double* arr[32];
+    for (int i = 0; i < narrays; ++i) {
+      if (!arrays[i] || array_sizes[i] < 0) return no(SDFS_ERR_ARG, "arrays[i] is NULL");
+      arr[i] = arrays[i] + (size_t)b * (size_t)array_sizes[i];
+    }
+    ModelTables M;
+    const int frc = fill_model(&hh, model, ndim, shapes, params + (size_t)b * nparams, nparams, arr, array_sizes, narrays, M);
+    if (frc) { g_create_error = hh.err; return frc; }
+    if ((int)hh.sens.hlam.size() != nl || (int)hh.sens.sigc.size() != nc || (int)hh.sens.z.size() != na3) return no(SDFS_ERR_ARG, "state arrays of unexpected size");
+    std::copy(hh.sens.hlam.begin(), hh.sens.hlam.end(), hl.begin() + (size_t)b * nl);
+    std::copy(hh.sens.sigc.begin(), hh.sens.sigc.end(), sg.begin() + (size_t)b * nc);
+    th[b] = hh.theta; be[b] = hh.beta; ga[b] = hh.sens.gamma;
+    if (zt_out)
+      for (int i = 0; i < na3; ++i) zt_out[(size_t)b * na3 + i] = hh.sens.mu_c + hh.sens.z[i];
+  }
+  SimArgs a{};
+  int ncdf = 0, ncdf0 = 0;
+  if (batch_sim_layout(D, ax_lam, ax_c, d, a, &ncdf, &ncdf0) >= 0) return no(SDFS_ERR_ARG, "start is not a state index");
+  batch_sim_stage(D, a, ncdf, ncdf0, words, (int)B, d, hl.data(), sg.data(), th.data(), be.data(), ga.data(), tab_out, scal_out, nullptr);
+  return words;
+}
+
+int sdfs_batch_sim_records_dev(sdfs_batch* h, const double* w_dev, const double* em_dev, const double* v_dev, double* records_dev) {
+  int rc = bcheck(h); if (rc) return rc;
+  if (!w_dev || !em_dev || !records_dev) return bfail(h, SDFS_ERR_ARG, "NULL grid pointer");
+  if (!h->sim_zt) {
+    BHIPCHK(h, hipMalloc((void**)&h->sim_zt, h->muz_host.size() * 8));
+    BHIPCHK(h, hipMemcpy(h->sim_zt, h->muz_host.data(), h->muz_host.size() * 8, hipMemcpyHostToDevice));
+  }
+  const int gx = std::min((h->d.N + 255) / 256, 64);
+  for (int b0 = 0; b0 < h->B; b0 += BSIM_YMAX) {
+    hipLaunchKernelGGL(k_batch_sim_records, dim3(gx, std::min(BSIM_YMAX, h->B - b0)), dim3(256), 0, h->stream, h->d, h->na3, b0,
+                       (const double*)h->sim_zt, w_dev, em_dev, v_dev, records_dev);
+    BHIPCHK(h, hipGetLastError());
+  }
+  return 0;
+}
+
+int sdfs_batch_sim_paths_dev(sdfs_batch* h, const double* records_dev, const sdfs_batch_sim_desc* d, double* stats_dev,
+                             double* moments_dev, uint8_t* idx_dev, double* series_dev) {
+  int rc = bcheck(h); if (rc) return rc;
+  if (!records_dev || !d) return bfail(h, SDFS_ERR_ARG, "NULL records or desc");
+  if (!stats_dev && !moments_dev) return bfail(h, SDFS_ERR_ARG, "stats_dev and moments_dev are both NULL: nothing to write");
+  if (!idx_dev != !series_dev) return bfail(h, SDFS_ERR_ARG, "idx and series are stored together: both NULL or neither");
+  if (d->n_paths < 1 || d->path_offset < 0 || d->path_offset + d->n_paths > (1LL << 32))
+    return bfail(h, SDFS_ERR_ARG, "paths %lld ... %lld: numbers lie in 0 ... 2^32 - 1", (long long)d->path_offset,
+                 (long long)(d->path_offset + d->n_paths - 1));
+  if (d->n_periods < 2 || d->burn_in < 0 || d->burn_in + d->n_periods >= (1LL << 32) - 8)
+    return bfail(h, SDFS_ERR_ARG, "burn_in = %lld, n_periods = %lld: T >= 2 and B + T < 2^32 - 8", (long long)d->burn_in,
+                 (long long)d->n_periods);
+  if (!d->cdf || (!d->start_fixed && !d->cdf0)) return bfail(h, SDFS_ERR_ARG, "NULL cumulative transition table");
+  if (d->has_kappa && !d->kappa) return bfail(h, SDFS_ERR_ARG, "has_kappa needs kappa[B]");
+  if (d->records < 0 || d->records > 2) return bfail(h, SDFS_ERR_ARG, "records = %d: 0 (default), 1 (LDS) or 2 (global)", d->records);
+  const int k = d->lookahead ? d->lookahead : BSIM_K_DEFAULT;
+  if (k != 1 && k != 2 && k != 4) return bfail(h, SDFS_ERR_ARG, "lookahead = %d: 1, 2 or 4", d->lookahead);
+  if (d->search != 0 && d->search != 2)
+    return bfail(h, d->search == 1 ? SDFS_ERR_UNSUPPORTED : SDFS_ERR_ARG, "search = %d: the batch kernels search by bisection (0 or 2)", d->search);
+  if (idx_dev && k != BSIM_K_DEFAULT) return bfail(h, SDFS_ERR_ARG, "stored paths run with the default lookahead");
+  const BatchDesc& D = h->d;
+  const int B = h->B;
+  const int words = batch_sim_words(D, h->ax_lam, h->ax_c);
+  const bool fits = batch_sim_lds(D, words, 1) <= BATCH_LDS_MAX;
+  if (d->records == 1 && !fits)
+    return bfail(h, SDFS_ERR_ARG, "records = 1: tables and %d records need %lld bytes of LDS, one CU has %d", D.N, batch_sim_lds(D, words, 1), BATCH_LDS_MAX);
+  const bool ldsrec = d->records ? d->records == 1 : (fits && BSIM_RECORDS_DEFAULT == 1);
+  const long long G = (d->n_paths + SIM_BLOCK - 1) / SIM_BLOCK;
+  const bool kap = d->has_kappa != 0;
+  const int nstat = 3 * (kap ? 9 : 6) + 1;
+  for (int b = 0; b < B; ++b)
+    if (kap && !(d->skip && d->skip[b]) && !std::isfinite(d->kappa[b])) return bfail(h, SDFS_ERR_ARG, "kappa[%d] is not finite", b);
+
+  // the members' table blocks, scalars and skip flags
+  SimArgs a{};
+  int ncdf = 0, ncdf0 = 0;
+  const int bad = batch_sim_layout(D, h->ax_lam, h->ax_c, d, a, &ncdf, &ncdf0);
+  if (bad >= 0) return bfail(h, SDFS_ERR_ARG, "start[%d] = %d: a state index of axis %d lies in 0 ... %d", bad, d->start[bad], bad, D.n[bad] - 1);
+  // the previous call's uploads read the staging vectors: wait for them (not for the stream's kernels)
+  if (h->sim_staged) BHIPCHK(h, hipEventSynchronize(h->sim_staged));
+  else BHIPCHK(h, hipEventCreateWithFlags(&h->sim_staged, hipEventDisableTiming));
+  auto& tb = h->sim_tab_host;
+  auto& sc = h->sim_scal_host;
+  auto& sk = h->sim_skip_host;
+  tb.resize((size_t)B * words); sc.resize((size_t)B * 4); sk.resize((size_t)B);
+  batch_sim_stage(D, a, ncdf, ncdf0, words, B, d, h->hlam_host.data(), h->sigc_host.data(), h->theta_host.data(), h->beta_host.data(),
+                  h->gam_host.data(), tb.data(), sc.data(), sk.data());
+  const size_t part_need = (size_t)B * nstat * (size_t)G * 3;
+  if ((rc = batch_sim_grow(h, &h->sim_tab, (size_t*)nullptr, tb.size())) || (rc = batch_sim_grow(h, &h->sim_scal, (size_t*)nullptr, sc.size())) ||
+      (rc = batch_sim_grow(h, &h->sim_skip, (size_t*)nullptr, sk.size())) || (rc = batch_sim_grow(h, &h->sim_part, &h->sim_part_cap, part_need)))
+    return rc;
+  hipStream_t st = h->stream;
+  BHIPCHK(h, hipMemcpyAsync(h->sim_tab, tb.data(), tb.size() * 8, hipMemcpyHostToDevice, st));
+  BHIPCHK(h, hipMemcpyAsync(h->sim_scal, sc.data(), sc.size() * 8, hipMemcpyHostToDevice, st));
+  BHIPCHK(h, hipMemcpyAsync(h->sim_skip, sk.data(), sk.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  BHIPCHK(h, hipEventRecord(h->sim_staged, st));
+
+  const batch_sim_fn fn = batch_sim_kernel_for(D.ndim, kap, ldsrec, idx_dev != nullptr, k);
+  const size_t lds = (size_t)batch_sim_lds(D, words, ldsrec ? 1 : 2);
+  if (lds > 64 * 1024) {
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> allowed;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = allowed[{(const void*)fn, h->device}];
+    if (lds > have) {
+      BHIPCHK(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      have = lds;
+    }
+  }
+  BatchSimArgs A;
+  memset(&A, 0, sizeof A);
+  A.s = a; A.tab = h->sim_tab; A.scal = h->sim_scal; A.skip = h->sim_skip; A.rec = records_dev;
+  A.stats = stats_dev; A.part = h->sim_part; A.idx = idx_dev; A.ser = series_dev;
+  A.simwords = words; A.N = D.N;
+  for (int b0 = 0; b0 < B; b0 += BSIM_YMAX) {
+    A.b0 = b0;
+    hipLaunchKernelGGL(fn, dim3((unsigned)G, (unsigned)std::min(BSIM_YMAX, B - b0)), dim3(SIM_BLOCK), lds, st, A);
+    BHIPCHK(h, hipGetLastError());
+  }
+  if (moments_dev) {
+    hipLaunchKernelGGL(k_batch_sim_moments, dim3((B * nstat + 255) / 256), dim3(256), 0, st, B, nstat, (int)G, (const int*)h->sim_skip,
+                       (const double*)h->sim_part, moments_dev);
+    BHIPCHK(h, hipGetLastError());
+  }
+  return 0;
+}
+
 int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap) {
   if (!h || !buf || cap < 1) return SDFS_ERR_ARG;
   std::string s;
@@ -4901,6 +5173,14 @@ int sdfs_batch_describe(const sdfs_batch* h, char* buf, int64_t cap) {
     snprintf(line, sizeof line, "pricing: v, E_M, the point weights, P_n with c_in, c_out (rescaled per stage) and w %s; %d words per problem, tilt tables of %d + %d + %d doubles per stage; at most 2 inner_max + n_max + %d applications per problem\n",
              h->price_reg ? "in registers (the Newton workspace holds them between launches only)" : "in global memory (w in the caller's buffer, seven in the Newton workspace)",
              BP_WORDS, h->d.n[h->ax_lam], h->d.n[h->ax_c], h->na3, 2 * BP_RESTARTS + 11);
+    s += line;
+  }
+  {
+    const int words = batch_sim_words(h->d, h->ax_lam, h->ax_c);
+    const bool fits = batch_sim_lds(h->d, words, 1) <= BATCH_LDS_MAX;
+    const bool ldsrec = fits && BSIM_RECORDS_DEFAULT == 1;
+    snprintf(line, sizeof line, "simulation: one path per lane, %d paths per workgroup, tables of %d doubles in LDS; records %s by default (the LDS form %s: %lld B); moments reduced per workgroup, then in workgroup order\n",
+             SIM_BLOCK, words, ldsrec ? "in LDS" : "gathered from global memory", fits ? "fits" : "does not fit", batch_sim_lds(h->d, words, 1));
     s += line;
   }
   snprintf(buf, (size_t)cap, "%s", s.c_str());

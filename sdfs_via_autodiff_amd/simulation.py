@@ -65,6 +65,40 @@ def _summary(a):
             "p95": float(np.percentile(ok, 95))}
 
 
+def _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol, return_paths, members=1, check_kappa=None):
+    """The checked request of ``simulate`` (and of the batch's): (P, T, B, path_offset, seed, rtol, fixed start or None)."""
+    P = _count(n_paths, "n_paths", 1, 1 << 32)
+    T = _count(n_periods, "n_periods", 2, (1 << 32) - 1)
+    B = _count(burn_in, "burn_in", 0, (1 << 32) - 1)
+    off = _count(path_offset, "path_offset", 0, (1 << 32) - 1)
+    sd = _count(seed, "seed", 0, (1 << 64) - 1)
+    if off + P > 1 << 32:
+        raise ValueError(f"path_offset + n_paths = {off + P} > 2^32: path numbers are 32-bit")
+    if B + T >= 1 << 32:
+        raise ValueError(f"burn_in + n_periods = {B + T} >= 2^32: step numbers are 32-bit")
+    if check_kappa is not None:       # (where ``simulate`` has always checked its kappa: after the counts)
+        check_kappa()
+    rtol = float(rtol)
+    if not (rtol > 0.0 and math.isfinite(rtol)):
+        raise ValueError(f"rtol must be positive, got {rtol!r}")
+    if return_paths and members * P * T > MAX_RETURNED:
+        what = "n_paths * n_periods" if members == 1 else "members * n_paths * n_periods"
+        raise ValueError(f"return_paths: {what} = {members * P * T} > 2^25 path-steps")
+    if isinstance(start, str):
+        if start != "stationary":
+            raise ValueError(f"start must be 'stationary' or one state index per axis, got {start!r}")
+        fixed = None
+    else:
+        fixed = tuple(start)
+        if len(fixed) != len(shapes):
+            raise ValueError(f"start needs one state index per axis ({len(shapes)}), got {len(fixed)}")
+        for a, (s, n) in enumerate(zip(fixed, shapes)):
+            if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < n:
+                raise ValueError(f"start[{a}] = {s!r}: a state index of axis {a} lies in 0 ... {n - 1}")
+        fixed = tuple(int(s) for s in fixed)
+    return P, T, B, off, sd, rtol, fixed
+
+
 def simulate(model, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, path_offset=0, start="stationary",
              kappa=None, rtol=1e-10, return_paths=False):
     """Simulate ``n_paths`` paths (numbered path_offset … path_offset + n_paths − 1) of ``n_periods`` recorded steps
@@ -80,33 +114,9 @@ def simulate(model, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, pa
     import torch
     kind, shapes = _shapes(model, shapes)
     _check_grid(w_star, shapes, "w_star")
-    P = _count(n_paths, "n_paths", 1, 1 << 32)
-    T = _count(n_periods, "n_periods", 2, (1 << 32) - 1)
-    B = _count(burn_in, "burn_in", 0, (1 << 32) - 1)
-    off = _count(path_offset, "path_offset", 0, (1 << 32) - 1)
-    sd = _count(seed, "seed", 0, (1 << 64) - 1)
-    if off + P > 1 << 32:
-        raise ValueError(f"path_offset + n_paths = {off + P} > 2^32: path numbers are 32-bit")
-    if B + T >= 1 << 32:
-        raise ValueError(f"burn_in + n_periods = {B + T} >= 2^32: step numbers are 32-bit")
+    P, T, B, off, sd, rtol, fixed = _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol,
+                                             return_paths, check_kappa=lambda: kappa is None or _kappa(kappa))
     k = None if kappa is None else _kappa(kappa)
-    rtol = float(rtol)
-    if not (rtol > 0.0 and math.isfinite(rtol)):
-        raise ValueError(f"rtol must be positive, got {rtol!r}")
-    if return_paths and P * T > MAX_RETURNED:
-        raise ValueError(f"return_paths: n_paths * n_periods = {P * T} > 2^25 path-steps")
-    if isinstance(start, str):
-        if start != "stationary":
-            raise ValueError(f"start must be 'stationary' or one state index per axis, got {start!r}")
-        fixed = None
-    else:
-        fixed = tuple(start)
-        if len(fixed) != len(shapes):
-            raise ValueError(f"start needs one state index per axis ({len(shapes)}), got {len(fixed)}")
-        for a, (s, n) in enumerate(zip(fixed, shapes)):
-            if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < n:
-                raise ValueError(f"start[{a}] = {s!r}: a state index of axis {a} lies in 0 ... {n - 1}")
-        fixed = tuple(int(s) for s in fixed)
     if isinstance(w_star, torch.Tensor):
         w_ok = bool(torch.all(w_star > 1.0))
     else:
