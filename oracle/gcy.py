@@ -144,7 +144,8 @@ def kfactor_gcy(a2, a3):
 
 def T_gcy_factorised(w, shapes, params, arrays):
     beta, theta, a1, a2, a3, zQ, zpQ, Qhz, Qhc, Qhzp, Qhl = _pieces(params, arrays)
-    w = np.asarray(w, dtype=np.float64)
+    w = np.asarray(w)
+    w = w.astype(np.result_type(w.dtype, np.float64), copy=False)   # a complex w stays complex (complex-step tests)
     S = expect_gcy(a1 * w ** theta, (zQ, zpQ, Qhz, Qhc, Qhzp, Qhl))
     return 1 + beta * (kfactor_gcy(a2, a3) * S) ** (1 / theta)
 

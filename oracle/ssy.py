@@ -111,7 +111,8 @@ def expect_ssy_T(y, arrays_Q):
 
 def T_ssy_factorised(w, shapes, params, arrays):
     beta, theta, a1, a2, a3, Ql, Qc, Qz, zQ = _pieces(params, arrays)
-    w = np.asarray(w, dtype=np.float64)
+    w = np.asarray(w)
+    w = w.astype(np.result_type(w.dtype, np.float64), copy=False)   # a complex w stays complex (complex-step tests)
     x = a1[:, None, None, None] * w ** theta
     S = expect_ssy(x, (Ql, Qc, Qz, zQ))
     K = a2[None, :, None, None] * a3[None, None, :, :]

@@ -22,6 +22,9 @@ Fixtures written (tests/golden/):
       at w = exp(default_rng(0).standard_normal(shapes)) and at w = 800
   sa_*.npz  : successive_approx fixed points + iteration counts + error traces
   sandpit_trace.npz : the recorded Newton trace of sandpit.ipynb:41-44 (typed in)
+  cal_<name>_ssy_2x3x4x5.npz, cal_<name>_gcy_2x3x2x3x2x3.npz : the same operator fixture with the reference's
+      models constructed at the six calibrations of tests/calibrations.py (written with fixed zip timestamps:
+      regenerating them gives the same bytes)
 """
 import io
 import os
@@ -155,6 +158,8 @@ def main():
         np.savez_compressed(os.path.join(HERE, f"gcy_{tag(shapes)}.npz"), **out)
         print("gcy", shapes, "ok")
 
+    calibration_fixtures(S, G)
+
     # --- successive-approximation fixed points via the reference's own loop ---
     def run_sa(T, shapes, tol):
         errs = []
@@ -225,6 +230,44 @@ def main():
     print("done")
 
 
+def save_npz_fixed(path, **arrays):
+    """np.savez_compressed stamps each member with the current time; this writes the same archive with the zip
+    format's epoch instead, members in the order given."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for name, a in arrays.items():
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with zf.open(info, "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
+
+
+def calibration_fixtures(S, G):
+    """The reference's SSY(...) / GCY(...) at the calibrations of tests/calibrations.py: params tuple, discretize_*,
+    T(w) vectorised and by loops at w = exp(default_rng(0).standard_normal(shapes))."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import calibrations as C
+    for kind, cls, disc, T, Tloops, names, shapes in [
+            ("ssy", S.SSY, S.discretize_ssy, S.T_ssy, S.T_ssy_loops, SSY_ARR, (2, 3, 4, 5)),
+            ("gcy", G.GCY, G.discretize_gcy, G.T_gcy, G.T_gcy_loops, GCY_ARR, (2, 3, 2, 3, 2, 3))]:
+        default = cls()
+        for name in C.NAMES:
+            # `shifted` scales the reference's own defaults, read off its default instance
+            fields = list(C.SHIFT_SSY if kind == "ssy" else C.SHIFT_GCY)
+            defaults = {k: getattr(default, g) for k, g in zip(fields, C.greek(dict.fromkeys(fields)))}
+            model = cls(**C.greek(C.overrides(kind, name, defaults)))
+            arrays = disc(model, shapes)
+            out = {"params": np.array(model.params), "shapes": np.array(shapes)}
+            out.update({"arr_" + n: np.asarray(a) for n, a in zip(names, arrays)})
+            wr = w_random(shapes)
+            out["w_rand"] = wr
+            out["T_rand"] = np.asarray(T(wr, shapes, model.params, arrays))
+            out["Tloops_rand"] = np.asarray(Tloops(wr, shapes, model.params, arrays))
+            save_npz_fixed(os.path.join(HERE, f"cal_{name}_{kind}_{tag(shapes)}.npz"), **out)
+            print("cal", name, kind, float(out["T_rand"].flat[0]), float(np.max(np.abs(out["T_rand"] - out["Tloops_rand"]))))
+
+
 def dense_fixtures(S, ssy):
     """temp_ssy.py has no import lines (it was cut out of a notebook): its text is executed as it
     stands in a namespace that supplies the names it expects -- numpy, the jax stand-ins, njit, and
@@ -292,4 +335,7 @@ def continuous_fixtures(ssy, gcy):
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["calibrations"]:          # the cal_* fixtures alone
+        calibration_fixtures(*import_reference()[:2])
+    else:
+        main()

@@ -118,9 +118,13 @@ def assert_same_member(x, bx, y, by, per_path=True, paths=True):
 @pytest.mark.parametrize("burn_in", [0, 7])
 @pytest.mark.parametrize("kappa", [None, 2.0])
 def test_every_member_matches_the_twin(S, kind, shapes, start, burn_in, kappa):
+    every_member_matches_the_twin(S, kind, shapes, start, burn_in, kappa, family(S, kind), solved(S, kind, shapes))
+
+
+def every_member_matches_the_twin(S, kind, shapes, start, burn_in, kappa, models, w):
+    """The body of test_every_member_matches_the_twin on any batch of models at their fixed points w; returns what
+    BatchOperator.simulate returned and the largest measured value of each of the three bounds (1e-12, 1e-10, 1e-9)."""
     from sdfs_via_autodiff_amd.simulation import cdf_tables
-    models = family(S, kind)
-    w = solved(S, kind, shapes)
     st = None if start == "stationary" else tuple(n // 2 for n in shapes)
     disc = S.discretize_ssy if kind == "ssy" else S.discretize_gcy
     op = S.BatchOperator.from_models(models, shapes)
@@ -133,7 +137,8 @@ def test_every_member_matches_the_twin(S, kind, shapes, start, burn_in, kappa):
     assert np.all(r["status"] == 0), r["status"]
     names = r["series"]
     ns = len(names)
-    assert r["index"].shape == (6, P, T + 1, len(shapes)) and r["index"].dtype == np.uint8
+    worst = {"series": 0.0, "statistics, two-pass": 0.0, "statistics, twin": 0.0}
+    assert r["index"].shape == (len(models), P, T + 1, len(shapes)) and r["index"].dtype == np.uint8
     for b, m in enumerate(models):
         arr = disc(m, shapes)
         cdf, cdf0 = cdf_tables(m, shapes, arr)
@@ -144,6 +149,7 @@ def test_every_member_matches_the_twin(S, kind, shapes, start, burn_in, kappa):
         assert names == tuple(ser)
         for i, nm in enumerate(names):
             got = r["paths"][b, i]
+            worst["series"] = max(worst["series"], close(got, ser[nm], 1.0))
             assert close(got, ser[nm], 1.0) <= 1e-12, (b, nm, close(got, ser[nm], 1.0))
             # the device's one-pass sums against the two-pass formulas on the device's own series (a mean is measured
             # against 1e-3 of the path's largest |value|, an ac1 against at least 0.01), then against the twin's
@@ -151,9 +157,13 @@ def test_every_member_matches_the_twin(S, kind, shapes, start, burn_in, kappa):
             floor_mean = 1e-3 * np.max(np.abs(got), axis=1)
             for j, (ref, floor) in enumerate(((mean, floor_mean), (sd, 0.0), (ac1, 1e-2))):
                 a = r["stats"][b, 3 * i + j]
+                worst["statistics, two-pass"] = max(worst["statistics, two-pass"], rel_err(a, ref, floor))
+                worst["statistics, twin"] = max(worst["statistics, twin"], close(a, stats[nm][STATS[j]], 1.0))
                 assert rel_err(a, ref, floor) <= 1e-10, (b, nm, STATS[j], rel_err(a, ref, floor))
                 assert close(a, stats[nm][STATS[j]], 1.0) <= 1e-9, (b, nm, STATS[j])
+        worst["statistics, twin"] = max(worst["statistics, twin"], close(r["stats"][b, 3 * ns], stats["slope"], 1.0))
         assert close(r["stats"][b, 3 * ns], stats["slope"], 1.0) <= 1e-9, b
+    return r, worst
 
 
 # -- (2) against simulate ---------------------------------------------------------------------------------------------------

@@ -104,9 +104,9 @@ def hook(op, mode, wd, v32, m):
     return host.astype(np.float64), names
 
 
-def jvp_forms(S, model, shapes, inputs, expect, knobs, tensors=None, modes=(1, 2, 3)):
+def jvp_forms(S, model, shapes, inputs, expect, knobs, tensors=None, modes=(1, 2, 3), fixed_point=True):
     """expect: "mfma" (the pair plan's fp32-MFMA kernels run in mode 3), "pair32" (pair plan, fp32 storage kernels, no
-    MFMA) or "generic" (the generic fp32 passes)."""
+    MFMA) or "generic" (the generic fp32 passes).  fixed_point=False: w from wbench only, no Newton solve first."""
     import torch
     params, arr = tensors or model_inputs(S, model, shapes, inputs)
     op = build(S, model, shapes, params, arr, **knobs)
@@ -117,13 +117,16 @@ def jvp_forms(S, model, shapes, inputs, expect, knobs, tensors=None, modes=(1, 2
     else:
         assert PAIR in desc and lines, desc
     ref = oracle(model, shapes, params, arr)
-    x, _, info = op.solve(np.full(shapes, 800.0), "newton", tol=1e-8)
-    assert info["status"] == 0
+    points = [("wbench", wbench(shapes))]
+    if fixed_point:
+        x, _, info = op.solve(np.full(shapes, 800.0), "newton", tol=1e-8)
+        assert info["status"] == 0
+        points.append(("fixed point", x))
     rng = np.random.default_rng(11)
     v32 = rng.standard_normal(shapes).astype(np.float32)
     v = v32.astype(np.float64)
     worst = {}
-    for wname, w in (("wbench", wbench(shapes)), ("fixed point", x)):
+    for wname, w in points:
         wd = torch.from_numpy(np.ascontiguousarray(w)).cuda()
         jv = ref.jvp(w, v)
         jabs = ref.jvp(w, np.abs(v))
@@ -355,10 +358,17 @@ def test_t_f32_one_application(S, model, shapes, inputs):
     fp32 middle pass unstreamed (SDFS_NO_F32_STREAM=1) and, on GCY, with a3 gathered by the last pass (z states that
     break its two-table form, given to the handle and the oracle alike; SSY's a3 does not vary along the last pass's
     pair, so its two tables always hold)."""
-    params, arr0 = model_inputs(S, model, shapes, inputs)
-    theta = (S.SSY() if model == "ssy" else S.GCY()).θ
+    t32_one_application(S, model, shapes, inputs)
+
+
+def t32_one_application(S, model, shapes, inputs, tensors=None, theta=None):
+    """The body of test_t_f32_one_application; tensors = (params, arrays) and theta of another model than the default."""
+    params, arr0 = tensors or model_inputs(S, model, shapes, inputs)
+    if theta is None:
+        theta = (S.SSY() if model == "ssy" else S.GCY()).θ
     w = wbench(shapes)
     want = {}
+    worst = 0.0
     for knobs, gathered in T32_CASES:
         if gathered and model != "gcy":
             continue
@@ -382,6 +392,8 @@ def test_t_f32_one_application(S, model, shapes, inputs):
         assert np.max(err) > 0, what
         assert abs(info["final_err"] - want_res) <= float(np.max(lim)), (what, info["final_err"], want_res)
         report(f"t_f32 {what} max err / bound", float(np.max(err / lim)))
+        worst = max(worst, float(np.max(err / lim)))
+    return worst
 
 
 @limit(120)

@@ -150,8 +150,14 @@ def assert_plan(op, marker):
 @limit(900)
 @pytest.mark.parametrize("kind,shapes,plan,marker,c_oracle", PLAN_CASES, ids=PLAN_IDS)
 def test_tilted_product_vs_oracle(S, kind, shapes, plan, marker, c_oracle):
-    m = model_of(S, kind)
+    tilted_product_case(S, kind, shapes, plan, marker, c_oracle)
+
+
+def tilted_product_case(S, kind, shapes, plan, marker, c_oracle, m=None):
+    """The body of test_tilted_product_vs_oracle; m: another model than the default.  Returns the worst relative error."""
+    m = m or model_of(S, kind)
     arr = disc(S, kind)(m, shapes)
+    worst = 0.0
     op = make_op(S, kind, shapes, m, arr, plan)
     assert_plan(op, marker)
     rng = np.random.default_rng(sum(shapes))
@@ -170,7 +176,9 @@ def test_tilted_product_vs_oracle(S, kind, shapes, plan, marker, c_oracle):
             want = folded_K(kind, shapes, m, arr, w, f, p, kl, kc, Tw=Tw)
         rel = np.max(np.abs(got - want) / np.abs(want))
         assert rel <= 1e-12, f"{kind} {shapes} tilt {(p, kl, kc)}: {rel:.3e}"
+        worst = max(worst, float(rel))
     op.close()
+    return worst
 
 
 @limit(900)

@@ -59,13 +59,14 @@ def model_of(S, kind):
 _W = {}
 
 
-def fixed_point(S, kind, shapes):
-    """A tight Newton fixed point on the operator simulation.py uses (cached per grid)."""
+def fixed_point(S, kind, shapes, m=None, tag=None):
+    """A tight Newton fixed point on the operator simulation.py uses (cached per grid; m, tag: another model than the
+    default and its name in the cache)."""
     import torch
     from sdfs_via_autodiff_amd import sensitivity as sens
-    key = (kind, tuple(shapes))
+    key = (kind, tuple(shapes)) if m is None else (kind, tuple(shapes), tag)
     if key not in _W:
-        m = model_of(S, kind)
+        m = m or model_of(S, kind)
         op, _ = sens._operator(m, shapes)
         w = torch.full(shapes, 800.0, dtype=torch.float64, device="cuda")
         _, info = op.solve_dev(w.data_ptr(), "newton", tol=1e-10, inner_rtol=1e-12, inner_atol=0.0)
@@ -76,9 +77,9 @@ def fixed_point(S, kind, shapes):
     return _W[key]
 
 
-def twin(S, kind, shapes, w, kappa, **kw):
+def twin(S, kind, shapes, w, kappa, m=None, **kw):
     from sdfs_via_autodiff_amd.simulation import cdf_tables
-    m = model_of(S, kind)
+    m = m or model_of(S, kind)
     arr = (S.discretize_ssy if kind == "ssy" else S.discretize_gcy)(m, shapes)
     cdf, cdf0 = cdf_tables(m, shapes, arr)
     em = S.sdf_moments(m, shapes, w)["E_M"]
@@ -105,19 +106,26 @@ GRIDS = [("ssy", (3, 4, 5, 6)), ("ssy", (15, 15, 15, 15)), ("ssy", (5, 4, 6, 7))
 @pytest.mark.parametrize("burn_in", [0, 7])
 @pytest.mark.parametrize("kappa", [None, 2.0])
 def test_paths_series_and_statistics_match_the_twin(S, kind, shapes, start, burn_in, kappa):
-    m = model_of(S, kind)
-    w = fixed_point(S, kind, shapes)
+    paths_series_and_statistics_case(S, kind, shapes, start, burn_in, kappa)
+
+
+def paths_series_and_statistics_case(S, kind, shapes, start, burn_in, kappa, m=None, tag=None):
+    """The body of test_paths_series_and_statistics_match_the_twin; m, tag: another model than the default."""
+    w = fixed_point(S, kind, shapes, m, tag)
+    m = m or model_of(S, kind)
     st = None if start == "stationary" else tuple(n // 2 for n in shapes)
     P, T, seed = 1000, 64, 0x9E3779B97F4A7C15
     out = S.simulate(m, shapes, w, P, T, burn_in=burn_in, seed=seed, path_offset=123,
                      start="stationary" if st is None else st, kappa=kappa, return_paths=True)
-    idx, ser, stats = twin(S, kind, shapes, w, kappa, seed=seed, path_offset=123, n_paths=P, burn_in=burn_in,
+    idx, ser, stats = twin(S, kind, shapes, w, kappa, m=m, seed=seed, path_offset=123, n_paths=P, burn_in=burn_in,
                            n_periods=T, start=st)
     got = out["paths"]
     assert got["index"].shape == (P, T + 1, len(shapes)) and got["index"].dtype == np.uint8
     assert np.array_equal(got["index"], idx), f"{np.sum(got['index'] != idx)} index entries differ"
     assert out["series"] == tuple(ser)
+    worst = {"series": 0.0, "statistics, two-pass": 0.0, "statistics, twin": 0.0}
     for nm in out["series"]:
+        worst["series"] = max(worst["series"], close(got[nm], ser[nm], 1.0))
         assert close(got[nm], ser[nm], 1.0) <= 1e-12, (nm, close(got[nm], ser[nm], 1.0))
     # statistics: the device's one-pass sums against the two-pass formulas on the device's own series (relative
     # error; a mean is measured against 1e-3 of the path's largest |value|, an ac1 or a slope against at least 0.01)
@@ -127,9 +135,13 @@ def test_paths_series_and_statistics_match_the_twin(S, kind, shapes, start, burn
         floor_mean = 1e-3 * np.max(np.abs(got[nm]), axis=1)
         for a, b, floor, what in ((pp["mean"], mean, floor_mean, "mean"), (pp["std"], sd, 0.0, "std"),
                                   (pp["ac1"], ac1, 1e-2, "ac1")):
+            worst["statistics, two-pass"] = max(worst["statistics, two-pass"], rel_err(a, b, floor))
+            worst["statistics, twin"] = max(worst["statistics, twin"], close(a, stats[nm][what], 1.0))
             assert rel_err(a, b, floor) <= 1e-10, (nm, what, rel_err(a, b, floor))
             assert close(a, stats[nm][what], 1.0) <= 1e-9, (nm, what)     # and the twin's (its own series)
+    worst["statistics, twin"] = max(worst["statistics, twin"], close(out["per_path"]["slope"], stats["slope"], 1.0))
     assert close(out["per_path"]["slope"], stats["slope"], 1.0) <= 1e-9
+    return worst          # largest measured value of each of the three bounds (1e-12, 1e-10, 1e-9)
 
 
 def rel_err(a, b, floor):

@@ -79,6 +79,25 @@ def test_discretize_gcy_matches_reference(shapes):
         np.testing.assert_allclose(a, b, rtol=1e-14, atol=0)
 
 
+@pytest.mark.parametrize("name", ["steep", "shallow", "positive", "fractional", "linear", "shifted"])
+@pytest.mark.parametrize("kind,shapes", [("ssy", (2, 3, 4, 5)), ("gcy", (2, 3, 2, 3, 2, 3))])
+def test_models_and_discretisation_at_other_calibrations(kind, shapes, name):
+    """The host mirror at the calibrations of tests/calibrations.py: params equal to the reference's tuple, theta from
+    the model's own gamma and psi, discretisation to the reference's arrays (tests/golden/cal_*.npz)."""
+    import sdfs_via_autodiff_amd as S
+    import calibrations as C
+    g = load_golden(f"cal_{name}_{kind}_{tag(shapes)}.npz")
+    m = C.package_model(S, kind, name)
+    assert np.array_equal(np.array(m.params), g["params"])
+    assert m.θ == (1 - m.γ) / (1 - 1 / m.ψ) and abs(m.θ - C.theta(kind, name)) <= 1e-15 * abs(m.θ)
+    got = (S.discretize_ssy if kind == "ssy" else S.discretize_gcy)(m, shapes)
+    want = golden_arrays(g, kind)
+    assert len(got) == len(want)
+    for a, b in zip(got, want):
+        assert a.shape == b.shape and a.dtype == np.float64
+        np.testing.assert_allclose(a, b, rtol=1e-14, atol=0)
+
+
 def test_rouwenhorst_rows_sum_to_one_and_moments():
     import sdfs_via_autodiff_amd as S
     mc = S.rouwenhorst(9, 0.9, 0.3, 0.2)
