@@ -465,8 +465,9 @@ int sdfs_batch_solve_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_d
  * 1 max_iter reached (max_iter < 1: before any application), 2 the iterate, a step or an inner product left the finite
  * range or an iterate has a point <= 0.  The eight vectors of a problem live in registers up to 2048 grid points and in
  * global memory beyond (sdfs_batch_describe says which): the handle allocates 7 N doubles per problem at its first
- * Newton solve, at most 2 GiB -- a larger batch runs group after group.  A problem's w, counts and error depend on its
- * own inputs only: not on B, its position in the batch or check_every.  Returns when every problem has stopped. */
+ * Newton solve, at most 2 GiB (or the bytes the environment variable SDFS_BATCH_WS_MAX named at sdfs_batch_create) -- a
+ * larger batch runs group after group.  A problem's w, counts and error depend on its own inputs only: not on B, its
+ * position in the batch or check_every.  Returns when every problem has stopped. */
 int sdfs_batch_newton_dev(sdfs_batch* h, const sdfs_opts* opts, double* w_inout_dev, int64_t* n_iter, int64_t* n_apply,
                           double* final_err, int32_t* status);
 

@@ -518,6 +518,23 @@ def _kind_of(models):
     raise TypeError("models must be all SSY or all GCY instances")
 
 
+def _batch_request(models, shapes, *w_star):
+    """What every ``*_batch`` call opens with: (models as a list, kind, shapes as a tuple of ints, ndim, B, w) with the
+    axes counted and, where ``w_star`` is passed, w = w_star as a float64 array of shape (B, *shapes), else None."""
+    models, kind = _kind_of(models)
+    shapes = tuple(int(s) for s in shapes)
+    ndim = _KINDS[kind][1]
+    if len(shapes) != ndim:
+        raise ValueError(f"{kind} grids have {ndim} axes, got shapes {shapes}")
+    B = len(models)
+    if not w_star:
+        return models, kind, shapes, ndim, B, None
+    w = _as_f64(w_star[0])
+    if w.shape != (B,) + shapes:
+        raise ValueError(f"w_star has shape {w.shape}, the batch is {(B,) + shapes}")
+    return models, kind, shapes, ndim, B, w
+
+
 def _start_values(w0, B, shapes):
     if w0 is None:
         return np.full((B,) + shapes, 800.0)               # the reference's drivers start from 800 everywhere
@@ -540,12 +557,7 @@ def solve_batch(models, shapes, w0=None, tol=1e-7, max_iter=10**6, method="rouwe
     _check_algorithm(algorithm)
     newton = algorithm == "newton"
     inner = dict(inner_rtol=inner_rtol, inner_atol=inner_atol, inner_max_iter=inner_max_iter) if newton else {}
-    models, kind = _kind_of(models)
-    shapes = tuple(int(s) for s in shapes)
-    ndim = _KINDS[kind][1]
-    if len(shapes) != ndim:
-        raise ValueError(f"{kind} grids have {ndim} axes, got shapes {shapes}")
-    B = len(models)
+    models, kind, shapes, ndim, B, _ = _batch_request(models, shapes)
     w = _start_values(w0, B, shapes)
     disc = discretize_ssy if kind == "ssy" else discretize_gcy
     if batch_lds_bytes(kind, shapes) is not None:
@@ -596,15 +608,7 @@ def gradient_batch(models, shapes, w_star, g, rtol=1e-10, atol=0.0, persistence=
     from . import sensitivity as sens
     if method != "rouwenhorst":
         raise ValueError(f"parameter tangents are implemented for Rouwenhorst grids only, not {method!r}")
-    models, kind = _kind_of(models)
-    shapes = tuple(int(s) for s in shapes)
-    ndim = _KINDS[kind][1]
-    if len(shapes) != ndim:
-        raise ValueError(f"{kind} grids have {ndim} axes, got shapes {shapes}")
-    B = len(models)
-    w = _as_f64(w_star)
-    if w.shape != (B,) + shapes:
-        raise ValueError(f"w_star has shape {w.shape}, the batch is {(B,) + shapes}")
+    models, kind, shapes, ndim, B, w = _batch_request(models, shapes, w_star)
     g = _grid_or_batch(g, B, shapes, "g")
     _, supported, _, _, allp = sens._kind(models[0])
     names = tuple(allp if persistence else supported)
@@ -747,15 +751,7 @@ def price_batch(models, shapes, w_star, kappa=None, n_max=0, kappa_ts=0.0, weigh
     Shapes beyond one CU run ``sdf_moments``, ``claim_prices`` and ``term_structure`` member by member
     (``plan == "loop"``).  Returns a BatchPrices."""
     from . import pricing
-    models, kind = _kind_of(models)
-    shapes = tuple(int(s) for s in shapes)
-    ndim = _KINDS[kind][1]
-    if len(shapes) != ndim:
-        raise ValueError(f"{kind} grids have {ndim} axes, got shapes {shapes}")
-    B = len(models)
-    w = _as_f64(w_star)
-    if w.shape != (B,) + shapes:
-        raise ValueError(f"w_star has shape {w.shape}, the batch is {(B,) + shapes}")
+    models, kind, shapes, ndim, B, w = _batch_request(models, shapes, w_star)
     n_max = _check_n_max(n_max)
     rtol, atol = _check_rtol(rtol, atol)
     kap = _per_member(kappa, B, "kappa", optional=True)
@@ -878,15 +874,7 @@ def simulate_batch(models, shapes, w_star, n_paths, n_periods, *, burn_in=0, see
     series (B·P·T <= 2^25).  Shapes beyond one CU run ``simulate`` member by member (``plan == "loop"``), the moments
     formed on the host.  Returns a BatchSimulation."""
     from . import simulation as sim
-    models, kind = _kind_of(models)
-    shapes = tuple(int(s) for s in shapes)
-    ndim = _KINDS[kind][1]
-    if len(shapes) != ndim:
-        raise ValueError(f"{kind} grids have {ndim} axes, got shapes {shapes}")
-    B = len(models)
-    w = _as_f64(w_star)
-    if w.shape != (B,) + shapes:
-        raise ValueError(f"w_star has shape {w.shape}, the batch is {(B,) + shapes}")
+    models, kind, shapes, ndim, B, w = _batch_request(models, shapes, w_star)
     P, T, Bn, off, sd, rtol, fixed = sim._request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol, return_paths,
                                                   members=B)
     records = _check_records(records)
