@@ -36,9 +36,6 @@ namespace sdfs {
 constexpr int MAXF = 5;   // block-fixed axis slots
 constexpr int MAXN = 32;  // max extent of a contracted axis (2 MFMA row tiles, 8 k-steps)
 
-enum { PRO_NONE = 0, PRO_POW = 1, PRO_POW_LIN = 2, PRO_MUL = 3 };
-enum { EPI_NONE = 0, EPI_CES = 1, EPI_CES_LIN = 2, EPI_MUL = 3 };
-
 struct PassDesc {
   // block-fixed axes (slowest first)
   int nfixed;
@@ -60,8 +57,8 @@ struct PassDesc {
   int qlds[3];                 // LDS offset (doubles) of step s's staged Q matrix
   const double* Q[3];
   // elementwise stages
-  int pro, epi;
-  int minus_identity;          // EPI_MUL: subtract old[idx]
+  int pro, epi;                // unused (always 0; kept so that the kernels' argument layout stays put): the kernel's MODE says it
+  int minus_identity;          // M_JLAST: subtract old[idx]
   double theta, inv_theta, beta;
   // current-state scale a3 applied by the aggregator instead of being folded into the z tensor: set
   // when every slice of a conditional tensor is the same matrix (Rouwenhorst / Tauchen chains), which
@@ -77,14 +74,14 @@ struct PassDesc {
 struct PassIO {
   const double* in;        // grid read by the prologue
   double* out;             // grid written by the epilogue
-  const double* aux_in;    // PRO_MUL: c1;  EPI_MUL: c2
-  double* aux_out;         // PRO_POW_LIN: c1;  EPI_CES_LIN: c2
-  const double* old;       // EPI_CES: w (for the residual);  EPI_MUL: v
-  unsigned long long* resid;        // EPI_CES: atomicMax target (bits of a non-negative double) or null
+  const double* aux_in;    // M_JFIRST: c1;  M_JLAST: c2
+  double* aux_out;         // M_TFIRST_LIN: c1;  M_TLAST_LIN: c2
+  const double* old;       // M_TONLY / M_TLAST / M_TLAST_LIN: w (for the residual);  M_JLAST: v
+  unsigned long long* resid;        // M_TONLY / M_TLAST / M_TLAST_LIN: atomicMax target (bits of a non-negative double) or null
   const unsigned long long* gate;   // if non-null and *gate <= tol bits: the iteration has converged, do nothing
   double gate_tol;
   unsigned long long* dbg;          // diagnostic builds (-DSDFS_STAMP): per-phase s_memtime stamps
-  double* dotp;                     // EPI_MUL with minus_identity: per-block partial sums of <out, v> and <out, out>
+  double* dotp;                     // M_JLAST with minus_identity: per-block partial sums of <out, v> and <out, out>
                                     // (BiCGSTAB's <t, s>, <t, t>: s is in registers anyway), [2][ntiles], or null
 };
 

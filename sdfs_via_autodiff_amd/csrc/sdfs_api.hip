@@ -620,31 +620,76 @@ struct Apply {
   bool f32() const { return prec == PREC_F32 || prec == PREC_BF16 || prec == PREC_MFMA32; }   // fp32 Krylov storage
 };
 
-// counter, timing scope, launch and error check of one kernel of a plan (counter name "<tag>:<label>")
-template <typename Desc, typename IO>
-int launch_kernel(sdfs_handle* h, const void* fn, unsigned grid, int block, size_t lds, const Desc& d, const IO& io,
-                  const char* tag, const std::string& label, double bytes, double flops) {
+// What one launch is counted as: a plain name, or "<tag>:<sub><label>" for a pass of a plan.  Only pointers are kept:
+// the name is put together when profiling is on, never on the plain launch path.
+struct Counter {
+  const char* tag; const char* sub; const std::string* label; double bytes, flops;
+  Counter(const char* name, double bytes_, double flops_) : tag(name), sub(""), label(nullptr), bytes(bytes_), flops(flops_) {}
+  Counter(const char* tag_, const std::string& label_, double bytes_, double flops_, const char* sub_ = "")
+      : tag(tag_), sub(sub_), label(&label_), bytes(bytes_), flops(flops_) {}
+};
+
+// counter, timing scope, launch on the handle's stream and error check of one kernel
+template <typename... P, typename... A>
+int launch_kernel(sdfs_handle* h, void (*fn)(P...), dim3 grid, dim3 block, size_t lds, const Counter& c, A&&... args) {
   int cid = -1;
   if (h->profiling) {
     char nm[48];
-    snprintf(nm, sizeof nm, "%s:%s", tag, label.c_str());
-    cid = counter_id(h, nm, bytes, flops);
+    if (c.label) snprintf(nm, sizeof nm, "%s:%s%s", c.tag, c.sub, c.label->c_str());
+    cid = counter_id(h, c.label ? nm : c.tag, c.bytes, c.flops);
   }
   ProfScope ps(h, cid);
-  hipLaunchKernelGGL((void (*)(const Desc, const IO))fn, dim3(grid), dim3(block), lds, h->stream, d, io);
+  hipLaunchKernelGGL(fn, grid, block, lds, h->stream, static_cast<P>(args)...);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
-int launch_pass(sdfs_handle* h, Pass& P, int pro, int epi, const PassIO& io, int minus_identity,
-                const char* tag, double bytes, int prec = 0, bool transposed = false) {
+// What pass i of a plan launches for a request: kernel, geometry, counter.  select_pass (below) is the one place that picks
+// the form of a pass -- run_passes launches it, sdfs_describe_plan prints it, the fused dot products of BiCGSTAB size their
+// partial sums by its grid.
+struct PassLaunch {
+  const void* fn = nullptr;          // (generic tiles: null -- VEC and EPT follow the pointers' alignment, launch_pass)
+  unsigned grid = 0;
+  int block = 256;
+  size_t lds = 0;
+  double bytes = 0;                  // algorithmic bytes of the counter
+  const char* tag = "";              // counter name "<tag>:<pass label>"
+  int kmode = 0;                     // the kernel's mode: M_* (generic tiles), S_* (slice passes), SM_* (small grid), L_* (line passes)
+  bool f32 = false;                  // generic tiles: the pass runs in fp32 storage
+  bool jfused = false;               // first pass with BiCGSTAB's p / s update (JFusedIO, JFused32IO with m32)
+  bool m32 = false;                  // fp32-MFMA form (f32_kernels.hpp, krylov_kernels.hpp)
+  bool persistent = false;           // ... its persistent middle pass, next tile in flight
+  bool push = false;                 // T's streamed last pass with the Anderson push
+  const double* dot_with = nullptr;  // J.v's last pass also sums <out, dot_with>
+  const char* err = nullptr;         // no kernel for this pass
+  int err_code = SDFS_ERR_UNSUPPORTED;
+};
+
+// ... and its launch: pass P (a Pass or a FastPass) with the kernel's descriptor and streams
+template <typename AnyPass, typename Desc, typename IO>
+int launch_selected(sdfs_handle* h, const PassLaunch& L, const AnyPass& P, const Desc& d, const IO& io) {
+  return launch_kernel(h, (void (*)(const Desc, const IO))L.fn, dim3(L.grid), dim3(L.block), L.lds,
+                       Counter(L.tag, P.label, L.bytes, P.flops), d, io);
+}
+
+// VEC and EPT of a generic pass: 16-byte accesses where the tile allows them and every grid pointer is aligned, float4
+// accesses for the fp32 streams of a J.v pass
+struct TileForm { int vec, ept; };
+TileForm tile_form(const Pass& P, bool aligned, bool f32_jv) {
+  const bool v2 = P.vec2 && aligned, v4 = v2 && P.vec4 && f32_jv;
+  return {v4 ? 4 : (v2 ? 2 : 1), v4 ? P.ept4 : (v2 ? P.ept2 : P.ept1)};
+}
+
+// one pass on the generic tiles (pass_kernel.hpp) in the kernel mode L.kmode
+int launch_pass(sdfs_handle* h, const Pass& P, PassLaunch L, const PassIO& io, int minus_identity, bool transposed) {
   PassDesc d = P.d;
   if (transposed)
     for (int s = 0; s < d.nsteps; ++s) d.Q[s] = h->ax[P.step_axes[s]].Qt;
-  d.pro = pro; d.epi = epi; d.minus_identity = minus_identity;
+  const int mode = L.kmode;
+  d.pro = d.epi = 0; d.minus_identity = minus_identity;
   d.theta = h->theta; d.inv_theta = 1.0 / h->theta; d.beta = h->beta;
   d.ablate = 0;
-  d.a3 = (epi == EPI_CES || epi == EPI_CES_LIN) ? h->a3 : nullptr;
+  d.a3 = (mode == M_TONLY || mode == M_TLAST || mode == M_TLAST_LIN) ? h->a3 : nullptr;   // (the aggregator's passes)
   d.ref_off = 0;
   d.lin_ref = h->sharded ? h->lin_ref : 0.0;
   if (!h->sharded) {                       // C-order offset of the mid-grid point
@@ -652,25 +697,16 @@ int launch_pass(sdfs_handle* h, Pass& P, int pro, int epi, const PassIO& io, int
     for (int a = h->ndim - 1; a >= 0; --a) { d.ref_off += (long long)(h->shape[a] / 2) * stride; stride *= h->shape[a]; }
   }
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool v2 = P.vec2 && al16(io.in) && al16(io.out) && al16(io.aux_in) && al16(io.aux_out) && al16(io.old);
-  if (!v2 && (long long)P.ept1 * P.block < (long long)d.m[0] * d.m[1] * d.m[2])
+  const TileForm tf = tile_form(P, al16(io.in) && al16(io.out) && al16(io.aux_in) && al16(io.aux_out) && al16(io.old),
+                               L.f32 && (mode == M_JFIRST || mode == M_MID || mode == M_JLAST));
+  if (tf.vec == 1 && (long long)P.ept1 * P.block < (long long)d.m[0] * d.m[1] * d.m[2])
     return fail(h, SDFS_ERR_ARG, "grid pointers must be 16-byte aligned for this tile shape");
-  int mode = M_MID;
-  if (pro == PRO_POW || pro == PRO_POW_LIN) {
-    if (epi == EPI_CES) mode = M_TONLY;
-    else if (epi == EPI_CES_LIN) return fail(h, SDFS_ERR_UNSUPPORTED, "single-pass linearise not supported");
-    else mode = (pro == PRO_POW_LIN) ? M_TFIRST_LIN : M_TFIRST;
-  } else if (epi == EPI_CES || epi == EPI_CES_LIN) mode = (epi == EPI_CES_LIN) ? M_TLAST_LIN : M_TLAST;
-  else if (pro == PRO_MUL) mode = M_JFIRST;
-  else if (epi == EPI_MUL) mode = M_JLAST;
-  if (pro == PRO_MUL && epi == EPI_MUL) return fail(h, SDFS_ERR_UNSUPPORTED, "single-pass JVP not supported");
-  const int block = P.block;
-  const bool v4 = v2 && P.vec4 && prec == 1 && (mode == M_JFIRST || mode == M_MID || mode == M_JLAST);
-  const int vec = v4 ? 4 : (v2 ? 2 : 1), ept = v4 ? P.ept4 : (v2 ? P.ept2 : P.ept1);
-  pass_fn fn = pass_kernel_variant(ept, vec, mode, prec);
-  if (!fn) return fail(h, SDFS_ERR_UNSUPPORTED, "no kernel variant for EPT %d VEC %d", ept, vec);
-  const long long grid = d.ntiles;
+  pass_fn fn = pass_kernel_variant(tf.ept, tf.vec, mode, L.f32 ? 1 : 0);
+  if (!fn) return fail(h, SDFS_ERR_UNSUPPORTED, "no kernel variant for EPT %d VEC %d", tf.ept, tf.vec);
+  L.fn = (const void*)fn;
 #ifdef SDFS_STAMP
+  const long long grid = L.grid;
+  const int block = L.block;
   PassIO io2 = io;
   static unsigned long long* dbg_dev = nullptr;
   if (!dbg_dev) hipMalloc((void**)&dbg_dev, 64 * 2 * 16 * 8);
@@ -699,7 +735,7 @@ int launch_pass(sdfs_handle* h, Pass& P, int pro, int epi, const PassIO& io, int
   }
   return 0;
 #endif
-  return launch_kernel(h, (const void*)fn, (unsigned)grid, block, P.lds_bytes, d, io, tag, P.label, bytes, P.flops);
+  return launch_selected(h, L, P, d, io);
 }
 
 int ensure_tmp(sdfs_handle* h) {
@@ -713,79 +749,65 @@ int ensure_lin(sdfs_handle* h) {
   return 0;
 }
 
-// Run the passes of `plan`.  first/last tell whether this plan holds the operator's
-// first pass (prologue) and last pass (epilogue) -- a sharded stage holds only one.
-// One application of the continuous-state operator (cont_kernel.hpp) in the role run_plan has for the
+// One application of the continuous-state operator (cont_kernel.hpp) in the role run_passes has for the
 // discretised one, so that every solver loop below serves both.
 template <int D>
-void launch_cont(sdfs_handle* h, int mode, const ContIO& io) {
+int launch_cont(sdfs_handle* h, int mode, const ContIO& io, const Counter& c) {
   const dim3 grid((unsigned)h->cd.N), block(256);
   // the staged box of the iterate + its pre-contracted form (x2 in the J.v kernel: the direction too)
   const size_t lds = (size_t)(h->cd.cap + h->cd.ucap) * sizeof(double);
-  if (mode == MODE_T) hipLaunchKernelGGL((cont_kernel<D, C_T>), grid, block, lds, h->stream, h->cd, io);
-  else if (mode == MODE_T_LIN) hipLaunchKernelGGL((cont_kernel<D, C_TLIN>), grid, block, lds, h->stream, h->cd, io);
-  else hipLaunchKernelGGL((cont_kernel<D, C_JVP>), grid, block, 2 * lds, h->stream, h->cd, io);
+  if (mode == MODE_T) return launch_kernel(h, cont_kernel<D, C_T>, grid, block, lds, c, h->cd, io);
+  if (mode == MODE_T_LIN) return launch_kernel(h, cont_kernel<D, C_TLIN>, grid, block, lds, c, h->cd, io);
+  return launch_kernel(h, cont_kernel<D, C_JVP>, grid, block, 2 * lds, c, h->cd, io);
 }
 
-int run_cont(sdfs_handle* h, int mode, const double* in, double* out, const double* old,
-             unsigned long long* resid, const unsigned long long* gate, double gate_tol, int minus_identity) {
+int run_cont(sdfs_handle* h, const Apply& a) {
   int rc = 0;
-  if (mode != MODE_T && (rc = ensure_lin(h))) return rc;
-  if (in == out) return fail(h, SDFS_ERR_ARG, "the continuous operator cannot run in place");
+  if (a.mode != MODE_T && (rc = ensure_lin(h))) return rc;
+  if (a.in == a.out) return fail(h, SDFS_ERR_ARG, "the continuous operator cannot run in place");
   ContIO io;
   memset(&io, 0, sizeof io);
-  io.out = out; io.gate = gate; io.gate_tol = gate_tol; io.minus_identity = minus_identity;
+  io.out = a.out; io.gate = a.gate; io.gate_tol = a.gate_tol; io.minus_identity = a.minus_identity;
   const double n8 = 8.0 * (double)h->cd.N;
   const double corners = (double)(1 << h->cd.D);
   double bytes = 2 * n8, flops = (double)h->cd.N * h->cd.M * (2.0 * corners + 2.0 * h->cd.D + 2.0);
   const char* tag = "cont:T";
-  if (mode == MODE_T) { io.w = in; io.old = old; io.resid = resid; if (resid) bytes += n8; }
-  else if (mode == MODE_T_LIN) {
+  if (a.mode == MODE_T) { io.w = a.in; io.old = a.old; io.resid = a.resid; if (a.resid) bytes += n8; }
+  else if (a.mode == MODE_T_LIN) {
     // keep the linearisation point: the JVP re-evaluates interp(w)^(theta-1) at every node
-    HIPCHK(h, hipMemcpyAsync(h->c1, in, (size_t)h->cd.N * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    io.w = in; io.old = old; io.resid = resid; io.c2_out = h->c2; bytes += 3 * n8; tag = "cont:Tlin";
-  } else { io.w = h->c1; io.v = in; io.c2_in = h->c2; bytes += 2 * n8; flops *= 1.5; tag = "cont:jvp"; }
-  int cid = h->profiling ? counter_id(h, tag, bytes, flops) : -1;
-  ProfScope ps(h, cid);
-  if (h->cd.D == 4) launch_cont<4>(h, mode, io);
-  else launch_cont<6>(h, mode, io);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+    HIPCHK(h, hipMemcpyAsync(h->c1, a.in, (size_t)h->cd.N * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    io.w = a.in; io.old = a.old; io.resid = a.resid; io.c2_out = h->c2; bytes += 3 * n8; tag = "cont:Tlin";
+  } else { io.w = h->c1; io.v = a.in; io.c2_in = h->c2; bytes += 2 * n8; flops *= 1.5; tag = "cont:jvp"; }
+  const Counter c(tag, bytes, flops);
+  return h->cd.D == 4 ? launch_cont<4>(h, a.mode, io, c) : launch_cont<6>(h, a.mode, io, c);
 }
 
-// One application of the dense single-index operator (dense_kernel.hpp), same role as run_plan.
-int run_dense(sdfs_handle* h, int mode, const double* in, double* out, const double* old,
-              unsigned long long* resid, const unsigned long long* gate, double gate_tol, int minus_identity) {
+// One application of the dense single-index operator (dense_kernel.hpp), same role as run_passes.
+int run_dense(sdfs_handle* h, const Apply& a) {
   int rc = ensure_tmp(h);
   if (rc) return rc;
-  if (mode != MODE_T && (rc = ensure_lin(h))) return rc;
+  if (a.mode != MODE_T && (rc = ensure_lin(h))) return rc;
   const long long N = h->N;
   DenseIO io;
   memset(&io, 0, sizeof io);
-  io.H = h->denseH; io.N = N; io.out = out; io.gate = gate; io.gate_tol = gate_tol;
-  io.beta = h->beta; io.inv_theta = 1.0 / h->theta; io.minus_identity = minus_identity;
+  io.H = h->denseH; io.N = N; io.out = a.out; io.gate = a.gate; io.gate_tol = a.gate_tol;
+  io.beta = h->beta; io.inv_theta = 1.0 / h->theta; io.minus_identity = a.minus_identity;
   const double hbytes = 8.0 * (double)N * (double)N, flops = 2.0 * (double)N * (double)N;
   const dim3 rows((unsigned)N), block(256);
-  if (mode == MODE_JVP) {
-    io.x = in; io.c1 = h->c1; io.c2_in = h->c2; io.old = in;
-    int cid = h->profiling ? counter_id(h, "dense:jvp", hbytes + 40.0 * N, flops) : -1;
-    ProfScope ps(h, cid);
-    hipLaunchKernelGGL((dense_gemv_kernel<D_JVP>), rows, block, 0, h->stream, io);
-    HIPCHK(h, hipGetLastError());
-    return 0;
+  if (a.mode == MODE_JVP) {
+    io.x = a.in; io.c1 = h->c1; io.c2_in = h->c2; io.old = a.in;
+    return launch_kernel(h, dense_gemv_kernel<D_JVP>, rows, block, 0, Counter("dense:jvp", hbytes + 40.0 * N, flops), io);
   }
+  // (the power runs ahead of the counted launch: the counter times the GEMV alone)
   const unsigned pblocks = (unsigned)std::min<long long>((N + 255) / 256, 4096);
-  if (mode == MODE_T_LIN)
-    hipLaunchKernelGGL((dense_pow_kernel<true>), dim3(pblocks), block, 0, h->stream, in, h->tmp, h->c1, N, h->theta, gate, gate_tol);
+  if (a.mode == MODE_T_LIN)
+    hipLaunchKernelGGL((dense_pow_kernel<true>), dim3(pblocks), block, 0, h->stream, a.in, h->tmp, h->c1, N, h->theta, a.gate, a.gate_tol);
   else
-    hipLaunchKernelGGL((dense_pow_kernel<false>), dim3(pblocks), block, 0, h->stream, in, h->tmp, (double*)nullptr, N, h->theta, gate, gate_tol);
-  io.x = h->tmp; io.old = old; io.resid = resid; io.c2_out = h->c2;
-  int cid = h->profiling ? counter_id(h, mode == MODE_T ? "dense:T" : "dense:Tlin", hbytes + 32.0 * N, flops) : -1;
-  ProfScope ps(h, cid);
-  if (mode == MODE_T) hipLaunchKernelGGL((dense_gemv_kernel<D_T>), rows, block, 0, h->stream, io);
-  else hipLaunchKernelGGL((dense_gemv_kernel<D_TLIN>), rows, block, 0, h->stream, io);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+    hipLaunchKernelGGL((dense_pow_kernel<false>), dim3(pblocks), block, 0, h->stream, a.in, h->tmp, (double*)nullptr, N, h->theta, a.gate, a.gate_tol);
+  io.x = h->tmp; io.old = a.old; io.resid = a.resid; io.c2_out = h->c2;
+  const Counter c(a.mode == MODE_T ? "dense:T" : "dense:Tlin", hbytes + 32.0 * N, flops);
+  return a.mode == MODE_T ? launch_kernel(h, dense_gemv_kernel<D_T>, rows, block, 0, c, io)
+                          : launch_kernel(h, dense_gemv_kernel<D_TLIN>, rows, block, 0, c, io);
 }
 
 // ---------------------------------------------------------------------------
@@ -1216,30 +1238,11 @@ int round_stream_bf16_n(sdfs_handle* h, void* p, long long n, const unsigned lon
   return 0;
 }
 
-// What pass i of a pair / small-grid / padded plan launches for request `a`: kernel, geometry, counter.  The one place that
-// picks the form of a pass -- run_fast_plan launches it, sdfs_describe_plan prints it, the fused dot products of BiCGSTAB
-// size their partial sums by its grid.
-struct PassLaunch {
-  const void* fn = nullptr;
-  unsigned grid = 0;
-  int block = 256;
-  size_t lds = 0;
-  double bytes = 0;                  // algorithmic bytes of the counter
-  const char* tag = "";              // counter name "<tag>:<pass label>"
-  int kmode = 0;                     // the kernel's mode: S_* (slice passes), SM_* (small grid), L_* (line passes)
-  bool jfused = false;               // first pass with BiCGSTAB's p / s update (JFusedIO, JFused32IO with m32)
-  bool m32 = false;                  // fp32-MFMA form (f32_kernels.hpp, krylov_kernels.hpp)
-  bool persistent = false;           // ... its persistent middle pass, next tile in flight
-  bool push = false;                 // T's streamed last pass with the Anderson push
-  const double* dot_with = nullptr;  // J.v's last pass also sums <out, dot_with>
-  const char* err = nullptr;         // no kernel for this pass
-  int err_code = SDFS_ERR_UNSUPPORTED;
-};
-
-PassLaunch select_pass(const sdfs_handle* h, const FastPlan& fp, int i, long long nloc, bool has_first, bool has_last,
-                       const Apply& a) {
+// What pass i launches for request `a` (PassLaunch, above): of the pair / small-grid / padded plan or sharded stage `fp`,
+// or, with fp == nullptr, of the generic tiles of `plan`; nloc = grid points of the block
+PassLaunch select_pass(const sdfs_handle* h, const FastPlan* fp, const Plan& plan, int i, long long nloc, bool has_first,
+                       bool has_last, const Apply& a) {
   PassLaunch L;
-  const FastPass& P = fp.passes[i];
   const bool vjp = a.mode == MODE_VJP;       // the J.v kernels with transposed matrices and c1 / c2 swapped (fp64)
   const int mode = vjp ? MODE_JVP : a.mode;
   // fp32 Krylov storage: every stream of a J.v application holds floats; a linearising T keeps fp64 streams and writes
@@ -1248,12 +1251,12 @@ PassLaunch select_pass(const sdfs_handle* h, const FastPlan& fp, int i, long lon
   // opts.t_f32: the intermediates between the passes of a plain T application as scaled floats (whole chunks everywhere)
   // (a sharded handle's stages, sdfs_set_t_f32: stage 0 then WRITES floats -- the exchange moves half the bytes -- and
   // stage 1 reads them)
-  const bool t32 = mode == MODE_T && a.prec == PREC_T32 && fp.f32_ok && !fp.small &&
+  const bool t32 = fp && mode == MODE_T && a.prec == PREC_T32 && fp->f32_ok && !fp->small &&
                    ((has_first && has_last) || (h->sharded && h->t32_ref > 0.0));
-  const bool last = has_last && i == (int)fp.passes.size() - 1;
+  const bool last = has_last && i == (int)(fp ? fp->passes.size() : plan.passes.size()) - 1;
   const double n8 = 8.0 * (double)nloc;
   L.tag = t32 ? "T32" : vjp ? "vjp" : (mode == MODE_JVP) ? (f32 ? "jvp32" : "jvp") : (mode == MODE_T_LIN ? "Tlin" : "T");
-  L.bytes = 2 * n8 + P.q_bytes;
+  L.bytes = 2 * n8 + (fp ? fp->passes[i].q_bytes : plan.passes[i].q_bytes);
   // first pass: c1 written (linearising T) or read (J.v); last pass: the epilogue's extra streams
   const int first_bytes = mode == MODE_T ? 0 : 1;
   auto last_mode = [&](int t, int tlin, int j) {
@@ -1263,6 +1266,28 @@ PassLaunch select_pass(const sdfs_handle* h, const FastPlan& fp, int i, long lon
     if (a.minus_identity) L.bytes += n8;
     return j;
   };
+  if (!fp) {
+    // generic tiles (pass_kernel.hpp): one kernel, the first and the last pass of the operator in modes of their own
+    const Pass& G = plan.passes[i];
+    const bool first = has_first && i == 0;
+    L.kmode = M_MID;
+    if (first) {
+      L.kmode = mode == MODE_T ? M_TFIRST : (mode == MODE_T_LIN ? M_TFIRST_LIN : M_JFIRST);
+      L.bytes += first_bytes * n8;
+    }
+    if (last) {
+      L.kmode = last_mode(M_TLAST, M_TLAST_LIN, M_JLAST);
+      // (a linearising pass writes c1 or c2 to the one aux_out, a J.v pass reads c1 or c2 from the one aux_in)
+      if (first && mode == MODE_T) L.kmode = M_TONLY;
+      else if (first) L.err = mode == MODE_T_LIN ? "single-pass linearise not supported" : "single-pass JVP not supported";
+    }
+    // (a linearising T stores floats only where it writes c1 and c2)
+    L.f32 = f32 && (mode == MODE_JVP || first || last);
+    if (L.f32 && mode == MODE_JVP) L.bytes *= 0.5;
+    L.grid = (unsigned)G.d.ntiles; L.block = G.block; L.lds = G.lds_bytes;
+    return L;
+  }
+  const FastPass& P = fp->passes[i];
   if (P.pad) {
     if (!P.line) {
       L.kmode = mode == MODE_T_LIN ? S_TFIRST_LIN : (mode == MODE_JVP ? S_JFIRST : S_TFIRST);
@@ -1388,9 +1413,16 @@ PassLaunch select_pass(const sdfs_handle* h, const FastPlan& fp, int i, long lon
   return L;
 }
 
-// fp = the whole-grid pair / small-grid / padded plan (has_first and has_last), or one stage of a sharded handle
-// (build_stage_fast_plans: stage 0 holds the first pass, stage 1 the last); nloc = grid points of the block
-int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, bool has_last, const Apply& a) {
+// the generic tile kernel has no word to clear ahead of the residual's atomicMax (its callers clear it)
+void clear_word(PassIO&, unsigned long long*) {}
+template <typename IO> void clear_word(IO& io, unsigned long long* word) { io.zero = word; }
+
+// One application: the passes of fp -- the whole-grid pair / small-grid / padded plan (has_first and has_last), or one
+// stage of a sharded handle (build_stage_fast_plans: stage 0 holds the first pass, stage 1 the last) -- or, with
+// fp == nullptr, of the generic tiles of `plan` (conditional tensors, extents above 16, sharded stages, the fp32-storage
+// fallback).  has_first / has_last tell whether the block holds the operator's first pass (prologue) and last pass
+// (epilogue): a sharded stage holds only one.
+int run_passes(sdfs_handle* h, const FastPlan* fp, const Plan& plan, bool has_first, bool has_last, const Apply& a) {
   const bool vjp = a.mode == MODE_VJP;
   const int mode = vjp ? MODE_JVP : a.mode;
   // J.v scalings: the cached linearisation, or the caller's (the tilted expectation's d1 / d2)
@@ -1399,11 +1431,18 @@ int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, 
   int rc = ensure_tmp(h);
   if (rc) return rc;
   if (mode != MODE_T) { rc = ensure_lin(h); if (rc) return rc; }
-  const int np = (int)fp.passes.size();
+  const long long nloc = fp == &h->fast ? h->N : plan.nloc;      // grid points of the block
+  const int np = (int)(fp ? fp->passes.size() : plan.passes.size());
   const bool bf16 = !vjp && a.prec == PREC_BF16 && mode != MODE_T;
+  // every pass reads the grid or the intermediate and writes the intermediate or the result, gated on the caller's word
+  auto open_io = [&](auto& io, int i) {
+    memset(&io, 0, sizeof io);
+    io.in = (i == 0) ? a.in : h->tmp; io.out = (i == np - 1) ? a.out : h->tmp;
+    io.gate = a.gate; io.gate_tol = a.gate_tol;
+  };
   // the first pass clears the word the last pass maximises into, and reads / writes c1; the last one reads / writes c2
   auto first_io = [&](auto& io) {
-    io.zero = (mode != MODE_JVP) ? a.resid : nullptr;
+    clear_word(io, (mode != MODE_JVP) ? a.resid : nullptr);
     if (mode == MODE_T_LIN) io.aux_out = h->c1;
     else if (mode == MODE_JVP) io.aux_in = vjp ? C2 : C1;
   };
@@ -1414,40 +1453,41 @@ int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, 
     if (mode == MODE_T_LIN) io.aux_out = h->c2;
   };
   for (int i = 0; i < np; ++i) {
-    const FastPass& P = fp.passes[i];
-    const bool last = has_last && i == np - 1;
-    const PassLaunch L = select_pass(h, fp, i, nloc, has_first, has_last, a);
+    const bool first = has_first && i == 0, last = has_last && i == np - 1;
+    const PassLaunch L = select_pass(h, fp, plan, i, nloc, has_first, has_last, a);
     if (L.err) return fail(h, L.err_code, "%s", L.err);
-    const double* pin = (i == 0) ? a.in : h->tmp;
-    double* pout = (i == np - 1) ? a.out : h->tmp;
-    if (P.pad) {
+    double* const pout = (i == np - 1) ? a.out : h->tmp;
+    if (!fp) {
+      PassIO io;
+      open_io(io, i);
+      if (first) first_io(io);
+      if (last) last_io(io);
+      rc = launch_pass(h, plan.passes[i], L, io, a.minus_identity, vjp);
+    } else if (const FastPass& P = fp->passes[i]; P.pad) {
       PadDesc d = P.pd;
       d.minus_identity = a.minus_identity;
       const int cls = P.nt == 16 ? 0 : (P.nt == 20 ? 1 : (P.nt == 24 ? 2 : 3));
       if (vjp) { d.Qx = h->ax[P.ax0].Qtpad[cls]; d.Qy = h->ax[P.ax1].Qtpad[cls]; }
       if (!P.line) {
         SliceIO io;
-        memset(&io, 0, sizeof io);
-        io.in = pin; io.out = pout; io.gate = a.gate; io.gate_tol = a.gate_tol;
+        open_io(io, i);
         first_io(io);
-        rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, d, io, L.tag, P.label, L.bytes, P.flops);
+        rc = launch_selected(h, L, P, d, io);
       } else {
         LineIO io;
-        memset(&io, 0, sizeof io);
-        io.in = pin; io.out = pout; io.gate = a.gate; io.gate_tol = a.gate_tol;
+        open_io(io, i);
         if (last) last_io(io);
-        rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, d, io, L.tag, P.label, L.bytes, P.flops);
+        rc = launch_selected(h, L, P, d, io);
       }
     } else if (P.small) {
       SmallIO io;
-      memset(&io, 0, sizeof io);
-      io.in = pin; io.out = pout; io.gate = a.gate; io.gate_tol = a.gate_tol;
+      open_io(io, i);
       SmallDesc d = P.sm;
       d.minus_identity = a.minus_identity;
       if (vjp) { d.Qxp = h->ax[P.ax0].Qtp; d.Qyp = h->ax[P.ax1].Qtp; }
       if (i == 0) first_io(io);
       else if (last) { last_io(io); io.dot_with = L.dot_with; }
-      rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, d, io, L.tag, P.label, L.bytes, P.flops);
+      rc = launch_selected(h, L, P, d, io);
     } else if (!P.line) {
       SliceDesc sd = P.sd;
       if (vjp) { sd.Qf = h->ax[P.ax1].Qt; sd.Qe = h->ax[P.ax0].Qt; }
@@ -1457,24 +1497,22 @@ int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, 
         memset(&jio, 0, sizeof jio);
         jio.upd = (float*)a.bicg.upd; jio.a = (const float*)a.bicg.a; jio.q = (const float*)a.bicg.q; jio.c1 = (const float*)h->c1;
         jio.out = (float*)pout; jio.sc = h->sc; jio.dot = a.bicg.dot; jio.gate = a.gate;
-        rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, sd, jio, L.tag, P.label, L.bytes, P.flops);
+        rc = launch_selected(h, L, P, sd, jio);
       } else if (L.jfused) {
         JFusedIO jio;
         memset(&jio, 0, sizeof jio);
         jio.upd = a.bicg.upd; jio.a = a.bicg.a; jio.q = a.bicg.q; jio.c1 = h->c1; jio.out = pout; jio.sc = h->sc;
         jio.dot = a.bicg.dot; jio.gate = a.gate;
-        rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, sd, jio, L.tag, P.label, L.bytes, P.flops);
+        rc = launch_selected(h, L, P, sd, jio);
       } else {
         SliceIO io;
-        memset(&io, 0, sizeof io);
-        io.in = pin; io.out = pout; io.gate = a.gate; io.gate_tol = a.gate_tol;
+        open_io(io, i);
         first_io(io);
-        rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, sd, io, L.tag, P.label, L.bytes, P.flops);
+        rc = launch_selected(h, L, P, sd, io);
       }
     } else {
       LineIO io;
-      memset(&io, 0, sizeof io);
-      io.in = pin; io.out = pout; io.gate = a.gate; io.gate_tol = a.gate_tol;
+      open_io(io, i);
       io.sched = h->sched + SCHED_WORDS * i;
       LineDesc d = P.ld;
       d.minus_identity = a.minus_identity;
@@ -1486,14 +1524,14 @@ int run_fast_plan(sdfs_handle* h, FastPlan& fp, long long nloc, bool has_first, 
         io.and_y = a.push.y; io.and_r = a.push.r; io.and_beta = a.push.beta; io.and_dot = a.push.dot;
         if (a.push.tiles) *a.push.tiles = P.ld.ntiles;
       }
-      rc = launch_kernel(h, L.fn, L.grid, L.block, L.lds, d, io, L.tag, P.label, L.bytes, P.flops);
+      rc = launch_selected(h, L, P, d, io);
     }
     if (rc) return rc;
     if (bf16) {
       // bf16r emulation: what this pass stored as floats is rounded to bfloat16 (the BiCGSTAB gate is a zero word when closed)
-      if (mode == MODE_JVP && (rc = round_stream_bf16_n(h, pout, (long long)h->N, a.gate))) return rc;
-      if (mode == MODE_T_LIN && i == 0 && (rc = round_stream_bf16_n(h, h->c1, (long long)h->N, nullptr))) return rc;
-      if (mode == MODE_T_LIN && last && (rc = round_stream_bf16_n(h, h->c2, (long long)h->N, nullptr))) return rc;
+      if (mode == MODE_JVP && (rc = round_stream_bf16_n(h, pout, nloc, a.gate))) return rc;
+      if (mode == MODE_T_LIN && first && (rc = round_stream_bf16_n(h, h->c1, nloc, nullptr))) return rc;
+      if (mode == MODE_T_LIN && last && (rc = round_stream_bf16_n(h, h->c2, nloc, nullptr))) return rc;
     }
   }
   return 0;
@@ -1514,11 +1552,13 @@ FastPlan* fast_plan_for(sdfs_handle* h, const Plan& plan, bool has_first, bool h
 // workgroups of the last pass of the whole-grid application `a` (one partial sum each of the fused dot products)
 long long last_pass_grid(sdfs_handle* h, const Apply& a) {
   if (h->cont || h->dense) return 0;
-  if (const FastPlan* fp = fast_plan_for(h, h->plan[0], true, true, a))
-    return select_pass(h, *fp, (int)fp->passes.size() - 1, h->N, true, true, a).grid;
-  return h->plan[0].passes.empty() ? 0 : h->plan[0].passes.back().d.ntiles;
+  const FastPlan* fp = fast_plan_for(h, h->plan[0], true, true, a);
+  const int np = (int)(fp ? fp->passes.size() : h->plan[0].passes.size());
+  return np ? select_pass(h, fp, h->plan[0], np - 1, h->N, true, true, a).grid : 0;
 }
 
+// One application on `plan` (the whole grid, or a stage of a sharded handle): the continuous or the dense operator, or the
+// passes of the plan that serves the request
 int run_plan(sdfs_handle* h, Plan& plan, bool has_first, bool has_last, const Apply& a) {
   if (a.mode == MODE_VJP) {
     if (h->cont || h->dense) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product exists for the discretised operator only");
@@ -1526,64 +1566,9 @@ int run_plan(sdfs_handle* h, Plan& plan, bool has_first, bool has_last, const Ap
       if (!h->ax[ax].Qt) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product needs unconditional transition tensors "
                                      "(axis %s is conditional)", h->ax[ax].name);
   }
-  if (h->cont) return run_cont(h, a.mode, a.in, a.out, a.old, a.resid, a.gate, a.gate_tol, a.minus_identity);
-  if (h->dense) return run_dense(h, a.mode, a.in, a.out, a.old, a.resid, a.gate, a.gate_tol, a.minus_identity);
-  if (FastPlan* fp = fast_plan_for(h, plan, has_first, has_last, a))
-    return run_fast_plan(h, *fp, fp == &h->fast ? h->N : plan.nloc, has_first, has_last, a);
-  const bool vjp = a.mode == MODE_VJP;       // the J.v launches with transposed matrices and c1 / c2 swapped
-  const int mode = vjp ? MODE_JVP : a.mode;
-  const double* const C1 = a.lc1 ? a.lc1 : h->c1;   // (lc1, lc2: the caller's J.v scalings, see run_fast_plan)
-  const double* const C2 = a.lc2 ? a.lc2 : h->c2;
-  const bool f32 = !vjp && a.f32();
-  int rc = ensure_tmp(h);
-  if (rc) return rc;
-  if (mode != MODE_T) { rc = ensure_lin(h); if (rc) return rc; }
-  const int np = (int)plan.passes.size();
-  const double n8 = 8.0 * (double)plan.nloc;
-  for (int i = 0; i < np; ++i) {
-    Pass& P = plan.passes[i];
-    const bool first = has_first && i == 0, last = has_last && i == np - 1;
-    PassIO io;
-    memset(&io, 0, sizeof io);
-    io.in = (i == 0) ? a.in : h->tmp;
-    io.out = (i == np - 1) ? a.out : h->tmp;
-    io.gate = a.gate; io.gate_tol = a.gate_tol;
-    int pro = PRO_NONE, epi = EPI_NONE;
-    double bytes = 2 * n8 + P.q_bytes;
-    if (first) {
-      if (mode == MODE_T) pro = PRO_POW;
-      else if (mode == MODE_T_LIN) { pro = PRO_POW_LIN; io.aux_out = h->c1; bytes += n8; }
-      else { pro = PRO_MUL; io.aux_in = vjp ? C2 : C1; bytes += n8; }
-    }
-    if (last) {
-      if (mode == MODE_T) { epi = EPI_CES; io.old = a.old; io.resid = a.resid; if (a.resid) bytes += n8; }
-      else if (mode == MODE_T_LIN) {
-        epi = EPI_CES_LIN; io.old = a.old; io.resid = a.resid; bytes += n8; if (a.resid) bytes += n8;
-        // aux_out of the LAST pass is c2; if the same pass is also the first, c1 and c2
-        // would collide on aux_out -- a single-pass plan splits linearisation in two launches
-        if (first) return fail(h, SDFS_ERR_UNSUPPORTED, "single-pass linearise not supported");
-        io.aux_out = h->c2;
-      } else {
-        epi = EPI_MUL; bytes += n8;
-        if (first) return fail(h, SDFS_ERR_UNSUPPORTED, "single-pass JVP not supported");
-        io.aux_in = vjp ? C1 : C2; io.old = a.old; if (a.minus_identity) bytes += n8;
-        if (a.minus_identity) io.dotp = a.dotp;
-      }
-    }
-    // fp32 Krylov storage: every stream of a J.v application is fp32; a linearising T keeps fp64
-    // streams and writes only c1 (first pass) and c2 (last pass) as fp32
-    const int prec = (f32 && (mode == MODE_JVP || (mode == MODE_T_LIN && (first || last)))) ? 1 : 0;
-    if (prec && mode == MODE_JVP) bytes *= 0.5;
-    const char* tag = vjp ? "vjp" : (mode == MODE_JVP) ? (f32 ? "jvp32" : "jvp") : (mode == MODE_T_LIN ? "Tlin" : "T");
-    rc = launch_pass(h, P, pro, epi, io, a.minus_identity, tag, bytes, prec, vjp);
-    if (rc) return rc;
-    if (prec && a.prec == PREC_BF16) {
-      if (mode == MODE_JVP && (rc = round_stream_bf16_n(h, io.out, plan.nloc, a.gate))) return rc;
-      if (mode == MODE_T_LIN && first && (rc = round_stream_bf16_n(h, h->c1, plan.nloc, nullptr))) return rc;
-      if (mode == MODE_T_LIN && last && (rc = round_stream_bf16_n(h, h->c2, plan.nloc, nullptr))) return rc;
-    }
-  }
-  return 0;
+  if (h->cont) return run_cont(h, a);
+  if (h->dense) return run_dense(h, a);
+  return run_passes(h, fast_plan_for(h, plan, has_first, has_last, a), plan, has_first, has_last, a);
 }
 
 // one application on the whole grid
@@ -1635,13 +1620,9 @@ int big_sa_line(sdfs_handle* h, int pass, bool first_only, const double* in, dou
   d.first_only = first_only ? 1 : 0;
   line_fn fn = line_variant(P.n, L_TFUSED, P.ld.lrest % LINE_R == 0);
   if (!fn) return fail(h, SDFS_ERR_UNSUPPORTED, "no fused line kernel variant");
-  int cid = -1;
   const double n8 = 8.0 * (double)h->N;
-  if (h->profiling) cid = counter_id(h, ((first_only ? "sa:open " : "sa:fused ") + P.label).c_str(), (first_only ? 2 : 4) * n8 + P.q_bytes, (first_only ? 1 : 2) * P.flops);
-  ProfScope ps(h, cid);
-  hipLaunchKernelGGL(fn, dim3((unsigned)d.ntiles), dim3(line_block(P.n)), line_lds_bytes(P.n), h->stream, d, io);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return launch_kernel(h, fn, dim3((unsigned)d.ntiles), dim3(line_block(P.n)), line_lds_bytes(P.n),
+                       Counter("sa", P.label, (first_only ? 2 : 4) * n8 + P.q_bytes, (first_only ? 1 : 2) * P.flops, first_only ? "open " : "fused "), d, io);
 }
 
 int big_sa_iteration(sdfs_handle* h, long long it, const double* w_old, double* w_new, unsigned long long* resid,
@@ -1652,14 +1633,10 @@ int big_sa_iteration(sdfs_handle* h, long long it, const double* w_old, double* 
   io.in = h->tmp; io.out = h->tmp; io.gate = gate; io.gate_tol = gate_tol;
   slice_fn fn = slice_variant(P.n, S_MID, false);
   if (!fn) return fail(h, SDFS_ERR_UNSUPPORTED, "no plain slice kernel variant");
-  {
-    int cid = -1;
-    if (h->profiling) cid = counter_id(h, ("sa:" + P.label).c_str(), 16.0 * (double)h->N + P.q_bytes, P.flops);
-    const long long ntile = (P.sd.nslices + slice_tile_slices(P.n, S_MID) - 1) / slice_tile_slices(P.n, S_MID);
-    ProfScope ps(h, cid);
-    hipLaunchKernelGGL(fn, dim3((unsigned)((ntile + 3) / 4)), dim3(256), slice_lds_bytes(P.n, S_MID), h->stream, P.sd, io);
-    HIPCHK(h, hipGetLastError());
-  }
+  const long long ntile = (P.sd.nslices + slice_tile_slices(P.n, S_MID) - 1) / slice_tile_slices(P.n, S_MID);
+  if (int rc = launch_kernel(h, fn, dim3((unsigned)((ntile + 3) / 4)), dim3(256), slice_lds_bytes(P.n, S_MID),
+                             Counter("sa", P.label, 16.0 * (double)h->N + P.q_bytes, P.flops), P.sd, io))
+    return rc;
   return big_sa_line(h, 1 + (int)(it & 1), false, h->tmp, w_new, w_old, resid, gate, gate_tol);
 }
 
@@ -1674,12 +1651,7 @@ int small_sa_prologue(sdfs_handle* h, const double* w) {
   io.in = w; io.out = h->tmp;
   small_fn fn = small_variant(SM_FIRST_T, P.r, P.wpt);
   if (!fn) return fail(h, SDFS_ERR_UNSUPPORTED, "no small-grid kernel variant");
-  int cid = -1;
-  if (h->profiling) cid = counter_id(h, ("sa:first " + P.label).c_str(), 16.0 * (double)h->N, P.flops);
-  ProfScope ps(h, cid);
-  hipLaunchKernelGGL(fn, dim3(small_grid(P.sm, P.wpt)), dim3(256), 0, h->stream, P.sm, io);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return launch_kernel(h, fn, dim3(small_grid(P.sm, P.wpt)), dim3(256), 0, Counter("sa", P.label, 16.0 * (double)h->N, P.flops, "first "), P.sm, io);
 }
 
 constexpr int SA_RING = SMALL_RING;   // most workgroups of an end pass for which the atomic-free residual is used
@@ -1708,16 +1680,35 @@ int small_sa_iteration(sdfs_handle* h, long long it, const double* w_old, double
     } else io.out = h->tmp;
     small_fn fn = small_variant(last ? SM_FUSED_T : SM_MID, P.r, P.wpt);
     if (!fn) return fail(h, SDFS_ERR_UNSUPPORTED, "no small-grid kernel variant");
-    int cid = -1;
-    if (h->profiling) cid = counter_id(h, ((last ? "sa:fused " : "sa:") + P.label).c_str(), (last ? 4 : 2) * n8, (last ? 2 : 1) * P.flops);
-    ProfScope ps(h, cid);
-    hipLaunchKernelGGL(fn, dim3(small_grid(P.sm, P.wpt)), dim3(256), 0, h->stream, P.sm, io);
-    HIPCHK(h, hipGetLastError());
+    if (int rc = launch_kernel(h, fn, dim3(small_grid(P.sm, P.wpt)), dim3(256), 0,
+                               Counter("sa", P.label, (last ? 4 : 2) * n8, (last ? 2 : 1) * P.flops, last ? "fused " : ""), P.sm, io))
+      return rc;
   }
   return 0;
 }
 
 double bits_to_double(unsigned long long b) { double d; memcpy(&d, &b, 8); return d; }
+
+long long lcm(long long a, long long b) { long long x = a, y = b; while (y) { const long long t = x % y; x = y; y = t; } return a / x * b; }
+
+// What `enqueue` launches on the handle's stream, captured and instantiated into *exec (in place of the graph it held)
+template <typename F>
+int capture_graph(sdfs_handle* h, hipGraphExec_t* exec, F&& enqueue) {
+  if (*exec) { hipGraphExecDestroy(*exec); *exec = nullptr; }
+  hipGraph_t g = nullptr;
+  HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+  const int rc = enqueue();
+  hipError_t e = hipStreamEndCapture(h->stream, &g);
+  if (rc || e != hipSuccess) {
+    if (g) hipGraphDestroy(g);
+    if (rc) return rc;
+    HIPCHK(h, e);
+  }
+  e = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
+  hipGraphDestroy(g);
+  HIPCHK(h, e);
+  return 0;
+}
 
 // ---------------------------------------------------------------------------
 // successive approximation (code/solvers.py:19-48), all iterations on the device.
@@ -1823,19 +1814,7 @@ int solve_sa(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int
   // hipStreamBeginCapture is illegal on the legacy NULL stream (sdfs_set_stream(h, NULL, 0)): plain launches there
   const bool graph = o.use_graph && !h->profiling && h->stream != nullptr;
   if (graph && (h->sa_graph == nullptr || h->sa_graph_chunk != chunk || h->sa_graph_tol != o.tol)) {
-    if (h->sa_graph) { hipGraphExecDestroy(h->sa_graph); h->sa_graph = nullptr; }
-    hipGraph_t g = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    rc = enqueue(0, chunk);
-    hipError_t e = hipStreamEndCapture(h->stream, &g);
-    if (rc || e != hipSuccess) {
-      if (g) hipGraphDestroy(g);
-      if (rc) return rc;
-      HIPCHK(h, e);
-    }
-    e = hipGraphInstantiate(&h->sa_graph, g, nullptr, nullptr, 0);
-    hipGraphDestroy(g);
-    HIPCHK(h, e);
+    if ((rc = capture_graph(h, &h->sa_graph, [&] { return enqueue(0, chunk); }))) return rc;
     h->sa_graph_chunk = chunk;
     h->sa_graph_tol = o.tol;
   }
@@ -2032,20 +2011,13 @@ int bicgstab_dev_t(sdfs_handle* h, const sdfs_opts& o, int64_t* matvecs, int pre
   const int gslot = std::is_same<T, float>::value ? 1 : 0;
   const bool graph = !plain && o.use_graph && !h->profiling && st != nullptr && chunk > 1 && !std::is_same<T, bf16r>::value;
   if (graph && (h->bicg_graph[gslot] == nullptr || h->bicg_graph_chunk[gslot] != chunk)) {
-    if (h->bicg_graph[gslot]) { hipGraphExecDestroy(h->bicg_graph[gslot]); h->bicg_graph[gslot] = nullptr; }
-    hipGraph_t gr = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    rc = 0;
-    for (int i = 0; i < chunk && !rc; ++i) rc = iteration();         // the whole chunk is one graph: one launch per synchronisation
-    hipError_t e = hipStreamEndCapture(st, &gr);
-    if (rc || e != hipSuccess) {
-      if (gr) hipGraphDestroy(gr);
-      if (rc) return rc;
-      HIPCHK(h, e);
-    }
-    e = hipGraphInstantiate(&h->bicg_graph[gslot], gr, nullptr, nullptr, 0);
-    hipGraphDestroy(gr);
-    HIPCHK(h, e);
+    // the whole chunk is one graph: one launch per synchronisation
+    rc = capture_graph(h, &h->bicg_graph[gslot], [&] {
+      int rc2 = 0;
+      for (int i = 0; i < chunk && !rc2; ++i) rc2 = iteration();
+      return rc2;
+    });
+    if (rc) return rc;
     h->bicg_graph_chunk[gslot] = chunk;
   }
   long long k = 0;
@@ -2302,7 +2274,6 @@ int solve_anderson(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_ite
   // large grids (the loop is HBM-bound there): the Gram matrix in one sweep where a solve is due (vec_kernels.hpp)
   const bool lazyp = h->knobs.and_fused && !fusedp && !h->sharded && m <= AND_LAZY_M && h->N >= (1LL << 21);
   if (lazyp) {
-    auto lcm = [](long long a, long long b) { long long x = a, y = b; while (y) { const long long t = x % y; x = y; y = t; } return a / x * b; };
     const long long unit = lcm(lcm(m, o.mixing_freq), 2);
     chunk = (int)(((chunk + unit - 1) / unit) * unit);
     if (!h->and_gram_partial) {
@@ -2311,7 +2282,6 @@ int solve_anderson(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_ite
     }
   }
   if (fusedp) {
-    auto lcm = [](long long a, long long b) { long long x = a, y = b; while (y) { const long long t = x % y; x = y; y = t; } return a / x * b; };
     const long long unit = lcm(lcm(m, 2), o.mixing_freq);
     // (a chunk of this form ends with a launch of its own and the passes do not depend on the chunking: the default
     // polling interval is stretched, an explicit one is honoured)
@@ -2361,6 +2331,14 @@ int solve_anderson(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_ite
   }
   h->trace.clear();
   const int cvec = h->profiling ? counter_id(h, "anderson_blas1", 0, 0) : -1;
+  // the end of every form of a chunk: the launches' error check, then errors, step kinds and the state go to the host
+  auto read_back = [&](int count, const AndState* state) -> int {
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(h->and_err_host, h->and_err, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(h->and_kind_host, h->and_kind, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(h->and_state_host, state, sizeof(AndState), hipMemcpyDeviceToHost, st));
+    return 0;
+  };
   auto enqueue = [&](int count) -> int {
     HIPCHK(h, hipMemsetAsync(h->and_kind, 0, sizeof(int) * (size_t)chunk, st));
     for (int i = 0; i < count; ++i) {
@@ -2373,11 +2351,7 @@ int solve_anderson(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_ite
                          o.tol, (double)o.max_iter, (int)o.mixing_freq, o.ridge);
       hipLaunchKernelGGL(k_and_mix_dev, dim3(g), dim3(VEC_BLOCK), 0, st, hp, (const AndState*)S, m, o.beta, x, (const double*)fx, pos, i, n);
     }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(h->and_err_host, h->and_err, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(h->and_kind_host, h->and_kind, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(h->and_state_host, S, sizeof(AndState), hipMemcpyDeviceToHost, st));
-    return 0;
+    return read_back(count, S);
   };
   // the fused form of a chunk: pass 0 starts from x as it stands, pass i > 0 opens with the step of pass i - 1; the step
   // and the update of the chunk's last pass are the two launches of the unfused form.  State of pass i: S[i & 1].
@@ -2436,11 +2410,7 @@ int solve_anderson(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_ite
       an.pos = lastp % m; an.rel = lastp; an.step_kind = 2;
       hipLaunchKernelGGL(small_and_finish, dim3((unsigned)std::min<long long>((n + 255) / 256, 512)), dim3(256), 0, st, an, (const double*)fx, n);
     }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(h->and_err_host, h->and_err, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(h->and_kind_host, h->and_kind, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(h->and_state_host, S + (count & 1), sizeof(AndState), hipMemcpyDeviceToHost, st));
-    return 0;
+    return read_back(count, S + (count & 1));
   };
   // Large grids: <r, r> per pass, the whole Gram matrix in one sweep where a solve is due, history as Y_j (vec_kernels.hpp)
   auto enqueue_lazy = [&](int count) -> int {
@@ -2473,30 +2443,14 @@ int solve_anderson(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_ite
                          m, pos, i, S, h->and_err + i, h->and_kind + i, o.tol, (double)o.max_iter, (int)o.mixing_freq, o.ridge);
       hipLaunchKernelGGL(k_and_mix_y, dim3(g), dim3(VEC_BLOCK), 0, st, hp, (const AndState*)S, m, o.beta, xo, (const double*)xo, pos, i, n);
     }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(h->and_err_host, h->and_err, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(h->and_kind_host, h->and_kind, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(h->and_state_host, S, sizeof(AndState), hipMemcpyDeviceToHost, st));
-    return 0;
+    return read_back(count, S);
   };
   auto enqueue_any = [&](int count) -> int { return fusedp ? enqueue_fused(count) : (lazyp ? enqueue_lazy(count) : enqueue(count)); };
   const bool graph = o.use_graph && !h->profiling && st != nullptr && chunk > 1;
   const double key[4] = {o.tol, (double)o.max_iter, o.beta, o.ridge};
   if (graph && (h->and_graph == nullptr || h->and_graph_chunk != chunk || h->and_graph_m != m || h->and_graph_freq != (int)o.mixing_freq ||
                 memcmp(key, h->and_graph_key, sizeof key) != 0)) {
-    if (h->and_graph) { hipGraphExecDestroy(h->and_graph); h->and_graph = nullptr; }
-    hipGraph_t gr = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    rc = enqueue_any(chunk);
-    hipError_t e = hipStreamEndCapture(st, &gr);
-    if (rc || e != hipSuccess) {
-      if (gr) hipGraphDestroy(gr);
-      if (rc) return rc;
-      HIPCHK(h, e);
-    }
-    e = hipGraphInstantiate(&h->and_graph, gr, nullptr, nullptr, 0);
-    hipGraphDestroy(gr);
-    HIPCHK(h, e);
+    if ((rc = capture_graph(h, &h->and_graph, [&] { return enqueue_any(chunk); }))) return rc;
     h->and_graph_chunk = chunk; h->and_graph_m = m; h->and_graph_freq = (int)o.mixing_freq;
     memcpy(h->and_graph_key, key, sizeof key);
   }
@@ -3342,21 +3296,17 @@ int sdfs_param_tangent_gen_dev(sdfs_handle* h, const double* w, const double* dp
   const double n8 = 8.0 * (double)h->N;
   if (need_jv) {
     g.ax_tab = h->sens.ax_a1;
-    { const int cid = h->profiling ? counter_id(h, "sens:prologue", 2 * n8, 0) : -1;
-      ProfScope ps(h, cid);
-      hipLaunchKernelGGL(k_sens_prologue, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, g, dla1, dtheta, w, h->sens.v);
-      HIPCHK(h, hipGetLastError()); }
+    if ((rc = launch_kernel(h, k_sens_prologue, dim3(grid), dim3(SENS_BLOCK), 0, Counter("sens:prologue", 2 * n8, 0), g, dla1, dtheta, w,
+                            h->sens.v)))
+      return rc;
     if ((rc = apply(h, Apply(MODE_JVP, h->sens.v, out, h->sens.v)))) return rc;
   }
   g.ax_tab = h->sens.ax_a2;
-  {
-    const int cid = h->profiling ? counter_id(h, need_jv ? "sens:epilogue" : "sens:epilogue_nojv", (need_jv ? 3 : 2) * n8, 0) : -1;
-    ProfScope ps(h, cid);
-    hipLaunchKernelGGL(k_sens_epilogue, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, g, dla2, dbeta / h->beta, dtheta / h->theta,
-                       1.0 / h->beta, 1.0 / h->theta, (const double*)Tw, need_jv ? (const double*)out : nullptr,
-                       any_a3 ? (const double*)h->sens.dla3 : nullptr, out);
-    HIPCHK(h, hipGetLastError());
-  }
+  if ((rc = launch_kernel(h, k_sens_epilogue, dim3(grid), dim3(SENS_BLOCK), 0,
+                          Counter(need_jv ? "sens:epilogue" : "sens:epilogue_nojv", (need_jv ? 3 : 2) * n8, 0), g, dla2, dbeta / h->beta,
+                          dtheta / h->theta, 1.0 / h->beta, 1.0 / h->theta, (const double*)Tw, need_jv ? (const double*)out : nullptr,
+                          any_a3 ? (const double*)h->sens.dla3 : nullptr, out)))
+    return rc;
   if (any_gen) {
     SensTab la2;
     for (int i = 0; i < SENS_MAXN; ++i) la2.t[i] = 0.0;
@@ -3375,11 +3325,9 @@ int sdfs_param_tangent_gen_dev(sdfs_handle* h, const double* w, const double* dp
         G.sup[i] = i < n - 1 ? dgen[a][2 * n + i] : 0.0;
       }
       // Tw, out read and out written; the two neighbours along the axis come from lines the sweep fetches anyway
-      const int cid = h->profiling ? counter_id(h, "sens:generator", 3 * n8, 0) : -1;
-      ProfScope ps(h, cid);
-      hipLaunchKernelGGL(k_sens_generator, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, g, G, la2, a, h->theta, 1.0 / h->theta,
-                         (const double*)Tw, (const double*)h->sens.la3, out);
-      HIPCHK(h, hipGetLastError());
+      if ((rc = launch_kernel(h, k_sens_generator, dim3(grid), dim3(SENS_BLOCK), 0, Counter("sens:generator", 3 * n8, 0), g, G, la2, a,
+                              h->theta, 1.0 / h->theta, (const double*)Tw, (const double*)h->sens.la3, out)))
+        return rc;
     }
   }
   return 0;
@@ -3497,21 +3445,14 @@ int sdfs_set_tilt_dev(sdfs_handle* h, const double* w, int sdf_power, double kap
   const int grid = (int)std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK, (long long)h->num_cus * 16);
   const double* ez = xz != 0.0 ? (const double*)Pr.ez : nullptr;
   const double n8 = 8.0 * (double)h->N;
-  const int cid = h->profiling ? counter_id(h, sdf_power == 0 ? "price:tilt0" : (sdf_power == 1 ? "price:tilt1" : "price:tilt2"),
-                                            (sdf_power == 0 ? 2 : 4) * n8, 0) : -1;
-  {
-    ProfScope ps(h, cid);
-    if (sdf_power == 0)
-      hipLaunchKernelGGL(k_tilt_scalings<0>, dim3(grid), dim3(PRICE_BLOCK), 0, h->stream, g, el, ec, ez, (const double*)nullptr,
-                         (const double*)nullptr, Pr.d1, Pr.d2);
-    else if (sdf_power == 1)
-      hipLaunchKernelGGL(k_tilt_scalings<1>, dim3(grid), dim3(PRICE_BLOCK), 0, h->stream, g, el, ec, ez, (const double*)h->c1,
-                         (const double*)h->c2, Pr.d1, Pr.d2);
-    else
-      hipLaunchKernelGGL(k_tilt_scalings<2>, dim3(grid), dim3(PRICE_BLOCK), 0, h->stream, g, el, ec, ez, (const double*)h->c1,
-                         (const double*)h->c2, Pr.d1, Pr.d2);
-    HIPCHK(h, hipGetLastError());
-  }
+  // (power 0 reads no linearisation)
+  auto fn = k_tilt_scalings<0>;
+  if (sdf_power == 1) fn = k_tilt_scalings<1>;
+  else if (sdf_power == 2) fn = k_tilt_scalings<2>;
+  if ((rc = launch_kernel(h, fn, dim3(grid), dim3(PRICE_BLOCK), 0,
+                          Counter(sdf_power == 0 ? "price:tilt0" : (sdf_power == 1 ? "price:tilt1" : "price:tilt2"), (sdf_power == 0 ? 2 : 4) * n8, 0),
+                          g, el, ec, ez, sdf_power ? (const double*)h->c1 : nullptr, sdf_power ? (const double*)h->c2 : nullptr, Pr.d1, Pr.d2)))
+    return rc;
   Pr.power = sdf_power;
   return 0;
 }
@@ -3622,30 +3563,21 @@ int sim_handle_ok(sdfs_handle* h, const char* fn) {
   return 0;
 }
 
+// k_sim_paths for a look-ahead k, a search and, on the defaults of both, with the paths stored
+typedef void (*sim_fn)(SimArgs, const double*, const double*, double*, unsigned char*, double*);
+
 template <int ND, bool KAP, bool LIN, int K>
-void sim_launch(sdfs_handle* h, dim3 grid, size_t lds, const SimArgs& a, const double* tab, const double* rec,
-                double* stats, unsigned char* idx, double* ser) {
+sim_fn sim_form(bool store) {
   if constexpr (LIN == SIM_LIN_DEFAULT && K == SIM_K_DEFAULT) {
-    if (idx) {
-      hipLaunchKernelGGL((k_sim_paths<ND, KAP, LIN, K, true>), grid, dim3(SIM_BLOCK), lds, h->stream, a, tab, rec, stats, idx, ser);
-      return;
-    }
+    if (store) return k_sim_paths<ND, KAP, LIN, K, true>;
   }
-  hipLaunchKernelGGL((k_sim_paths<ND, KAP, LIN, K, false>), grid, dim3(SIM_BLOCK), lds, h->stream, a, tab, rec, stats, idx, ser);
+  return k_sim_paths<ND, KAP, LIN, K, false>;
 }
 
 template <int ND, bool KAP>
-void sim_dispatch(sdfs_handle* h, int k, bool lin, dim3 grid, size_t lds, const SimArgs& a, const double* tab,
-                  const double* rec, double* stats, unsigned char* idx, double* ser) {
-  if (lin) {
-    if (k == 1) sim_launch<ND, KAP, true, 1>(h, grid, lds, a, tab, rec, stats, idx, ser);
-    else if (k == 2) sim_launch<ND, KAP, true, 2>(h, grid, lds, a, tab, rec, stats, idx, ser);
-    else sim_launch<ND, KAP, true, 4>(h, grid, lds, a, tab, rec, stats, idx, ser);
-  } else {
-    if (k == 1) sim_launch<ND, KAP, false, 1>(h, grid, lds, a, tab, rec, stats, idx, ser);
-    else if (k == 2) sim_launch<ND, KAP, false, 2>(h, grid, lds, a, tab, rec, stats, idx, ser);
-    else sim_launch<ND, KAP, false, 4>(h, grid, lds, a, tab, rec, stats, idx, ser);
-  }
+sim_fn sim_variant(int k, bool lin, bool store) {
+  if (lin) return k == 1 ? sim_form<ND, KAP, true, 1>(store) : (k == 2 ? sim_form<ND, KAP, true, 2>(store) : sim_form<ND, KAP, true, 4>(store));
+  return k == 1 ? sim_form<ND, KAP, false, 1>(store) : (k == 2 ? sim_form<ND, KAP, false, 2>(store) : sim_form<ND, KAP, false, 4>(store));
 }
 }  // namespace
 }  // extern "C++"
@@ -3668,14 +3600,9 @@ int sdfs_sim_records_dev(sdfs_handle* h, const double* w, const double* v, doubl
   // E_x[M] = K(1, theta, -gamma) 1: the product sdf_moments forms, bit for bit
   if ((rc = sdfs_set_tilt_dev(h, w, 1, h->theta, -S.gamma))) return rc;
   if ((rc = sdfs_apply_tilted_dev(h, Sm.one, Sm.em))) return rc;
-  const int cid = h->profiling ? counter_id(h, "sim:records", (double)h->N * (16.0 + (v ? 8.0 : 0.0) + 8.0 * SIM_REC), 0) : -1;
-  {
-    ProfScope ps(h, cid);
-    hipLaunchKernelGGL(k_sim_records, dim3(fgrid), dim3(PRICE_BLOCK), 0, h->stream, price_geom(h), (const double*)Sm.zt, w,
+  return launch_kernel(h, k_sim_records, dim3(fgrid), dim3(PRICE_BLOCK), 0,
+                       Counter("sim:records", (double)h->N * (16.0 + (v ? 8.0 : 0.0) + 8.0 * SIM_REC), 0), price_geom(h), (const double*)Sm.zt, w,
                        (const double*)Sm.em, v, rec);
-    HIPCHK(h, hipGetLastError());
-  }
-  return 0;
 }
 
 int sdfs_sim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_sim_desc* d, double* stats, uint8_t* idx, double* ser) {
@@ -3738,20 +3665,12 @@ int sdfs_sim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_sim_desc* d
   const dim3 grid((unsigned)((d->n_paths + SIM_BLOCK - 1) / SIM_BLOCK));
   const size_t lds = sizeof(double) * (size_t)a.lds_n;
   const double steps = (double)d->n_paths * (double)(d->burn_in + d->n_periods);
-  const int cid = h->profiling ? counter_id(h, "sim:paths", 8.0 * SIM_REC * (double)d->n_paths * (double)(d->n_periods + 1), steps) : -1;
-  {
-    ProfScope ps(h, cid);
-    const double* tab = h->sim.tab;
-    if (h->ndim == 4) {
-      if (d->has_kappa) sim_dispatch<4, true>(h, k, lin, grid, lds, a, tab, rec, stats, idx, ser);
-      else sim_dispatch<4, false>(h, k, lin, grid, lds, a, tab, rec, stats, idx, ser);
-    } else {
-      if (d->has_kappa) sim_dispatch<6, true>(h, k, lin, grid, lds, a, tab, rec, stats, idx, ser);
-      else sim_dispatch<6, false>(h, k, lin, grid, lds, a, tab, rec, stats, idx, ser);
-    }
-    HIPCHK(h, hipGetLastError());
-  }
-  return 0;
+  const bool store = idx != nullptr;
+  const sim_fn fn = h->ndim == 4 ? (d->has_kappa ? sim_variant<4, true>(k, lin, store) : sim_variant<4, false>(k, lin, store))
+                                 : (d->has_kappa ? sim_variant<6, true>(k, lin, store) : sim_variant<6, false>(k, lin, store));
+  return launch_kernel(h, fn, grid, dim3(SIM_BLOCK), lds,
+                       Counter("sim:paths", 8.0 * SIM_REC * (double)d->n_paths * (double)(d->n_periods + 1), steps), a,
+                       (const double*)h->sim.tab, rec, stats, idx, ser);
 }
 
 int sdfs_residual(sdfs_handle* h, double* sup_norm) {
@@ -4172,7 +4091,7 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
                  P.label.c_str(), P.wpt, P.wpt == 1 ? "" : "s", P.r, P.sm.ntiles, small_grid(P.sm, P.wpt));
       } else if (!P.line) {
         // (the first pass of T)
-        const PassLaunch L = select_pass(h, h->fast, (int)i, h->N, true, true, Apply(MODE_T, nullptr, nullptr, nullptr));
+        const PassLaunch L = select_pass(h, &h->fast, h->plan[0], (int)i, h->N, true, true, Apply(MODE_T, nullptr, nullptr, nullptr));
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, L.fn, L.block, L.lds);
         const long long nt = (P.sd.nslices + slice_tile_slices(P.n, S_TFIRST) - 1) / slice_tile_slices(P.n, S_TFIRST);
         snprintf(line, sizeof line, "pair plan pass %zu: %s lds %zu B block 256 (4 wave tiles) wave-tiles %lld blocks/CU %d\n", i,
@@ -4194,13 +4113,13 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
     if (h->fast.small && anderson_fused_ok(h, 10))
       s += "small-grid plan, Anderson: passes in reverse order, push on the last pass, control step + update of x on the first\n";
     // the fp32 J.v forms of each pass (opts.krylov_f32 = 1 / 2: fp32 streams on the fp64 tile; 3: the fp32-MFMA kernel
-    // run_fast_plan picks, with its row width and, for a middle pass, whether it runs persistent)
+    // select_pass picks, with its row width and, for a middle pass, whether it runs persistent)
     Apply m32(MODE_JVP, nullptr, nullptr, nullptr);
     m32.prec = PREC_MFMA32; m32.minus_identity = 1;
     for (size_t i = 0; i < h->fast.passes.size() && h->fast.f32_ok && !h->fast.small && !h->fast.pad; ++i) {
       const FastPass& P = h->fast.passes[i];
       const bool last = i + 1 == h->fast.passes.size();
-      const PassLaunch L = select_pass(h, h->fast, (int)i, h->N, true, true, m32);
+      const PassLaunch L = select_pass(h, &h->fast, h->plan[0], (int)i, h->N, true, true, m32);
       if (!P.line) {
         snprintf(line, sizeof line, "pair plan pass %zu fp32: %s mfma32 %s\n", i, P.label.c_str(), L.fn ? "slice32" : "none");
       } else {
@@ -4233,11 +4152,13 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
     for (size_t i = 0; i < pl.passes.size(); ++i) {
       const Pass& P = pl.passes[i];
       int occ = -1;
-      pass_fn fn = pass_kernel_variant(P.vec2 ? P.ept2 : P.ept1, P.vec2 ? 2 : 1, M_MID);
-      if (fn) hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)fn, P.block, P.lds_bytes);
+      // (the middle form on aligned fp64 streams)
+      const PassLaunch L = select_pass(h, nullptr, pl, (int)i, pl.nloc, false, false, Apply(MODE_T, nullptr, nullptr, nullptr));
+      const TileForm tf = tile_form(P, true, false);
+      pass_fn fn = pass_kernel_variant(tf.ept, tf.vec, L.kmode);
+      if (fn) hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)fn, L.block, L.lds);
       snprintf(line, sizeof line, "stage %d pass %zu: %s tile %dx%dx%d lds %zu B block %d vec %d ept %d tiles %lld blocks/CU %d\n", st, i,
-               P.label.c_str(), P.d.m[0], P.d.m[1], P.d.m[2], P.lds_bytes, P.block, P.vec2 ? 2 : 1,
-               P.vec2 ? P.ept2 : P.ept1, P.d.ntiles, occ);
+               P.label.c_str(), P.d.m[0], P.d.m[1], P.d.m[2], L.lds, L.block, tf.vec, tf.ept, (long long)L.grid, occ);
       s += line;
     }
   }
