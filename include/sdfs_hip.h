@@ -276,6 +276,45 @@ int sdfs_sim_records_dev(sdfs_handle* h, const double* w_dev, const double* v_de
 int sdfs_sim_paths_dev(sdfs_handle* h, const double* records_dev, const sdfs_sim_desc* desc, double* stats_dev,
                        uint8_t* idx_dev, double* series_dev);
 
+/* Simulated paths of the continuous-state model at w* (handles of sdfs_create_continuous only, else
+ * SDFS_ERR_UNSUPPORTED; fp64).
+ *
+ * em = E_x[M] of the handle's nodes and weights on the grid (device pointers, N doubles each, distinct):
+ *   beta^theta (w(x) - 1)^(1 - theta) exp(-gamma (mu_c + z) + gamma^2 sigma_c(x)^2 / 2)
+ *     * sum_m W_m exp(theta h_lambda'(x, m)) lin_interp(w)(x'(x, m))^(theta - 1)
+ * by T's kernel with the exponent theta - 1 on the interpolant, on the gather path T takes.  NaN where w <= 1. */
+int sdfs_cont_sdf_mean_dev(sdfs_handle* h, const double* w_dev, double* em_dev);
+/* One 16-byte record {w, -ln E_x[M]} per grid point into records_dev (N x 2 doubles, 16-byte aligned). */
+int sdfs_cont_sim_records_dev(sdfs_handle* h, const double* w_dev, const double* em_dev, double* records_dev);
+/* Step s0 + k of path p (s0 = step_offset) draws the Philox4x32-10 blocks b = 0, 1 with counter (s0 + k, p, b, 1) and key
+ * (seed & 0xffffffff, seed >> 32); the words r0 ... r3 of a block give the normals n_4b ... n_4b+3 by Box-Muller
+ * (u = (r0 + 0.5) 2^-32, phi = 2 pi r1 2^-32: sqrt(-2 ln u) cos phi, sqrt(-2 ln u) sin phi; r2, r3 likewise); eta_d = n_d for
+ * d < ndim in the handle's state order, xi = n_ndim.  x_k = next_state(x_{k-1}, eta_k) (the reference's); steps 1 ... B
+ * are burn-in, B+1 ... B+T recorded. */
+typedef struct sdfs_cont_sim_desc {
+  uint64_t seed;
+  int64_t path_offset;      /* number of the first path; path_offset + n_paths <= 2^32 */
+  int64_t n_paths;
+  int64_t burn_in;          /* B >= 0 */
+  int64_t n_periods;        /* T >= 2 */
+  int64_t step_offset;      /* s0 >= 0, s0 + B + T < 2^32 */
+  int32_t start_mode;       /* x_0: 0 the zero state, 1 start[] for every path, 2 start_dev */
+  int32_t lookahead;        /* states interpolated side by side: 1, 2 or 4 (0: the default) */
+  int32_t group;            /* corners loaded together: 4, 8 or, in 6-D with lookahead <= 2, 16 (0: the default) */
+  int32_t reserved;
+  double start[6];
+  const double* start_dev;  /* DEVICE: n_paths x ndim, the start of every path of this call */
+} sdfs_cont_sim_desc;
+/* desc->n_paths paths, one lane each, from the records of sdfs_cont_sim_records_dev, whose two fields are interpolated
+ * along the path (multilinear, coordinates clamped to the grid as lin_interp clamps them).  stats_dev: 19 x n_paths
+ * doubles, structure of arrays: mean, std, ac1 of series k at rows 3k ... 3k+2 for dc, m, rf, rc, xc, wc, then the OLS
+ * slope of xc_t on ln(w(x_{t-1}) - 1).  clamped_dev: n_paths counts of recorded steps whose x_t lay outside the grid on
+ * some axis.  final_state_dev: n_paths x ndim, x_{B+T}.  states_dev (n_paths x (T+1) x ndim: x_B ... x_{B+T}) and
+ * series_dev (6 x n_paths x T) are both NULL or both set; set, they run with the default lookahead and group.  No host
+ * synchronisation and no atomics; a path's output depends only on its number, the seed, s0, its start and the model. */
+int sdfs_cont_sim_paths_dev(sdfs_handle* h, const double* records_dev, const sdfs_cont_sim_desc* desc, double* stats_dev,
+                            uint32_t* clamped_dev, double* final_state_dev, double* states_dev, double* series_dev);
+
 /* max|T(w) - w| of the most recent apply that computed it. */
 int sdfs_residual(sdfs_handle* h, double* sup_norm);
 

@@ -29,7 +29,7 @@ from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_rat
                           discretize_gcy_persistence_tangent, SSY_PERSISTENCE, GCY_PERSISTENCE,
                           adjoint_moments_to_gradient)
 from .pricing import stationary_weights, sdf_moments, term_structure, claim_prices
-from .simulation import simulate
+from .simulation import simulate, simulate_continuous
 from .batch import (BatchOperator, BatchResult, solve_batch, batch_lds_bytes, BatchGradient, gradient_batch, BatchPrices,
                     price_batch, price_words_to_stats, BatchSimulation, simulate_batch, batch_sim_lds_bytes,
                     batch_cdf_tables, batch_sim_tables)
@@ -48,7 +48,7 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "discretize_ssy_tangent", "discretize_gcy_tangent", "wc_ratio_sensitivities", "wc_ratio_gradient",
            "rouwenhorst_generator", "discretize_ssy_persistence_tangent", "discretize_gcy_persistence_tangent",
            "SSY_PERSISTENCE", "GCY_PERSISTENCE", "adjoint_moments_to_gradient",
-           "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate",
+           "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate", "simulate_continuous",
            "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes", "BatchGradient", "gradient_batch", "BatchPrices", "price_batch", "price_words_to_stats",
            "BatchSimulation", "simulate_batch", "batch_sim_lds_bytes", "batch_cdf_tables", "batch_sim_tables",
            "SdfsError", "LIB_PATH"]

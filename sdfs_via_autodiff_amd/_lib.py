@@ -50,6 +50,13 @@ class sdfs_sim_desc(C.Structure):
                 ("cdf", C.POINTER(C.c_double)), ("cdf0", C.POINTER(C.c_double))]
 
 
+class sdfs_cont_sim_desc(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("path_offset", C.c_int64), ("n_paths", C.c_int64),
+                ("burn_in", C.c_int64), ("n_periods", C.c_int64), ("step_offset", C.c_int64),
+                ("start_mode", C.c_int32), ("lookahead", C.c_int32), ("group", C.c_int32), ("reserved", C.c_int32),
+                ("start", C.c_double * 6), ("start_dev", C.c_void_p)]
+
+
 class sdfs_batch_sim_desc(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("path_offset", C.c_int64), ("n_paths", C.c_int64),
                 ("burn_in", C.c_int64), ("n_periods", C.c_int64),
@@ -100,6 +107,9 @@ SYMBOLS = {
     "sdfs_tilted_horizons_dev": (C.c_int, [_P, C.c_int64, C.POINTER(_D), C.c_int64, C.POINTER(C.c_int64), C.POINTER(_P), _D]),
     "sdfs_sim_records_dev": (C.c_int, [_P, _P, _P, _P]),
     "sdfs_sim_paths_dev": (C.c_int, [_P, _P, C.POINTER(sdfs_sim_desc), _P, _P, _P]),
+    "sdfs_cont_sdf_mean_dev": (C.c_int, [_P, _P, _P]),
+    "sdfs_cont_sim_records_dev": (C.c_int, [_P, _P, _P, _P]),
+    "sdfs_cont_sim_paths_dev": (C.c_int, [_P, _P, C.POINTER(sdfs_cont_sim_desc), _P, _P, _P, _P, _P]),
     "sdfs_residual": (C.c_int, [_P, _D]),
     "sdfs_solve": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _I64, _I64, _D]),
     "sdfs_solve_dev": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _I64, _I64, _D]),

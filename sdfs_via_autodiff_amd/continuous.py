@@ -160,6 +160,33 @@ class ContinuousOperator(KoopmansOperator):
         self._finalizer = weakref.finalize(self, lib.sdfs_destroy, h)
         self.size = int(lib.sdfs_grid_size(h))
 
+    # -- simulated paths (simulation.simulate_continuous) ------------------------------------------------
+    def cont_sdf_mean_dev(self, w_ptr, em_ptr):
+        """E_x[M] of this operator's nodes and weights at the grid function w (device pointers, N doubles each)."""
+        check(lib.sdfs_cont_sdf_mean_dev(self._h, w_ptr, em_ptr), self._h)
+
+    def cont_sim_records_dev(self, w_ptr, em_ptr, rec_ptr):
+        """One 16-byte record {w, −ln E_x[M]} per grid point into rec_ptr (N x 2 doubles)."""
+        check(lib.sdfs_cont_sim_records_dev(self._h, w_ptr, em_ptr, rec_ptr), self._h)
+
+    def cont_sim_paths_dev(self, rec_ptr, seed, path_offset, n_paths, burn_in, n_periods, stats_ptr, clamped_ptr,
+                           final_state_ptr, step_offset=0, start=None, start_ptr=None, states_ptr=None, series_ptr=None,
+                           lookahead=0, group=0):
+        """Paths of the continuous-state model from the records (sdfs_cont_sim_paths_dev).  start: one state for every
+        path; start_ptr: a device array (n_paths, D), one state per path; neither: the zero state."""
+        d = _lib.sdfs_cont_sim_desc()
+        d.seed, d.path_offset, d.n_paths = int(seed), int(path_offset), int(n_paths)
+        d.burn_in, d.n_periods, d.step_offset = int(burn_in), int(n_periods), int(step_offset)
+        d.lookahead, d.group = int(lookahead), int(group)
+        if start_ptr is not None:
+            d.start_mode, d.start_dev = 2, start_ptr
+        elif start is not None:
+            d.start_mode = 1
+            for a, s in enumerate(start):
+                d.start[a] = float(s)
+        check(lib.sdfs_cont_sim_paths_dev(self._h, rec_ptr, C.byref(d), stats_ptr, clamped_ptr, final_state_ptr, states_ptr,
+                                          series_ptr), self._h)
+
 
 def T_fun_factory(params, method="quadrature", batch_size=10000, device=0):
     """Function factory for the operator T; ``params`` as in the reference:

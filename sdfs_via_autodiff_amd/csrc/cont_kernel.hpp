@@ -76,7 +76,12 @@ struct ContIO {
   int minus_identity;
 };
 
-enum ContMode { C_T = 0, C_TLIN = 1, C_JVP = 2 };
+// C_EM: the conditional mean of the SDF at the grid function w,
+//   E_x[M] = beta^theta (w(x) - 1)^(1 - theta) exp(-gamma (mu_c + z) + gamma^2 sigma_c(x)^2 / 2)
+//            * sum_m W_m exp(theta h_lambda'(x, m)) interp(w)(x'(x, m))^(theta - 1)
+// -- T's node sum with the exponent theta - 1 on the interpolant, -gamma where T's constant has 1 - gamma, and its own
+// epilogue; the box, the pre-contraction and the node loop are T's, so the host's box logic decides its path as it does T's.
+enum ContMode { C_T = 0, C_TLIN = 1, C_JVP = 2, C_EM = 3 };
 
 template <int D, int d, typename Idx>
 struct InterpRec {
@@ -276,7 +281,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
       wq = P.wq[m];
     }
     double pw[1];
-    pow_fast_n<true, 1>(g, P.theta, PT, pw);
+    pow_fast_n<true, 1>(g, MODE == C_EM ? P.theta - 1.0 : P.theta, PT, pw);
     if (MODE == C_JVP) acc = fma(wq * (pw[0] / g[0]), iv, acc);      // W g^(theta-1) interp(v)
     else acc = fma(wq, pw[0], acc);
   }
@@ -302,6 +307,14 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
     if (P.hcdim == d) hcval = x[d];
   }
   const double sig_c = P.phi_c * exp(hcval);
+  if (MODE == C_EM) {
+    if (lane == 0) {
+      const double gam = 1.0 - P.one_m_gamma, wx = io.w[p];          // (the descriptor carries 1 - gamma)
+      const double lc = P.theta * log(P.beta) - gam * (P.mu_c + zval) + 0.5 * gam * gam * sig_c * sig_c + P.theta_rho0 * x[0];
+      io.out[p] = wx > 1.0 ? exp(lc) * pow(wx - 1.0, 1.0 - P.theta) * e : __builtin_nan("");
+    }
+    return;
+  }
   const double C = exp(P.one_m_gamma * (P.mu_c + zval) + 0.5 * P.one_m_gamma * P.one_m_gamma * sig_c * sig_c)
                    * exp(P.theta_rho0 * x[0]);
   const double Kg[1] = {C * e};

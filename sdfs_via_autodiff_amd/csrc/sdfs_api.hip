@@ -224,6 +224,7 @@ struct sdfs_handle {
   // continuous-state operator (sdfs_create_continuous): no plan, one kernel per application
   bool cont = false;
   ContDesc cd;
+  double cont_gamma = 0.0;           // gamma as given (the descriptor carries 1 - gamma): the series of cont_sim.hpp
 
   // single-index dense form (sdfs_create_dense): H materialised, one GEMV per application
   bool dense = false;
@@ -2942,7 +2943,7 @@ int sdfs_create_continuous(int model, int ndim, const int64_t* shapes, const dou
     // dims  : h_lam, h_c, h_z, z  (ssy_wc_ratio_continuous.py:66-87)
     const double* q = params;
     h->beta = q[0]; h->theta = (1 - q[1]) / (1 - 1 / q[2]);
-    cd.one_m_gamma = 1 - q[1]; cd.mu_c = q[3]; cd.phi_c = q[6];
+    cd.one_m_gamma = 1 - q[1]; cd.mu_c = q[3]; cd.phi_c = q[6]; h->cont_gamma = q[1];
     cd.rho[0] = q[9]; cd.sconst[0] = q[12];
     cd.rho[1] = q[8]; cd.sconst[1] = q[11];
     cd.rho[2] = q[7]; cd.sconst[2] = q[10];
@@ -2955,7 +2956,7 @@ int sdfs_create_continuous(int model, int ndim, const int64_t* shapes, const dou
     // dims  : h_lam, h_c, h_z, h_zpi, z, z_pi  (gcy_wc_ratio_continuous.py:78-116)
     const double* q = params;
     h->beta = q[0]; h->theta = (1 - q[2]) / (1 - 1 / q[1]);
-    cd.one_m_gamma = 1 - q[2]; cd.mu_c = q[5]; cd.phi_c = q[6];
+    cd.one_m_gamma = 1 - q[2]; cd.mu_c = q[5]; cd.phi_c = q[6]; h->cont_gamma = q[2];
     cd.rho[0] = q[3]; cd.sconst[0] = q[4];
     cd.rho[1] = q[10]; cd.sconst[1] = q[11];
     cd.rho[2] = q[12]; cd.sconst[2] = q[13];
@@ -4168,4 +4169,5 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
 
 }  // extern "C"
 
+#include "cont_sim.hpp"    // continuous-state paths (sdfs_cont_sdf_mean_dev, sdfs_cont_sim_*), built on the definitions above
 #include "batch_api.hpp"   // the batch API (sdfs_batch_*), built on the definitions above

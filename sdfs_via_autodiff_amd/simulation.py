@@ -15,6 +15,9 @@ transitions x_{t−1} → x_t with a standard normal ξ_t (t = B+1 … B+T):
 Random numbers are Philox4x32-10 with counter (t, p, b, 0) for step t of path p, so every index can be reproduced
 (tests/sim_oracle.py is the numpy twin).  The grid work (records) and the paths (one lane each) run in libsdfs_hip.so
 (sdfs_sim_records_dev, sdfs_sim_paths_dev), fp64.  DESIGN §4.8.
+
+``simulate_continuous`` walks the continuous-state model instead (x_t = next_state(x_{t−1}, η_t), w* and −ln E_x[M]
+interpolated along the path): counter (t, p, b, 1), tests/cont_sim_oracle.py, sdfs_cont_sim_*_dev, DESIGN §4.14.
 """
 import math
 
@@ -173,4 +176,144 @@ def simulate(model, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, pa
     return out
 
 
-__all__ = ["simulate", "cdf_tables"]
+CONT_REC_BYTES = 16               # per grid point: {w, −ln E_x[M]}
+
+
+def _cont_request(model, grids, w_star, n_paths, n_periods, burn_in, seed, path_offset, step_offset, start, operator, d,
+                  return_paths):
+    """The checked request of ``simulate_continuous``; raises before any device call."""
+    kind = _kind(model)[0]                                 # (TypeError for anything but an SSY or a GCY)
+    nd = 4 if kind == "ssy" else 6
+    try:
+        grids = tuple(np.ascontiguousarray(np.asarray(g, dtype=np.float64)) for g in grids)
+    except (TypeError, ValueError):
+        raise ValueError("grids must be a sequence of 1-D axis grids") from None
+    if len(grids) != nd:
+        raise ValueError(f"{kind.upper()} has {nd} state variables, got {len(grids)} grids")
+    for a, g in enumerate(grids):
+        if g.ndim != 1 or g.size < 2 or not np.all(np.isfinite(g)) or not np.all(np.diff(g) > 0):
+            raise ValueError(f"grids[{a}] must be a finite increasing 1-D grid of at least 2 points")
+    shapes = tuple(g.size for g in grids)
+    _check_grid(w_star, shapes, "w_star")
+    P, T, B, off, sd, _, _ = _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, "stationary", 1e-10,
+                                      return_paths)
+    s0 = _count(step_offset, "step_offset", 0, (1 << 32) - 1)
+    if s0 + B + T >= 1 << 32:
+        raise ValueError(f"step_offset + burn_in + n_periods = {s0 + B + T} >= 2^32: step numbers are 32-bit")
+    if start is not None:
+        try:
+            start = np.ascontiguousarray(np.asarray(start, dtype=np.float64))
+        except (TypeError, ValueError):
+            raise ValueError("start must be None, one state (D,) or one state per path (n_paths, D)") from None
+        if start.shape not in ((nd,), (P, nd)):
+            raise ValueError(f"start has shape {start.shape}: one state ({nd},) or one per path ({P}, {nd})")
+        if not np.all(np.isfinite(start)):
+            raise ValueError("start must be finite")
+    if operator is not None:
+        from .continuous import ContinuousOperator
+        if not isinstance(operator, ContinuousOperator):
+            raise TypeError(f"operator must be a ContinuousOperator, not {type(operator).__name__}")
+        if operator.params != tuple(float(p) for p in model.params) or operator.shapes != shapes or \
+                not all(np.array_equal(a, b) for a, b in zip(operator.grids, grids)):
+            raise ValueError("operator was built on other parameters or grids than (model, grids)")
+    else:
+        d = _count(d, "d", 1, 64)
+        if d ** nd > 1 << 24:
+            raise ValueError(f"d = {d}: the tensor rule has {d ** nd} > 2^24 nodes")
+    import torch
+    if isinstance(w_star, torch.Tensor):
+        w_ok = bool(torch.all(w_star > 1.0))
+    else:
+        w_ok = bool(np.all(np.asarray(w_star, dtype=np.float64) > 1.0))
+    if not w_ok:
+        raise ValueError("w_star must exceed 1 at every grid point (the log return needs ln(w - 1))")
+    return kind, grids, shapes, P, T, B, off, sd, s0, start, d
+
+
+def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, seed=0, path_offset=0, step_offset=0,
+                        start=None, operator=None, d=5, return_paths=False, device=0):
+    """Simulate ``n_paths`` paths (numbered path_offset … path_offset + n_paths − 1) of the continuous-state model:
+    x_t = next_state(x_{t−1}, η_t) with standard normal η_t, the grid function ``w_star`` (on ``grids``, as
+    ``wc_ratio_continuous`` returns them) and −ln E_x[M] interpolated multilinearly along the path, the coordinates
+    clamped to the grid as ``lin_interp`` clamps them.  After ``burn_in`` steps, ``n_periods`` steps are recorded:
+
+        dc_t = μ_c + z_{t−1} + φ_c exp(h_c,t−1) ξ_t
+        m_t  = θ ln β + θ h_λ,t − γ dc_t + (θ−1)(ln ŵ(x_t) − ln(ŵ(x_{t−1}) − 1))
+        rf_t = r̂f(x_{t−1}),  rc_t = dc_t + ln ŵ(x_t) − ln(ŵ(x_{t−1}) − 1),  xc_t = rc_t − rf_t,  wc_t = ŵ(x_t)
+
+    start: None (the zero state), one state (D,) or one per path (P, D).  operator: a ``ContinuousOperator`` on these
+    parameters and grids, whose nodes and weights define E_x[M]; otherwise one is built with ``qnwnorm([d] * D)``.
+    step_offset: the run's steps are numbered step_offset + 1 …, so that a run continued from ``final_state`` with
+    step_offset = the steps already taken draws the random numbers the longer run would have drawn.
+
+    Returns the dict of ``simulate`` ("series", "per_path", "summary", "pooled") for dc, m, rf, rc, xc, wc (slope: xc_t
+    on ln(ŵ(x_{t−1}) − 1)) and "clamped" = {"per_path": share of the recorded steps whose x_t lay outside the grid on
+    some axis, "summary"}, "final_state" (P, D), "E_M" on the grid, and with ``return_paths`` "paths" = {"state":
+    (P, T+1, D) for t = B … B+T, name: (P, T)}.  Random numbers are Philox4x32-10 with counter (t, p, b, 1)
+    (tests/cont_sim_oracle.py is the numpy twin).  A path's result depends only on its number, the seed, step_offset,
+    its start and the model.  DESIGN §4.14."""
+    import torch
+    from .continuous import ContinuousOperator, qnwnorm
+    kind, grids, shapes, P, T, B, off, sd, s0, start, d = _cont_request(
+        model, grids, w_star, n_paths, n_periods, burn_in, seed, path_offset, step_offset, start, operator, d, return_paths)
+    nd = len(shapes)
+    ns = len(SERIES)
+    N = int(np.prod(shapes))
+    need = N * (CONT_REC_BYTES + 16) + (3 * ns + 1) * P * 8 + P * 4 + 2 * P * nd * 8
+    if return_paths:
+        need += P * T * ns * 8 + P * (T + 1) * nd * 8
+    devno = operator.device if operator is not None else int(device)
+    dev = torch.device("cuda", devno)
+    free = torch.cuda.mem_get_info(dev)[0]
+    if need > free:
+        raise ValueError(f"the per-point records and outputs need {need / 2**30:.2f} GiB, {free / 2**30:.2f} GiB of "
+                         "device memory is free")
+    op = operator
+    if op is None:
+        nodes, weights = qnwnorm([d] * nd)
+        op = ContinuousOperator(np.array(model.params), grids, np.ascontiguousarray(nodes.T), weights, device=devno)
+    w = _device_grid(op, w_star, "w_star")
+    em = torch.empty_like(w)
+    rec = torch.empty((N, 2), dtype=torch.float64, device=dev)
+    stats = torch.empty((3 * ns + 1, P), dtype=torch.float64, device=dev)
+    clamped = torch.empty((P,), dtype=torch.int32, device=dev)
+    final = torch.empty((P, nd), dtype=torch.float64, device=dev)
+    start_dev = states = ser = None
+    if start is not None and start.ndim == 2:
+        start_dev = torch.from_numpy(start).to(dev)
+    if return_paths:
+        states = torch.empty((P, T + 1, nd), dtype=torch.float64, device=dev)
+        ser = torch.empty((ns, P, T), dtype=torch.float64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()           # (the library runs on the operator's own stream)
+    op.cont_sdf_mean_dev(w.data_ptr(), em.data_ptr())
+    op.cont_sim_records_dev(w.data_ptr(), em.data_ptr(), rec.data_ptr())
+    op.cont_sim_paths_dev(rec.data_ptr(), sd, off, P, B, T, stats.data_ptr(), clamped.data_ptr(), final.data_ptr(),
+                          step_offset=s0, start=start if start is not None and start.ndim == 1 else None,
+                          start_ptr=start_dev.data_ptr() if start_dev is not None else None,
+                          states_ptr=states.data_ptr() if states is not None else None,
+                          series_ptr=ser.data_ptr() if ser is not None else None)
+    op.synchronize()
+    st = stats.cpu().numpy()
+    per_path = {nm: {s: st[3 * i + j] for j, s in enumerate(STATS)} for i, nm in enumerate(SERIES)}
+    per_path["slope"] = st[3 * ns]
+    summary = {nm: {s: _summary(per_path[nm][s]) for s in STATS} for nm in SERIES}
+    summary["slope"] = _summary(per_path["slope"])
+    pooled = {}
+    for nm in SERIES:
+        m = per_path[nm]["mean"]
+        pooled[nm] = {"mean": float(m.mean()), "se": float(m.std(ddof=1) / math.sqrt(P)) if P > 1 else float("nan")}
+    share = clamped.cpu().numpy().astype(np.float64) / T
+    out = {"series": SERIES, "per_path": per_path, "summary": summary, "pooled": pooled,
+           "clamped": {"per_path": share, "summary": _summary(share)}, "final_state": final.cpu().numpy(),
+           "E_M": em.cpu().numpy()}
+    if return_paths:
+        s = ser.cpu().numpy()
+        paths = {"state": states.cpu().numpy()}
+        for i, nm in enumerate(SERIES):
+            paths[nm] = s[i]
+        out["paths"] = paths
+    del rec
+    return out
+
+
+__all__ = ["simulate", "simulate_continuous", "cdf_tables"]
