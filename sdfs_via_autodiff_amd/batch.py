@@ -844,21 +844,12 @@ def _sim_fields(names, mom, stats, index, paths):
 
     def triple(k):
         return {"n": mom[:, k, 0].copy(), "mean": mom[:, k, 1].copy(), "se": mom[:, k, 2].copy()}
-    moments = {nm: {s: triple(3 * i + j) for j, s in enumerate(sim.STATS)} for i, nm in enumerate(names)}
-    moments["slope"] = triple(3 * len(names))
-    per_path = None
-    if stats is not None:
-        def entry(k):
-            sm = [sim._summary(row) for row in stats[:, k]]
-            return {"values": stats[:, k], **{q: np.array([x[q] for x in sm]) for q in ("median", "p05", "p95")}}
-        per_path = {nm: {s: entry(3 * i + j) for j, s in enumerate(sim.STATS)} for i, nm in enumerate(names)}
-        per_path["slope"] = entry(3 * len(names))
-    out_paths = None
-    if paths is not None:
-        out_paths = {"index": index}
-        for i, nm in enumerate(names):
-            out_paths[nm] = paths[:, i]
-    return moments, per_path, out_paths
+
+    def entry(k):
+        sm = [sim._summary(row) for row in stats[:, k]]
+        return {"values": stats[:, k], **{q: np.array([x[q] for x in sm]) for q in ("median", "p05", "p95")}}
+    return (sim._by_statistic(names, triple), None if stats is None else sim._by_statistic(names, entry),
+            None if paths is None else sim._named_paths({"index": index}, names, paths))
 
 
 def simulate_batch(models, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, path_offset=0, start="stationary",

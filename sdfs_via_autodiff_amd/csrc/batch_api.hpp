@@ -659,31 +659,6 @@ batch_sim_fn batch_sim_kernel_for(int ndim, bool kap, bool ldsrec, bool store, i
   return kap ? batch_sim_kernel_of<6, true>(ldsrec, store, k) : batch_sim_kernel_of<6, false>(ldsrec, store, k);
 }
 
-// offsets of a member's table block into `a` (with the request's scalars); *ncdf, *ncdf0: doubles of the cumulative rows
-// and of the cumulative marginals of one member.  Returns the axis of a bad start index, or -1.
-int batch_sim_layout(const BatchDesc& D, int ax_lam, int ax_c, const sdfs_batch_sim_desc* d, SimArgs& a, int* ncdf, int* ncdf0) {
-  int off = 0, bad = -1;
-  for (int ax = 0; ax < D.ndim; ++ax) {
-    a.n[ax] = D.n[ax]; a.stride[ax] = D.stride[ax];
-    a.cdf_off[ax] = off; off += D.n[ax] * D.n[ax];
-    if (d->start_fixed && (d->start[ax] < 0 || d->start[ax] >= D.n[ax]) && bad < 0) bad = ax;
-    a.start[ax] = d->start_fixed ? d->start[ax] : 0;
-  }
-  *ncdf = off;
-  *ncdf0 = 0;
-  for (int ax = 0; ax < D.ndim; ++ax) { a.cdf0_off[ax] = off; off += D.n[ax]; *ncdf0 += D.n[ax]; }
-  a.ax_lam = ax_lam; a.ax_c = ax_c;
-  a.hl_off = off; off += D.n[ax_lam];
-  a.sc_off = off; off += D.n[ax_c];
-  a.lds_n = off;
-  a.start_fixed = d->start_fixed ? 1 : 0;
-  a.key0 = (unsigned)(d->seed & 0xffffffffu); a.key1 = (unsigned)(d->seed >> 32);
-  a.path0 = (unsigned long long)d->path_offset;
-  a.n_paths = d->n_paths;
-  a.burn_in = (unsigned)d->burn_in; a.n_periods = (unsigned)d->n_periods;
-  return bad;
-}
-
 // the table blocks [B][words], the scalars [B][4] = theta, theta ln beta, gamma, kappa and the skip flags [B] of a request,
 // from the members' host fields (h_lambda [B][n_lam], sigma_c [B][n_c], theta, beta, gamma [B]).  Host only.
 void batch_sim_stage(const BatchDesc& D, const SimArgs& a, int ncdf, int ncdf0, int words, int B, const sdfs_batch_sim_desc* d,
@@ -692,12 +667,8 @@ void batch_sim_stage(const BatchDesc& D, const SimArgs& a, int ncdf, int ncdf0, 
   const int nl = D.n[a.ax_lam], nc = D.n[a.ax_c];
   std::fill(tb, tb + (size_t)B * words, 0.0);
   for (int b = 0; b < B; ++b) {
-    double* const t = tb + (size_t)b * words;
-    std::copy(d->cdf + (size_t)b * ncdf, d->cdf + (size_t)(b + 1) * ncdf, t);
-    if (d->start_fixed) std::fill(t + ncdf, t + ncdf + ncdf0, 2.0);
-    else std::copy(d->cdf0 + (size_t)b * ncdf0, d->cdf0 + (size_t)(b + 1) * ncdf0, t + ncdf);
-    std::copy(hlam + (size_t)b * nl, hlam + (size_t)(b + 1) * nl, t + a.hl_off);
-    std::copy(sigc + (size_t)b * nc, sigc + (size_t)(b + 1) * nc, t + a.sc_off);
+    sim_fill_table(a, ncdf, ncdf0, d->cdf + (size_t)b * ncdf, d->start_fixed ? nullptr : d->cdf0 + (size_t)b * ncdf0, hlam + (size_t)b * nl,
+                   sigc + (size_t)b * nc, tb + (size_t)b * words);
     const int skip = d->skip && d->skip[b] ? 1 : 0;
     if (sk) sk[b] = skip;
     sc[4 * b] = theta[b]; sc[4 * b + 1] = theta[b] * std::log(beta[b]); sc[4 * b + 2] = gam[b];
@@ -759,7 +730,7 @@ int64_t sdfs_batch_sim_tables(int model, int ndim, const int64_t* shapes, int64_
   }
   SimArgs a{};
   int ncdf = 0, ncdf0 = 0;
-  if (batch_sim_layout(D, c.ax_lam, c.ax_c, d, a, &ncdf, &ncdf0) >= 0) return no(SDFS_ERR_ARG, "start is not a state index");
+  if (sim_layout(D.ndim, D.n, D.stride, c.ax_lam, c.ax_c, d, a, &ncdf, &ncdf0) >= 0) return no(SDFS_ERR_ARG, "start is not a state index");
   batch_sim_stage(D, a, ncdf, ncdf0, words, (int)B, d, hl.data(), sg.data(), th.data(), be.data(), ga.data(), tab_out, scal_out, nullptr);
   return words;
 }
@@ -786,12 +757,8 @@ int sdfs_batch_sim_paths_dev(sdfs_batch* h, const double* records_dev, const sdf
   if (!records_dev || !d) return bfail(h, SDFS_ERR_ARG, "NULL records or desc");
   if (!stats_dev && !moments_dev) return bfail(h, SDFS_ERR_ARG, "stats_dev and moments_dev are both NULL: nothing to write");
   if (!idx_dev != !series_dev) return bfail(h, SDFS_ERR_ARG, "idx and series are stored together: both NULL or neither");
-  if (d->n_paths < 1 || d->path_offset < 0 || d->path_offset + d->n_paths > (1LL << 32))
-    return bfail(h, SDFS_ERR_ARG, "paths %lld ... %lld: numbers lie in 0 ... 2^32 - 1", (long long)d->path_offset,
-                 (long long)(d->path_offset + d->n_paths - 1));
-  if (d->n_periods < 2 || d->burn_in < 0 || d->burn_in + d->n_periods >= (1LL << 32) - 8)
-    return bfail(h, SDFS_ERR_ARG, "burn_in = %lld, n_periods = %lld: T >= 2 and B + T < 2^32 - 8", (long long)d->burn_in,
-                 (long long)d->n_periods);
+  char msg[160];
+  if (!sim_ranges_ok(msg, d->path_offset, d->n_paths, nullptr, d->burn_in, d->n_periods, 8)) return bfail(h, SDFS_ERR_ARG, "%s", msg);
   if (!d->cdf || (!d->start_fixed && !d->cdf0)) return bfail(h, SDFS_ERR_ARG, "NULL cumulative transition table");
   if (d->has_kappa && !d->kappa) return bfail(h, SDFS_ERR_ARG, "has_kappa needs kappa[B]");
   if (d->records < 0 || d->records > 2) return bfail(h, SDFS_ERR_ARG, "records = %d: 0 (default), 1 (LDS) or 2 (global)", d->records);
@@ -816,7 +783,7 @@ int sdfs_batch_sim_paths_dev(sdfs_batch* h, const double* records_dev, const sdf
   // the members' table blocks, scalars and skip flags
   SimArgs a{};
   int ncdf = 0, ncdf0 = 0;
-  const int bad = batch_sim_layout(D, h->ax_lam, h->ax_c, d, a, &ncdf, &ncdf0);
+  const int bad = sim_layout(D.ndim, D.n, D.stride, h->ax_lam, h->ax_c, d, a, &ncdf, &ncdf0);
   if (bad >= 0) return bfail(h, SDFS_ERR_ARG, "start[%d] = %d: a state index of axis %d lies in 0 ... %d", bad, d->start[bad], bad, D.n[bad] - 1);
   // the previous call's uploads read the staging vectors: wait for them (not for the stream's kernels)
   if (h->sim_staged) BHIPCHK(h, hipEventSynchronize(h->sim_staged));

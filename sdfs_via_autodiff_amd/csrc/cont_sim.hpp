@@ -380,12 +380,8 @@ int sdfs_cont_sim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_cont_s
   if ((rc = cont_handle_ok(h, "sdfs_cont_sim_paths_dev"))) return rc;
   if (!rec || !d || !stats || !clamped || !final_state) return fail(h, SDFS_ERR_ARG, "NULL records, desc, stats, clamped or final_state");
   if (!states != !series) return fail(h, SDFS_ERR_ARG, "states and series are stored together: both NULL or neither");
-  if (d->n_paths < 1 || d->path_offset < 0 || d->path_offset + d->n_paths > (1LL << 32))
-    return fail(h, SDFS_ERR_ARG, "paths %lld ... %lld: numbers lie in 0 ... 2^32 - 1", (long long)d->path_offset,
-                (long long)(d->path_offset + d->n_paths - 1));
-  if (d->n_periods < 2 || d->burn_in < 0 || d->step_offset < 0 || d->step_offset + d->burn_in + d->n_periods >= (1LL << 32))
-    return fail(h, SDFS_ERR_ARG, "step_offset = %lld, burn_in = %lld, n_periods = %lld: T >= 2 and s0 + B + T < 2^32",
-                (long long)d->step_offset, (long long)d->burn_in, (long long)d->n_periods);
+  char msg[160];
+  if (!sim_ranges_ok(msg, d->path_offset, d->n_paths, &d->step_offset, d->burn_in, d->n_periods, 0)) return fail(h, SDFS_ERR_ARG, "%s", msg);
   if (d->start_mode < 0 || d->start_mode > 2 || (d->start_mode == 2 && !d->start_dev))
     return fail(h, SDFS_ERR_ARG, "start_mode = %d: 0 (zero state), 1 (start[]) or 2 (start_dev, not NULL)", d->start_mode);
   const ContDesc& cd = h->cd;

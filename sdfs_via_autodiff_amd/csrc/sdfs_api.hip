@@ -34,6 +34,7 @@
 #include "sens_kernels.hpp"
 #include "price_kernels.hpp"
 #include "sim_kernels.hpp"
+#include "sim_host.hpp"
 #include "batch_kernels.hpp"
 #include "batch_newton.hpp"
 #include "batch_adjoint.hpp"
@@ -3611,12 +3612,8 @@ int sdfs_sim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_sim_desc* d
   if ((rc = sim_handle_ok(h, "sdfs_sim_paths_dev"))) return rc;
   if (!rec || !d || !stats) return fail(h, SDFS_ERR_ARG, "NULL records, desc or stats");
   if (!idx != !ser) return fail(h, SDFS_ERR_ARG, "idx and series are stored together: both NULL or neither");
-  if (d->n_paths < 1 || d->path_offset < 0 || d->path_offset + d->n_paths > (1LL << 32))
-    return fail(h, SDFS_ERR_ARG, "paths %lld ... %lld: numbers lie in 0 ... 2^32 - 1", (long long)d->path_offset,
-                (long long)(d->path_offset + d->n_paths - 1));
-  if (d->n_periods < 2 || d->burn_in < 0 || d->burn_in + d->n_periods >= (1LL << 32))
-    return fail(h, SDFS_ERR_ARG, "burn_in = %lld, n_periods = %lld: T >= 2 and B + T < 2^32", (long long)d->burn_in,
-                (long long)d->n_periods);
+  char msg[160];
+  if (!sim_ranges_ok(msg, d->path_offset, d->n_paths, nullptr, d->burn_in, d->n_periods, 0)) return fail(h, SDFS_ERR_ARG, "%s", msg);
   if (d->has_kappa && !std::isfinite(d->kappa)) return fail(h, SDFS_ERR_ARG, "kappa is not finite");
   if (!d->cdf || (!d->start_fixed && !d->cdf0)) return fail(h, SDFS_ERR_ARG, "NULL cumulative transition table");
   const int k = d->lookahead ? d->lookahead : SIM_K_DEFAULT;
@@ -3627,39 +3624,17 @@ int sdfs_sim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_sim_desc* d
     return fail(h, SDFS_ERR_ARG, "stored paths run with the default lookahead and search");
   const auto& S = h->sens;
   SimArgs a{};
+  int stride[SIM_MAXD], ncdf = 0, ncdf0 = 0;
+  long long st = 1;
+  for (int ax = h->ndim - 1; ax >= 0; --ax) { stride[ax] = (int)st; st *= h->shape[ax]; }
+  const int bad = sim_layout(h->ndim, h->shape, stride, S.ax_a1, S.ax_a2, d, a, &ncdf, &ncdf0);
+  if (bad >= 0)
+    return fail(h, SDFS_ERR_ARG, "start[%d] = %d: a state index of axis %d lies in 0 ... %d", bad, d->start[bad], bad, h->shape[bad] - 1);
+  if (a.lds_n > SIM_TAB_MAX) return fail(h, SDFS_ERR_ARG, "LDS table of %d doubles", a.lds_n);
   auto& tb = h->sim.tab_host;
   HIPCHK(h, hipStreamSynchronize(h->stream));   // (the previous call's staging copy may still be in flight)
-  tb.clear();
-  size_t ci = 0, c0 = 0;
-  for (int ax = 0; ax < h->ndim; ++ax) {
-    const int n = h->shape[ax];
-    a.n[ax] = n;
-    a.cdf_off[ax] = (int)tb.size();
-    tb.insert(tb.end(), d->cdf + ci, d->cdf + ci + (size_t)n * n);
-    ci += (size_t)n * n;
-    if (d->start_fixed && (d->start[ax] < 0 || d->start[ax] >= n))
-      return fail(h, SDFS_ERR_ARG, "start[%d] = %d: a state index of axis %d lies in 0 ... %d", ax, d->start[ax], ax, n - 1);
-    a.start[ax] = d->start_fixed ? d->start[ax] : 0;
-  }
-  for (int ax = 0; ax < h->ndim; ++ax) {
-    const int n = h->shape[ax];
-    a.cdf0_off[ax] = (int)tb.size();
-    if (d->start_fixed) tb.insert(tb.end(), (size_t)n, 2.0);
-    else tb.insert(tb.end(), d->cdf0 + c0, d->cdf0 + c0 + n);
-    c0 += n;
-  }
-  long long st = 1;
-  for (int ax = h->ndim - 1; ax >= 0; --ax) { a.stride[ax] = (int)st; st *= h->shape[ax]; }
-  a.ax_lam = S.ax_a1; a.ax_c = S.ax_a2;
-  a.hl_off = (int)tb.size(); tb.insert(tb.end(), S.hlam.begin(), S.hlam.end());
-  a.sc_off = (int)tb.size(); tb.insert(tb.end(), S.sigc.begin(), S.sigc.end());
-  a.lds_n = (int)tb.size();
-  if (a.lds_n > SIM_TAB_MAX) return fail(h, SDFS_ERR_ARG, "LDS table of %d doubles", a.lds_n);
-  a.start_fixed = d->start_fixed ? 1 : 0;
-  a.key0 = (unsigned)(d->seed & 0xffffffffu); a.key1 = (unsigned)(d->seed >> 32);
-  a.path0 = (unsigned long long)d->path_offset;
-  a.n_paths = d->n_paths;
-  a.burn_in = (unsigned)d->burn_in; a.n_periods = (unsigned)d->n_periods;
+  tb.resize((size_t)a.lds_n);
+  sim_fill_table(a, ncdf, ncdf0, d->cdf, d->start_fixed ? nullptr : d->cdf0, S.hlam.data(), S.sigc.data(), tb.data());
   a.theta = h->theta; a.theta_ln_beta = h->theta * std::log(h->beta); a.gamma = S.gamma; a.kappa = d->has_kappa ? d->kappa : 0.0;
   if (!h->sim.tab && (rc = dev_alloc(h, &h->sim.tab, SIM_TAB_MAX))) return rc;
   HIPCHK(h, hipMemcpyAsync(h->sim.tab, tb.data(), sizeof(double) * tb.size(), hipMemcpyHostToDevice, h->stream));

@@ -68,6 +68,39 @@ def _summary(a):
             "p95": float(np.percentile(ok, 95))}
 
 
+def _by_statistic(names, entry):
+    """{name: {"mean" | "std" | "ac1": entry(row)}, "slope": entry(3 nser)}: the rows of a statistics array, named."""
+    out = {nm: {s: entry(3 * i + j) for j, s in enumerate(STATS)} for i, nm in enumerate(names)}
+    out["slope"] = entry(3 * len(names))
+    return out
+
+
+def _named_paths(first, names, series):
+    """The "paths" of a result: its first entry (indices or states), then series[..., i, :, :] under names[i]."""
+    return {**first, **{nm: series[..., i, :, :] for i, nm in enumerate(names)}}
+
+
+def _result(names, st, P):
+    """The dict ``simulate`` returns (without "paths") from the (3 nser + 1, P) statistics ``st``."""
+    per_path = _by_statistic(names, lambda k: st[k])
+    summary = _by_statistic(names, lambda k: _summary(st[k]))
+    pooled = {}
+    for nm in names:
+        m = per_path[nm]["mean"]
+        pooled[nm] = {"mean": float(m.mean()), "se": float(m.std(ddof=1) / math.sqrt(P)) if P > 1 else float("nan")}
+    return {"series": names, "per_path": per_path, "summary": summary, "pooled": pooled}
+
+
+def _check_w_star(w_star):
+    import torch
+    if isinstance(w_star, torch.Tensor):
+        w_ok = bool(torch.all(w_star > 1.0))
+    else:
+        w_ok = bool(np.all(np.asarray(w_star, dtype=np.float64) > 1.0))
+    if not w_ok:
+        raise ValueError("w_star must exceed 1 at every grid point (the log return needs ln(w - 1))")
+
+
 def _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol, return_paths, members=1, check_kappa=None):
     """The checked request of ``simulate`` (and of the batch's): (P, T, B, path_offset, seed, rtol, fixed start or None)."""
     P = _count(n_paths, "n_paths", 1, 1 << 32)
@@ -120,12 +153,7 @@ def simulate(model, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, pa
     P, T, B, off, sd, rtol, fixed = _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol,
                                              return_paths, check_kappa=lambda: kappa is None or _kappa(kappa))
     k = None if kappa is None else _kappa(kappa)
-    if isinstance(w_star, torch.Tensor):
-        w_ok = bool(torch.all(w_star > 1.0))
-    else:
-        w_ok = bool(np.all(np.asarray(w_star, dtype=np.float64) > 1.0))
-    if not w_ok:
-        raise ValueError("w_star must exceed 1 at every grid point (the log return needs ln(w - 1))")
+    _check_w_star(w_star)
     arr = _kind(model)[2](model, shapes)
     cdf, cdf0 = cdf_tables(model, shapes, arr)          # (ValueError when the chain does not factorise)
     names = SERIES_KAPPA if k is not None else SERIES
@@ -156,22 +184,9 @@ def simulate(model, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, pa
                      None if fixed is not None else np.concatenate(cdf0), sd, off, P, B, T, kappa=k, start=fixed,
                      stats_ptr=stats.data_ptr(), idx_ptr=idx.data_ptr() if idx is not None else None,
                      series_ptr=ser.data_ptr() if ser is not None else None)
-    st = stats.cpu().numpy()
-    per_path = {nm: {s: st[3 * i + j] for j, s in enumerate(STATS)} for i, nm in enumerate(names)}
-    per_path["slope"] = st[3 * ns]
-    summary = {nm: {s: _summary(per_path[nm][s]) for s in STATS} for nm in names}
-    summary["slope"] = _summary(per_path["slope"])
-    pooled = {}
-    for nm in names:
-        m = per_path[nm]["mean"]
-        pooled[nm] = {"mean": float(m.mean()), "se": float(m.std(ddof=1) / math.sqrt(P)) if P > 1 else float("nan")}
-    out = {"series": names, "per_path": per_path, "summary": summary, "pooled": pooled}
+    out = _result(names, stats.cpu().numpy(), P)
     if return_paths:
-        s = ser.cpu().numpy()
-        paths = {"index": idx.cpu().numpy()}
-        for i, nm in enumerate(names):
-            paths[nm] = s[i]
-        out["paths"] = paths
+        out["paths"] = _named_paths({"index": idx.cpu().numpy()}, names, ser.cpu().numpy())
     del rec
     return out
 
@@ -220,13 +235,7 @@ def _cont_request(model, grids, w_star, n_paths, n_periods, burn_in, seed, path_
         d = _count(d, "d", 1, 64)
         if d ** nd > 1 << 24:
             raise ValueError(f"d = {d}: the tensor rule has {d ** nd} > 2^24 nodes")
-    import torch
-    if isinstance(w_star, torch.Tensor):
-        w_ok = bool(torch.all(w_star > 1.0))
-    else:
-        w_ok = bool(np.all(np.asarray(w_star, dtype=np.float64) > 1.0))
-    if not w_ok:
-        raise ValueError("w_star must exceed 1 at every grid point (the log return needs ln(w - 1))")
+    _check_w_star(w_star)
     return kind, grids, shapes, P, T, B, off, sd, s0, start, d
 
 
@@ -293,25 +302,12 @@ def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, 
                           states_ptr=states.data_ptr() if states is not None else None,
                           series_ptr=ser.data_ptr() if ser is not None else None)
     op.synchronize()
-    st = stats.cpu().numpy()
-    per_path = {nm: {s: st[3 * i + j] for j, s in enumerate(STATS)} for i, nm in enumerate(SERIES)}
-    per_path["slope"] = st[3 * ns]
-    summary = {nm: {s: _summary(per_path[nm][s]) for s in STATS} for nm in SERIES}
-    summary["slope"] = _summary(per_path["slope"])
-    pooled = {}
-    for nm in SERIES:
-        m = per_path[nm]["mean"]
-        pooled[nm] = {"mean": float(m.mean()), "se": float(m.std(ddof=1) / math.sqrt(P)) if P > 1 else float("nan")}
     share = clamped.cpu().numpy().astype(np.float64) / T
-    out = {"series": SERIES, "per_path": per_path, "summary": summary, "pooled": pooled,
-           "clamped": {"per_path": share, "summary": _summary(share)}, "final_state": final.cpu().numpy(),
-           "E_M": em.cpu().numpy()}
+    out = _result(SERIES, stats.cpu().numpy(), P)
+    out.update({"clamped": {"per_path": share, "summary": _summary(share)}, "final_state": final.cpu().numpy(),
+                "E_M": em.cpu().numpy()})
     if return_paths:
-        s = ser.cpu().numpy()
-        paths = {"state": states.cpu().numpy()}
-        for i, nm in enumerate(SERIES):
-            paths[nm] = s[i]
-        out["paths"] = paths
+        out["paths"] = _named_paths({"state": states.cpu().numpy()}, SERIES, ser.cpu().numpy())
     del rec
     return out
 

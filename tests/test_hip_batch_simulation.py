@@ -166,6 +166,63 @@ def every_member_matches_the_twin(S, kind, shapes, start, burn_in, kappa, models
     return r, worst
 
 
+# -- (1b) every look-ahead of the global form, and runs shorter than the ring -------------------------------------------------
+@pytest.mark.parametrize("kind,shapes", SMALL[:2], ids=sid)
+@pytest.mark.parametrize("n_periods", [2, 3, 9])
+@pytest.mark.parametrize("kappa", [None, 2.0])
+def test_every_lookahead_matches_the_twin(S, kind, shapes, n_periods, kappa):
+    """``simulate_dev`` with the records gathered at look-ahead 1 and 4, with and without a claim, 300 paths (a partial workgroup) and runs shorter
+    than, as long as and no multiple of the ring.  These forms store no path: their per-path statistics are held against
+    the twin's (1e-9) and their statistics and moments against the default form's bit for bit (the forms agree in every
+    bit at the parent commit too, as tools/batch_simulation_times.py asserts of the moments); the default form, which
+    stores, gives the indices (exact) and series (1e-12) of these run lengths."""
+    import torch
+    from sdfs_via_autodiff_amd.batch import batch_cdf_tables
+    from sdfs_via_autodiff_amd.simulation import cdf_tables
+    ids, Pn, Bn, off = IDS[:3], 300, 3, 123
+    models, w = family(S, kind, ids), solved(S, kind, shapes)[:3]
+    disc = S.discretize_ssy if kind == "ssy" else S.discretize_gcy
+    op = S.BatchOperator.from_models(models, shapes)
+    try:
+        grids = op.price(w, kappa, return_grids=True)[2]
+        wd, em = (op._to_dev(np.ascontiguousarray(x, dtype=np.float64)) for x in (w, grids["E_M"]))
+        pd = op._to_dev(np.ascontiguousarray(grids["pd"], dtype=np.float64)) if kappa is not None else None
+        dev = wd.device
+        rec = torch.empty((3, op.size, 8), dtype=torch.float64, device=dev)
+        cdf, cdf0 = batch_cdf_tables(kind, shapes, op._arrays)
+        ns, nd = 9 if kappa is not None else 6, len(shapes)
+
+        def run_form(k, store):
+            st = torch.full((3, 3 * ns + 1, Pn), -7.0, dtype=torch.float64, device=dev)
+            mom = torch.full((3, 3 * ns + 1, 3), -7.0, dtype=torch.float64, device=dev)
+            idx = torch.empty((3, Pn, n_periods + 1, nd), dtype=torch.uint8, device=dev) if store else None
+            ser = torch.empty((3, ns, Pn, n_periods), dtype=torch.float64, device=dev) if store else None
+            torch.cuda.synchronize()
+            op.simulate_dev(wd.data_ptr(), em.data_ptr(), None if pd is None else pd.data_ptr(), rec.data_ptr(), cdf, cdf0, Pn, n_periods, burn_in=Bn,
+                            seed=SEED, path_offset=off, kappa=None if kappa is None else np.full(3, kappa), records=2, lookahead=k, stats_ptr=st.data_ptr(),
+                            moments_ptr=mom.data_ptr(), idx_ptr=None if idx is None else idx.data_ptr(),
+                            series_ptr=None if ser is None else ser.data_ptr())
+            op.synchronize()
+            return st.cpu().numpy(), mom.cpu().numpy(), None if idx is None else idx.cpu().numpy(), None if ser is None else ser.cpu().numpy()
+        st0, mom0, idx0, ser0 = run_form(0, True)
+        forms = {k: run_form(k, False) for k in (1, 4)}
+    finally:
+        op.close()
+    for b, m in enumerate(models):
+        arr = disc(m, shapes)
+        c, c0 = cdf_tables(m, shapes, arr)
+        idx, ser, stats = so.simulate(kind, m.params, arr, shapes, c, c0, w[b], grids["E_M"][b], grids["pd"][b] if kappa is not None else None, kappa,
+                                      seed=SEED, path_offset=off, n_paths=Pn, burn_in=Bn, n_periods=n_periods)
+        assert np.array_equal(idx0[b], idx), b
+        for i, nm in enumerate(ser):
+            assert close(ser0[b, i], ser[nm], 1.0) <= 1e-12, (b, nm)
+        want = np.stack([stats[nm][s] for nm in ser for s in STATS] + [stats["slope"]])
+        for k, (st, mom, _, _) in forms.items():
+            print(f"member {b} lookahead {k}: statistics vs twin {close(st[b], want, 1.0):.3e}")
+            assert close(st[b], want, 1.0) <= 1e-9, (b, k)
+            assert same(st[b], st0[b]) and same(mom[b], mom0[b]), (b, k)
+
+
 # -- (2) against simulate ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind,shapes", SMALL[:2] + [BIG], ids=sid)
 def test_members_match_simulate(S, kind, shapes):

@@ -217,6 +217,58 @@ def test_states_series_and_statistics_match_the_twin(S, kind, sizes, sd, burn_in
     check_against_twin(S, grids, w, out, tw)
 
 
+@pytest.mark.parametrize("kind,sizes,sd", [CC.GRIDS[0], CC.GRIDS[5]], ids=[GRID_IDS[0], GRID_IDS[5]])
+@pytest.mark.parametrize("n_periods", [2, 3, 9])
+def test_every_lookahead_and_group_gives_the_default_forms_bits(S, kind, sizes, sd, n_periods):
+    """sdfs_cont_sim_paths_dev with look-ahead 1, 2, 4 and groups of 4, 8 and (6-D, look-ahead <= 2) 16 corners, at 300
+    paths (a partial block) and runs shorter than, as long as and no multiple of the look-ahead.  These forms store no
+    path; cont_sim.hpp promises that the copies of a step round alike, so their statistics, clamped counts and final
+    states are the default form's bit for bit.  The default form, which stores, is held against the twin with the bound
+    of the test above (states and series), and its statistics against the two-pass values of its own series (1e-10)."""
+    import torch
+    m, par, grids, op, w, em = fixed_point(S, kind, sizes, sd)
+    Pn, Bn, D = 300, 3, len(grids)
+    st0 = CC.start_of(grids, "vector")
+    kw = dict(burn_in=Bn, seed=CC.SEED, path_offset=CC.PATH_OFFSET, start=st0)
+    out = S.simulate_continuous(m, grids, w, Pn, n_periods, operator=op, return_paths=True, **kw)
+    tw = co.simulate(kind, par, grids, w, em, n_paths=Pn, n_periods=n_periods, **kw)
+    worst = {"state": co.close(out["paths"]["state"], tw["state"], 1.0),
+             "series": max(co.close(out["paths"][nm], tw["series"][nm], 1.0) for nm in co.SERIES)}
+    print(f"device vs twin: states {worst['state']:.3e}, series {worst['series']:.3e}")
+    assert worst["state"] <= BOUND and worst["series"] <= BOUND, worst
+    for nm in co.SERIES:
+        mean, sd_, ac1 = so.two_pass(out["paths"][nm])
+        pp = out["per_path"][nm]
+        floor_mean = 1e-3 * np.max(np.abs(out["paths"][nm]), axis=1)
+        for a, b, floor in ((pp["mean"], mean, floor_mean), (pp["std"], sd_, 0.0), (pp["ac1"], ac1, 1e-2)):
+            assert rel_err(a, b, floor) <= 1e-10, nm
+    # ... and the slope against the two-pass OLS value at the device's own states (check_against_twin's bound and floor)
+    prv = np.ascontiguousarray(out["paths"]["state"][:, :-1, :].reshape(-1, D).T)
+    xr = np.log(S.lin_interp(prv, w, grids).reshape(Pn, n_periods) - 1.0)
+    slope = rel_err(out["per_path"]["slope"], so.ols_slope(xr, out["paths"]["xc"]), 1e-2)
+    print(f"slope vs two-pass OLS: {slope:.3e}")
+    assert slope <= 1e-10, slope
+    default = np.stack([out["per_path"][nm][s] for nm in co.SERIES for s in ("mean", "std", "ac1")] + [out["per_path"]["slope"]])
+    dev = torch.device("cuda", op.device)
+    wd = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(dev)
+    ed = torch.empty_like(wd)
+    rec = torch.empty((wd.numel(), 2), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    op.cont_sdf_mean_dev(wd.data_ptr(), ed.data_ptr())
+    op.cont_sim_records_dev(wd.data_ptr(), ed.data_ptr(), rec.data_ptr())
+    forms = [(k, g) for k in (1, 2, 4) for g in (4, 8)] + ([(1, 16), (2, 16)] if D == 6 else [])
+    for k, g in forms:
+        st = torch.full((19, Pn), -7.0, dtype=torch.float64, device=dev)
+        cl = torch.full((Pn,), -7, dtype=torch.int32, device=dev)
+        fin = torch.full((Pn, D), -7.0, dtype=torch.float64, device=dev)
+        op.cont_sim_paths_dev(rec.data_ptr(), CC.SEED, CC.PATH_OFFSET, Pn, Bn, n_periods, st.data_ptr(), cl.data_ptr(), fin.data_ptr(),
+                              start=st0, lookahead=k, group=g)
+        op.synchronize()
+        assert np.array_equal(st.cpu().numpy(), default, equal_nan=True), (k, g)
+        assert np.array_equal(cl.cpu().numpy() / n_periods, out["clamped"]["per_path"]), (k, g)
+        assert np.array_equal(fin.cpu().numpy(), out["final_state"]), (k, g)
+
+
 # -- (3) interpolation ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind,sizes,sd", CC.GRIDS, ids=GRID_IDS)
 def test_series_are_lin_interp_at_the_device_states(S, kind, sizes, sd):

@@ -154,6 +154,50 @@ def rel_err(a, b, floor):
     return float(np.max(np.abs(a[ok] - b[ok]) / np.maximum(den, 1e-300)))
 
 
+# -- (2b) every look-ahead and search, and runs shorter than the ring ----------------------------------------------------------
+@pytest.mark.parametrize("kind,shapes", [("ssy", (5, 4, 6, 7)), ("gcy", (3, 4, 3, 5, 2, 4))], ids=["ssy", "gcy"])
+@pytest.mark.parametrize("n_periods", [2, 3, 9])
+@pytest.mark.parametrize("kappa", [None, 2.0])
+def test_every_lookahead_and_search_matches_the_twin(S, kind, shapes, n_periods, kappa):
+    """sdfs_sim_paths_dev with look-ahead 1 and 4 and both searches, with and without a claim, at 300 paths (a partial block) and runs shorter
+    than, as long as and no multiple of the ring: these forms store no path, so their statistics are held against the
+    twin's (1e-9, the bound of the test above), and against the default form's bit for bit (the forms agree in every
+    bit at the parent commit too).  The default form, which stores, gives the indices (exact) and series (1e-12) of
+    these run lengths."""
+    import torch
+    from sdfs_via_autodiff_amd import sensitivity as sens
+    from sdfs_via_autodiff_amd.simulation import cdf_tables
+    m = model_of(S, kind)
+    w = fixed_point(S, kind, shapes)
+    P, B, seed, off = 300, 3, 0x9E3779B97F4A7C15, 123
+    idx, ser, stats = twin(S, kind, shapes, w, kappa, seed=seed, path_offset=off, n_paths=P, burn_in=B, n_periods=n_periods)
+    out = S.simulate(m, shapes, w, P, n_periods, burn_in=B, seed=seed, path_offset=off, kappa=kappa, return_paths=True)
+    assert np.array_equal(out["paths"]["index"], idx)
+    for nm in out["series"]:
+        assert close(out["paths"][nm], ser[nm], 1.0) <= 1e-12, nm
+    op, _ = sens._operator(m, shapes)
+    dev = torch.device("cuda", 0)
+    wd = torch.from_numpy(w).to(dev)
+    vd = torch.from_numpy(S.claim_prices(m, shapes, w, kappa)["pd"]).to(dev) if kappa is not None else None
+    rec = torch.empty((op.size, 8), dtype=torch.float64, device=dev)
+    op.sim_records_dev(wd.data_ptr(), None if vd is None else vd.data_ptr(), rec.data_ptr())
+    cdf, cdf0 = cdf_tables(m, shapes)
+    cdf, cdf0 = np.concatenate([c.ravel() for c in cdf]), np.concatenate(cdf0)
+    names = out["series"]
+    default = np.stack([out["per_path"][nm][s] for nm in names for s in ("mean", "std", "ac1")] + [out["per_path"]["slope"]])
+    want = np.stack([stats[nm][s] for nm in names for s in ("mean", "std", "ac1")] + [stats["slope"]])
+    for k in (1, 4):
+        for search in (1, 2):
+            st = torch.full((3 * len(names) + 1, P), -7.0, dtype=torch.float64, device=dev)
+            op.sim_paths_dev(rec.data_ptr(), cdf, cdf0, seed, off, P, B, n_periods, kappa=kappa, stats_ptr=st.data_ptr(),
+                             lookahead=k, search=search)
+            torch.cuda.synchronize()
+            got = st.cpu().numpy()
+            print(f"lookahead {k} search {search}: statistics vs twin {close(got, want, 1.0):.3e}")
+            assert close(got, want, 1.0) <= 1e-9, (k, search)
+            assert np.array_equal(got, default, equal_nan=True), (k, search)
+
+
 # -- (3) determinism and splits -------------------------------------------------------------------------------------------
 @limit(300)
 @pytest.mark.parametrize("kind,shapes", [("ssy", (5, 4, 6, 7)), ("gcy", (3, 4, 3, 5, 2, 4))], ids=["ssy", "gcy"])
