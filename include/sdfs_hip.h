@@ -383,6 +383,12 @@ int sdfs_krylov_gate(sdfs_handle* h, const void** gate_dev);
  * scatters the exchanged result back, instead of a subtraction and a copy over the whole shard. */
 int sdfs_unpack_blocks_sub(sdfs_handle* h, const void* packed_dev, void* grid_out_dev, const void* sub_dev, int64_t outer,
                            int64_t n_axis, int64_t inner, int nblocks, const int64_t* offs, int elem_bytes);
+/* sdfs_pack_blocks(unpack = 1) behind a gate word of the handle (sdfs_anderson_gate, sdfs_krylov_gate): the launch returns at
+ * once while the word is 0 and grid_out keeps its contents.  The sharded Anderson loop lands T x in its two iterate buffers
+ * through this call, so that the passes a chunk enqueues behind the pass that ended the loop cannot overwrite the iterate
+ * that pass left (the stage kernels in front of it are gated on the same word). */
+int sdfs_unpack_blocks_gated(sdfs_handle* h, const void* packed_dev, void* grid_out_dev, int64_t outer, int64_t n_axis,
+                             int64_t inner, int nblocks, const int64_t* offs, int elem_bytes, const void* gate_dev);
 
 /* Anderson acceleration (jaxopt.AndersonAcceleration as called at code/solvers.py:104-114; semantics restated in
  * oracle/solvers.py, iterate parity unpinned) on a SHARDED grid: the single-GPU loop's large-grid kernels

@@ -121,6 +121,7 @@ SYMBOLS = {
     "sdfs_krylov_scalars": (C.c_int, [_P, _P]),
     "sdfs_krylov_gate": (C.c_int, [_P, C.POINTER(_P)]),
     "sdfs_unpack_blocks_sub": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "sdfs_unpack_blocks_gated": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, _P]),
     "sdfs_anderson_begin": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, C.c_double, C.c_int64, C.c_double, C.c_double, C.c_int]),
     "sdfs_anderson_gate": (C.c_int, [_P, C.POINTER(_P)]),
     "sdfs_anderson_step": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P]),

@@ -3719,8 +3719,8 @@ int sdfs_apply_stage_dev(sdfs_handle* h, int stage, int mode, const double* in, 
   return sdfs_apply_stage_gated_dev(h, stage, mode, in, out, old, resid_dev, nullptr, 0.0);
 }
 
-int sdfs_pack_blocks(sdfs_handle* h, int unpack, const void* src, void* dst, int64_t outer, int64_t n_axis, int64_t inner,
-                     int nblocks, const int64_t* offs, int elem_bytes) {
+static int pack_blocks_launch(sdfs_handle* h, int unpack, const void* src, void* dst, int64_t outer, int64_t n_axis, int64_t inner,
+                              int nblocks, const int64_t* offs, int elem_bytes, const unsigned long long* gate) {
   int rc = check(h); if (rc) return rc;
   if (!src || !dst || !offs) return fail(h, SDFS_ERR_ARG, "NULL argument");
   if (nblocks < 1) return fail(h, SDFS_ERR_ARG, "at least one block");
@@ -3742,7 +3742,10 @@ int sdfs_pack_blocks(sdfs_handle* h, int unpack, const void* src, void* dst, int
   const unsigned grid = (unsigned)std::min<long long>((total + VEC_BLOCK - 1) / VEC_BLOCK, 8192);
 #define SDFS_PACK_LAUNCH(U)                                                                                              \
   do {                                                                                                                   \
-    if (unpack) hipLaunchKernelGGL((k_pack_blocks<U, true>), dim3(grid), dim3(VEC_BLOCK), 0, h->stream, (const U*)src, (U*)dst, \
+    if (unpack && gate) hipLaunchKernelGGL((k_pack_blocks<U, true, false, true>), dim3(grid), dim3(VEC_BLOCK), 0, h->stream,   \
+                                           (const U*)src, (U*)dst, (unsigned)outer, (unsigned)n_axis, (unsigned)innerU, B,       \
+                                           (const U*)nullptr, gate);                                                     \
+    else if (unpack) hipLaunchKernelGGL((k_pack_blocks<U, true>), dim3(grid), dim3(VEC_BLOCK), 0, h->stream, (const U*)src, (U*)dst, \
                                    (unsigned)outer, (unsigned)n_axis, (unsigned)innerU, B);                              \
     else hipLaunchKernelGGL((k_pack_blocks<U, false>), dim3(grid), dim3(VEC_BLOCK), 0, h->stream, (const U*)src, (U*)dst,       \
                             (unsigned)outer, (unsigned)n_axis, (unsigned)innerU, B);                                     \
@@ -3753,6 +3756,17 @@ int sdfs_pack_blocks(sdfs_handle* h, int unpack, const void* src, void* dst, int
 #undef SDFS_PACK_LAUNCH
   HIPCHK(h, hipGetLastError());
   return 0;
+}
+
+int sdfs_pack_blocks(sdfs_handle* h, int unpack, const void* src, void* dst, int64_t outer, int64_t n_axis, int64_t inner,
+                     int nblocks, const int64_t* offs, int elem_bytes) {
+  return pack_blocks_launch(h, unpack, src, dst, outer, n_axis, inner, nblocks, offs, elem_bytes, nullptr);
+}
+
+int sdfs_unpack_blocks_gated(sdfs_handle* h, const void* packed, void* grid_out, int64_t outer, int64_t n_axis, int64_t inner,
+                             int nblocks, const int64_t* offs, int elem_bytes, const void* gate_dev) {
+  if (!gate_dev) { int rc = check(h); if (rc) return rc; return fail(h, SDFS_ERR_ARG, "NULL gate"); }
+  return pack_blocks_launch(h, 1, packed, grid_out, outer, n_axis, inner, nblocks, offs, elem_bytes, (const unsigned long long*)gate_dev);
 }
 
 int sdfs_stream_copy_dev(sdfs_handle* h, const double* src_dev, double* dst_dev, int64_t n) {

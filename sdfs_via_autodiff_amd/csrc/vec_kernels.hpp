@@ -628,7 +628,8 @@ __device__ __forceinline__ bool and_mix_due(const AndState* __restrict__ S, int 
   return it1 >= m && it1 >= S->no_mix_until && ((long long)it1) % mixing_freq == 0;
 }
 
-// partial sums of <R_i, R_j>, i <= j < m, pair (i, j) at index i m - i (i - 1) / 2 + (j - i): partial[pair * gridDim.x + block]
+// partial sums of <R_i, R_j>, i <= j < m, pair (i, j) at index AND_LAZY_M i - i (i - 1) / 2 + (j - i) -- the stride is the
+// capacity AND_LAZY_M, not m; the pairs with j >= m stay 0 --: partial[pair * gridDim.x + block]
 __global__ void __launch_bounds__(VEC_BLOCK)
 k_and_gram_full(AndPtrs h, int m, int mixing_freq, long long n, double* __restrict__ partial, const AndState* __restrict__ S) {
   if (S->gate == 0ULL || !and_mix_due(S, m, mixing_freq)) return;
@@ -787,11 +788,15 @@ __device__ __forceinline__ double2 unit_sub(const double2 a, const double2 b) { 
 __device__ __forceinline__ double unit_sub(const double a, const double b) { return a - b; }
 __device__ __forceinline__ float unit_sub(const float a, const float b) { return a - b; }
 __device__ __forceinline__ float4 unit_sub(const float4 a, const float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-template <typename U, bool UNPACK, bool SUB = false>
+// GATED (unpack only): a no-op while *gate == 0 -- the unpack that lands T x in the iterate buffers of the sharded
+// Anderson loop, so that the passes enqueued behind the one that ended the loop leave the returned iterate alone
+template <typename U, bool UNPACK, bool SUB = false, bool GATED = false>
 __global__ void __launch_bounds__(VEC_BLOCK)
 k_pack_blocks(const U* __restrict__ src, U* __restrict__ dst, unsigned outer, unsigned n_axis, unsigned innerU, PackBlocks B,
-              const U* __restrict__ sub = nullptr) {
+              const U* __restrict__ sub = nullptr, const unsigned long long* gate = nullptr) {
   static_assert(!SUB || UNPACK, "the subtraction rides on the unpack");
+  static_assert(!GATED || UNPACK, "only the unpack is gated");
+  if (GATED) SDFS_GATED(gate);
   const unsigned total = outer * n_axis * innerU;          // < 2^31 (host check)
   for (unsigned e = blockIdx.x * VEC_BLOCK + threadIdx.x; e < total; e += gridDim.x * VEC_BLOCK) {
     const unsigned q = e / innerU, r = e - q * innerU;

@@ -138,16 +138,24 @@ class HipStages:
                                              gate.data_ptr() if gate is not None else None, float(gate_tol)), self._h)
         return out
 
-    def pack_blocks(self, grid, packed, axis, offs, unpack=False):
+    def pack_blocks(self, grid, packed, axis, offs, unpack=False, gate=None):
         """One launch between `grid` (contiguous, any rank) and the 1-D buffer `packed` in which every block
-        offs[j]:offs[j+1] of `axis` is one contiguous piece (sdfs_pack_blocks); unpack=True writes `grid`."""
+        offs[j]:offs[j+1] of `axis` is one contiguous piece (sdfs_pack_blocks); unpack=True writes `grid`.  gate (unpack
+        only): a gate word of the handle (gate_tensor); while it holds 0 the launch is a no-op and `grid` keeps its
+        contents (sdfs_unpack_blocks_gated)."""
         shp = list(grid.shape)
         outer = int(np.prod(shp[:axis], dtype=np.int64)) if axis > 0 else 1
         inner = int(np.prod(shp[axis + 1:], dtype=np.int64)) if axis + 1 < len(shp) else 1
         o = (C.c_int64 * len(offs))(*[int(v) for v in offs])
         src, dst = (packed, grid) if unpack else (grid, packed)
-        rc = lib.sdfs_pack_blocks(self._h, int(unpack), src.data_ptr(), dst.data_ptr(), outer, shp[axis], inner,
-                                  len(offs) - 1, o, grid.element_size())
+        if gate is not None:
+            if not unpack:
+                raise ValueError("only the unpack is gated")
+            rc = lib.sdfs_unpack_blocks_gated(self._h, src.data_ptr(), dst.data_ptr(), outer, shp[axis], inner,
+                                              len(offs) - 1, o, grid.element_size(), gate.data_ptr())
+        else:
+            rc = lib.sdfs_pack_blocks(self._h, int(unpack), src.data_ptr(), dst.data_ptr(), outer, shp[axis], inner,
+                                      len(offs) - 1, o, grid.element_size())
         if rc == _lib.SDFS_ERR_UNSUPPORTED:
             return False                      # more blocks / bigger units than the kernel takes: the caller copies per peer
         check(rc, self._h)
@@ -291,12 +299,14 @@ class ShardedKoopmans:
         self._bufs[("flip", role)] = n
         return f"{role}{n}"
 
-    def _reshard(self, x, src_axis, src_sizes, src_off, dst_axis, dst_sizes, dst_off, out=None, minus=None):
+    def _reshard(self, x, src_axis, src_sizes, src_off, dst_axis, dst_sizes, dst_off, out=None, minus=None, gate=None):
         """x is sharded on src_axis (this rank's block) with dst_axis full; return the grid sharded
         on dst_axis with src_axis full.  Rank r receives block (all src, its dst block).
         Blocks along axis 0 are contiguous slabs: they are sent / received in place, the other
         side goes through one packed copy.  Result and pack buffers are allocated once (`out`, or two
-        alternating buffers per direction: the result stays valid across the next re-shard of the same kind)."""
+        alternating buffers per direction: the result stays valid across the next re-shard of the same kind).
+        gate: a gate word of the backend's handle; while it holds 0 `out` is not written (the exchange still runs, into
+        the receive buffer: the write into `out` is the gated unpack launch -- a device grid that is not received in place)."""
         r = self.rank
         shp = list(x.shape)
         shp[src_axis] = sum(src_sizes)
@@ -305,6 +315,8 @@ class ShardedKoopmans:
             out = self.buf(self._flip(f"reshard{src_axis}"), shp, x.dtype, x.device)
         # device grids: one pack / unpack launch for the whole shard (sdfs_pack_blocks) instead of a strided copy per peer
         fused = x.is_cuda and x.is_contiguous() and hasattr(self.backend, "pack_blocks")
+        if gate is not None and (not fused or src_axis == 0 or minus is not None):
+            raise ValueError("a gated re-shard needs the unpack launch of a device grid")
         send = [x.narrow(dst_axis, dst_off[j], dst_sizes[j]) for j in range(self.world)]
         if dst_axis != 0:
             packed = None
@@ -349,8 +361,10 @@ class ShardedKoopmans:
         if src_axis != 0:
             if rflat is not None and minus is not None and self.backend.unpack_blocks_sub(out, rflat, minus, src_axis, offs_src):
                 minus = None                                               # (the subtraction rode on the unpack)
-            elif rflat is not None and self.backend.pack_blocks(out, rflat, src_axis, offs_src, unpack=True):
+            elif rflat is not None and self.backend.pack_blocks(out, rflat, src_axis, offs_src, unpack=True, gate=gate):
                 pass
+            elif gate is not None:
+                raise _lib.SdfsError("the gated unpack does not take this block table")
             else:
                 for slot, t in zip(slots, recv):                           # unpack
                     slot.copy_(t)
@@ -362,10 +376,11 @@ class ShardedKoopmans:
     def a_to_b(self, x, out=None):
         return self._reshard(x, self.axis_a, self.a_sizes, self.a_off, self.axis_b, self.b_sizes, self.b_off, out=out)
 
-    def b_to_a(self, x, out=None, minus=None):
+    def b_to_a(self, x, out=None, minus=None, gate=None):
         """minus (a grid in the A-sharded layout): the result is (re-sharded x) - minus, the subtraction folded into the
-        unpack launch."""
-        return self._reshard(x, self.axis_b, self.b_sizes, self.b_off, self.axis_a, self.a_sizes, self.a_off, out=out, minus=minus)
+        unpack launch.  gate: `out` is left alone while the word holds 0 (_reshard)."""
+        return self._reshard(x, self.axis_b, self.b_sizes, self.b_off, self.axis_a, self.a_sizes, self.a_off, out=out, minus=minus,
+                             gate=gate)
 
     @property
     def mirror_ok(self):
@@ -399,14 +414,15 @@ class ShardedKoopmans:
         return t, res
 
     # -- operator -------------------------------------------------------------------
-    def _apply(self, mode, x, out=None, minus=None, gate=None):
+    def _apply(self, mode, x, out=None, minus=None, gate=None, gate_out=False):
         """gate: a 1-element device tensor; while it holds 0 the stage kernels are no-ops (the exchanges still run, on
-        whatever the buffers hold).  out / minus: as in b_to_a."""
+        whatever the buffers hold).  out / minus: as in b_to_a.  gate_out: the launch that writes `out` is gated too, so
+        that a closed gate leaves `out` as it is (without it `out` receives whatever the stale stage buffers hold)."""
         kw = {} if gate is None else dict(gate=gate, gate_tol=0.0)
         y = self._stage(self.backend, 0, mode, x, "s0", **kw)
         z = self.a_to_b(y)
         t = self._stage(self.backend, 1, mode, z, "s1", **kw)
-        return self.b_to_a(t, out=out, minus=minus)
+        return self.b_to_a(t, out=out, minus=minus, gate=gate if gate_out else None)
 
     def apply_T(self, w_loc):
         return self._apply(MODE_T, w_loc)
@@ -648,7 +664,10 @@ def _anderson_sharded_device(op, w_loc, tol, max_iter, m, mixing_frequency, beta
     Gram sweep and an all-reduce of its 78 sums, the control step (one workgroup: stopping test, solve, safeguard --
     identical on every rank, it only sees all-reduced values) and the update of x.  The iterate alternates between two
     buffers (a plain step x = T x is no copy), nothing is cloned, and the host reads the state every `check_every`
-    passes: host_syncs <= n_iter / check_every + 2."""
+    passes: host_syncs <= n_iter / check_every + 2.  The passes a chunk enqueues behind the one that ended the loop write
+    nothing: the stage kernels, the loop's own kernels AND the unpack that lands T x in X[.] are gated on the loop's word
+    (ungated, the second such pass unpacked the stale stage-1 output T(x_(it-1)) over X[it & 1], the mixed iterate of
+    a closing pass that mixed), so the iterate returned does not depend on check_every."""
     be = op.backend
     dev = w_loc.device
     n = w_loc.numel()
@@ -673,7 +692,7 @@ def _anderson_sharded_device(op, w_loc, tol, max_iter, m, mixing_frequency, beta
         cnt = min(check_every, max_iter - enq, 256)
         for i in range(enq, enq + cnt):
             xi, xo = X[i & 1], X[(i + 1) & 1]
-            op._apply(MODE_T, xi, out=xo, gate=gate)
+            op._apply(MODE_T, xi, out=xo, gate=gate, gate_out=True)
             step(AND_PUSH, i, xi, xo)
             op.allreduce_sum(sums[:1])
             if (i + 1) % mixing_frequency == 0:
@@ -693,6 +712,7 @@ def _anderson_sharded_device(op, w_loc, tol, max_iter, m, mixing_frequency, beta
         stats["rejected_mixes"] = int(st[4]) if host_syncs else 0
         stats["host_syncs"] = host_syncs
         stats["status"] = int(st[3]) if host_syncs else 0
+        stats["last_mixed"] = int(st[6]) if host_syncs else 0
     return X[it & 1], it          # pass i leaves the iterate in buffer (i + 1) & 1
 
 

@@ -124,6 +124,37 @@ def main():
     dist.destroy_process_group()
 
 
+def anderson_check_every_sweep(D, op, start, m=3, lo=2, hi=9):
+    """The device-resident sharded Anderson loop must return the same count, error trace and iterate whatever check_every
+    is -- also when the pass that ends the loop MIXED and two or more passes of its chunk are enqueued behind it (they
+    must all be no-ops, the unpack that lands T x in the iterate buffers included).  A trace with check_every = 1 picks a
+    tol that closes the loop on a mixing pass p >= m + 1 (a new minimum of the error, 20 % below every error before it)."""
+    for mf in (1, 2):
+        errs, st = [], {}
+        D.anderson_sharded(op, start.clone(), tol=0.0, max_iter=16, history_size=m, mixing_frequency=mf, errors=errs, stats=st,
+                           check_every=1)
+        if st.get("rejected_mixes", 0) or st.get("status", 0) or not all(np.isfinite(errs)):
+            continue
+        cands = [p for p in range(m + 1, len(errs)) if (p + 1) % mf == 0 and 0.0 < errs[p] < 0.8 * min(errs[:p])
+                 and any((ce - (p + 1) % ce) % ce >= 2 for ce in range(lo, hi + 1))]
+        if not cands:
+            continue
+        p = cands[0]
+        tol = float(np.sqrt(errs[p] * min(errs[:p])))
+        base, st = [], {}
+        x1, n1 = D.anderson_sharded(op, start.clone(), tol=tol, max_iter=3000, history_size=m, mixing_frequency=mf, errors=base,
+                                    stats=st, check_every=1)
+        res = dict(mf=mf, tol=tol, picked_pass=p, it=n1, last_mixed=st.get("last_mixed", -1), rejected=st.get("rejected_mixes", -1),
+                   runs=[])
+        for ce in range(lo, hi + 1):
+            e = []
+            x, n = D.anderson_sharded(op, start.clone(), tol=tol, max_iter=3000, history_size=m, mixing_frequency=mf, errors=e,
+                                      check_every=ce)
+            res["runs"].append([ce, n, e == base, float(op.sup_norm_diff(x, x1)), (ce - n1 % ce) % ce])
+        return res
+    return {"error": "no tol closes the loop on a mixing pass"}
+
+
 def body(rank, model, shapes, use_hip, plain=False):
     if True:
         from sdfs_via_autodiff_amd import distributed as D
@@ -231,6 +262,8 @@ def body(rank, model, shapes, use_hip, plain=False):
             xa3, n_and1 = D.anderson_sharded(op, op.scatter_from_full(torch.full(shapes, 800.0, dtype=torch.float64)).to(dev),
                                              tol=a_tol, max_iter=3000, check_every=1)
             out["anderson_check1"] = (n_and1, float((xa3 - xa2).abs().max().item()))
+            near = xs + 0.5 * (np.random.default_rng(11).random(shapes) - 0.5)
+            out["anderson_sweep"] = anderson_check_every_sweep(D, op, op.scatter_from_full(torch.from_numpy(near)).to(dev))
         xo2, n_ando = osol.anderson_solver(T, np.full(shapes, 800.0), tol=a_tol, max_iter=3000, verbose=False)
         out["anderson_iters"] = (n_and, n_ando)
         out["anderson_err"] = float(np.max(np.abs(op.gather_full(xa2).cpu().numpy() - xo2)))

@@ -65,6 +65,20 @@ def check_device_gated_newton_and_anderson(out):
     assert out["anderson_check1"] == [na, 0.0], out          # chunked loop = one-pass-per-read loop, bit for bit
 
 
+def check_anderson_check_every_sweep(out):
+    """Device-resident sharded Anderson (m = 3): the loop closes on a pass that mixed, and the count, the error trace and the
+    returned iterate are bit-identical for check_every = 1 .. 9 -- with, for at least one value, two or more passes enqueued
+    behind the closing pass: the second of them used to unpack the stale T(x_(it-1)) over the mixed iterate."""
+    s = out["anderson_sweep"]
+    assert "error" not in s, s
+    assert s["last_mixed"] == 1 and s["rejected"] == 0 and s["it"] >= 3 + 2 and s["it"] == s["picked_pass"] + 1, s
+    assert [r[0] for r in s["runs"]] == list(range(2, 10)), s
+    for ce, n, same_errors, diff, behind in s["runs"]:
+        assert behind == (ce - s["it"] % ce) % ce
+        assert n == s["it"] and same_errors and diff == 0.0, (ce, s)
+    assert max(r[4] for r in s["runs"]) >= 2, s
+
+
 def check_sa_gating_and_anderson(out):
     """Device-gated loop: one host read per check_every iterations (+ one per phase), the same iterates as the
     one-read-per-iteration form; Anderson: the oracle's fixed point, and its iteration count within a quarter."""
@@ -131,6 +145,7 @@ def test_sharded_hip_stages_world2(model, shapes):
     assert out["sa_iters"][0] == out["sa_iters"][1] and out["sa_err"] < 1e-8, out
     check_device_gated_newton_and_anderson(out)
     check_sa_gating_and_anderson(out)
+    check_anderson_check_every_sweep(out)
 
 
 @pytest.mark.gpu
@@ -180,7 +195,7 @@ def test_sharded_stages_on_the_pair_plan_kernels(world):
     assert n < 20 and err < 1e-7, out["newton"]
     assert 0 < syncs <= its / 8 + 2 * n + 2, out["newton"]
     n, r, err, syncs = out["anderson"]
-    # (with jaxopt's absolute ridge of 1e-5 the mixing stalls once the residuals are this small -- 348 iterations here,
+    # (with jaxopt's absolute ridge of 1e-6 the mixing stalls once the residuals are this small -- 348 iterations here,
     # DESIGN 4.2; what is held is that the loop ends at the fixed point with one state read per check_every passes)
     assert r < 2e-7 and err < 1e-5 and syncs <= n / 8 + 3, out["anderson"]
 
@@ -208,6 +223,7 @@ def test_sharded_layer_on_rccl_world1(model, shapes):
     assert na == no and out["sa_err"] < 1e-8, out
     check_sa_gating_and_anderson(out)
     check_device_gated_newton_and_anderson(out)
+    check_anderson_check_every_sweep(out)
 
 
 @pytest.mark.gpu
