@@ -315,6 +315,36 @@ typedef struct sdfs_cont_sim_desc {
 int sdfs_cont_sim_paths_dev(sdfs_handle* h, const double* records_dev, const sdfs_cont_sim_desc* desc, double* stats_dev,
                             uint32_t* clamped_dev, double* final_state_dev, double* states_dev, double* series_dev);
 
+/* Asset prices of the continuous-state model at w (handles of sdfs_create_continuous only, else
+ * SDFS_ERR_UNSUPPORTED; fp64).  With the handle's nodes eta_m and weights W_m, x'_m = next_state(x, eta_m) and ^ the
+ * multilinear interpolant of lin_interp (clamped coordinates), for a power p in {0, 1, 2} of the SDF:
+ *   K f (x) = d2(x) sum_m W_m exp(kappa_lam s_lam eta_0m) w^(x'_m)^(p (theta-1)) f^(x'_m)
+ *   d2(x)   = [beta^theta (w(x) - 1)^(1-theta)]^p exp(kappa_c (mu_c + z) + kappa_c^2 sigma_c(x)^2 / 2 + kappa_lam rho_lam h_lam)
+ * -- the K of sdfs_set_tilt_dev with the quadrature in place of H' and w(x) - 1 where that one has Tw(x) - 1 (what
+ * sdfs_cont_sdf_mean_dev does: (1, theta, -gamma) applied to 1 is its E_x[M]).  (1, theta, 1 - gamma) is J(w) up to
+ * |theta - 1| |Tw - w| / (w - 1); (2, 2 theta, -2 gamma) applied to 1 is E_x[M^2]; (1, theta, kappa - gamma) is the price
+ * operator of a claim on G_c^kappa; (0, 0, kappa) the physical E_x[G_c^kappa f].  K runs on the gather path T takes.
+ *
+ * sdfs_cont_set_tilt_dev copies w (the caller's buffer is free afterwards; NULL allowed when sdf_power = 0), writes d2
+ * (NaN where sdf_power > 0 and w <= 1) and the tilted node weights.  It leaves the cached linearisation untouched: a J.v
+ * before and after gives the same bits.  SDFS_ERR_ARG: sdf_power outside {0, 1, 2}, sdf_power > 0 without w, non-finite
+ * exponents; for the later calls, any call before a set_tilt. */
+int sdfs_cont_set_tilt_dev(sdfs_handle* h, const double* w_dev, int sdf_power, double kappa_lam, double kappa_c);
+/* out = K f (device pointers, N doubles each, distinct: f == out is SDFS_ERR_ARG). */
+int sdfs_cont_apply_tilted_dev(sdfs_handle* h, const double* f_dev, double* out_dev);
+/* x = (I - K)^{-1} rhs by the device BiCGSTAB (the stopping rule and opts of sdfs_solve_linear_dev; fp64).
+ * SDFS_ERR_NUMERIC for a breakdown or a solve that stops above the tolerance. */
+int sdfs_cont_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const double* rhs_dev, double* x_dev,
+                               int64_t* n_iter, double* final_rel_resid);
+/* P_0 = 1, P_n = K P_{n-1} for n = 1 ... n_max (1 ... 2^24) on the device, no host synchronisation per horizon.
+ * price_host (n_max x nq) = P_n interpolated at the nq query states (`states`: HOST, laid out [ndim][nq], finite; nq may
+ * be 0); bracket_host (n_max x 2) = min and max of P_n / P_{n-1} over the grid (the Collatz-Wielandt bracket of the
+ * spectral radius of K).  P_n is copied to save_dev[j] (device, N doubles) at the horizons save_at[j] (strictly rising
+ * within 1 ... n_max; anything else is SDFS_ERR_ARG).  The reductions are finished in a fixed order, no atomics: two
+ * runs give identical bits.  SDFS_ERR_NUMERIC (results written) if some P_n leaves the positive finite numbers. */
+int sdfs_cont_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* states, int64_t nq, int64_t n_save,
+                                  const int64_t* save_at, double* const* save_dev, double* price_host, double* bracket_host);
+
 /* max|T(w) - w| of the most recent apply that computed it. */
 int sdfs_residual(sdfs_handle* h, double* sup_norm);
 

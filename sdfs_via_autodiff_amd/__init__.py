@@ -28,7 +28,8 @@ from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_rat
                           wc_ratio_gradient, rouwenhorst_generator, discretize_ssy_persistence_tangent,
                           discretize_gcy_persistence_tangent, SSY_PERSISTENCE, GCY_PERSISTENCE,
                           adjoint_moments_to_gradient)
-from .pricing import stationary_weights, sdf_moments, term_structure, claim_prices
+from .pricing import (stationary_weights, sdf_moments, term_structure, claim_prices, sdf_moments_continuous,
+                      term_structure_continuous, claim_prices_continuous)
 from .simulation import simulate, simulate_continuous
 from .batch import (BatchOperator, BatchResult, solve_batch, batch_lds_bytes, BatchGradient, gradient_batch, BatchPrices,
                     price_batch, price_words_to_stats, BatchSimulation, simulate_batch, batch_sim_lds_bytes,
@@ -49,6 +50,7 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "rouwenhorst_generator", "discretize_ssy_persistence_tangent", "discretize_gcy_persistence_tangent",
            "SSY_PERSISTENCE", "GCY_PERSISTENCE", "adjoint_moments_to_gradient",
            "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate", "simulate_continuous",
+           "sdf_moments_continuous", "term_structure_continuous", "claim_prices_continuous",
            "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes", "BatchGradient", "gradient_batch", "BatchPrices", "price_batch", "price_words_to_stats",
            "BatchSimulation", "simulate_batch", "batch_sim_lds_bytes", "batch_cdf_tables", "batch_sim_tables",
            "SdfsError", "LIB_PATH"]

@@ -81,7 +81,17 @@ struct ContIO {
 //            * sum_m W_m exp(theta h_lambda'(x, m)) interp(w)(x'(x, m))^(theta - 1)
 // -- T's node sum with the exponent theta - 1 on the interpolant, -gamma where T's constant has 1 - gamma, and its own
 // epilogue; the box, the pre-contraction and the node loop are T's, so the host's box logic decides its path as it does T's.
-enum ContMode { C_T = 0, C_TLIN = 1, C_JVP = 2, C_EM = 3 };
+//
+// C_K0 / C_K1 / C_K2: the tilted expectation K(p, kappa_lambda, kappa_c) f of DESIGN 4.15 for the SDF power p = 0, 1, 2,
+//   K f (x) = d2(x) * sum_m Wt_m * interp(w)(x'(x, m))^(p (theta - 1)) * interp(f)(x'(x, m))
+// with the tilted node weights Wt_m = W_m exp(kappa_lambda s_lambda eta_0m) in P.wq and the per-point factor d2 (k_cont_tilt_d2)
+// in io.c2_in.  p = 1, 2 stage and interpolate w (io.w) and f (io.v) as C_JVP stages w and v, one pow_fast_n per node;
+// p = 0 stages f alone (io.w = io.v = f), with T's LDS and no power.  The epilogue is J.v's: out = d2 * e (- f).
+// C_K2 takes one power with the exponent 2 (theta - 1): squaring the theta - 1 power measured the same.
+enum ContMode { C_T = 0, C_TLIN = 1, C_JVP = 2, C_EM = 3, C_K0 = 4, C_K1 = 5, C_K2 = 6 };
+
+// modes that stage and interpolate a second field (io.v) beside io.w
+constexpr bool cont_two_fields(int mode) { return mode == C_JVP || mode == C_K1 || mode == C_K2; }
 
 template <int D, int d, typename Idx>
 struct InterpRec {
@@ -116,6 +126,7 @@ __device__ __forceinline__ void interp_cell(const ContDesc& P, const double (&c)
 
 template <int D, int MODE>
 __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContIO io) {
+  constexpr bool TWO = cont_two_fields(MODE);
   __shared__ double red[4];
   if (io.gate != nullptr) {
     const unsigned long long g = *io.gate;
@@ -178,7 +189,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
         go += (long long)(blo[d] + q) * P.stride[d];
       }
       box[e] = io.w[go];
-      if (MODE == C_JVP) box[P.cap + e] = io.v[go];
+      if (TWO) box[P.cap + e] = io.v[go];
     }
     __syncthreads();
   }
@@ -189,7 +200,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
   const int inner_v = bext[D - 1] * bext[D - 2];
   const int Vo = staged ? V / inner_v : 0;
   const bool tensor = staged && tq > 0 && (long long)Vo * tq2 <= (long long)P.ucap;
-  double* const Uw = box + (MODE == C_JVP ? 2 : 1) * P.cap;
+  double* const Uw = box + (TWO ? 2 : 1) * P.cap;
   double* const Uv = Uw + P.ucap;
   int lsU[DO > 0 ? DO : 1];
   if (tensor) {
@@ -215,7 +226,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
         const double v1 = fma(tt[1], box[base + ls[D - 2] + 1] - box[base + ls[D - 2]], box[base + ls[D - 2]]);
         Uw[e] = fma(tt[0], v1 - v0, v0);
       }
-      if (MODE == C_JVP) {
+      if (TWO) {
         const double* bv = box + P.cap;
         const double v0 = fma(tt[1], bv[base + 1] - bv[base], bv[base]);
         const double v1 = fma(tt[1], bv[base + ls[D - 2] + 1] - bv[base + ls[D - 2]], bv[base + ls[D - 2]]);
@@ -251,7 +262,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
       const int jb = (int)__umulhi((unsigned)r, P.tmagic), ja = r - jb * tq;   // j_{D-1}, j_{D-2}
       off += ja * tq + jb;
       g[0] = InterpRec<DO, 0, int>::run(Uw, off, lsU, to);
-      if (MODE == C_JVP) iv = InterpRec<DO, 0, int>::run(Uv, off, lsU, to);
+      if (TWO) iv = InterpRec<DO, 0, int>::run(Uv, off, lsU, to);
       wq = P.wq[m];
     } else if (valid) {
       double c[D], t[D];
@@ -270,19 +281,24 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
           off += il * ls[d];
         }
         g[0] = InterpRec<D, 0, int>::run(box, off, ls, t);
-        if (MODE == C_JVP) iv = InterpRec<D, 0, int>::run(box + P.cap, off, ls, t);
+        if (TWO) iv = InterpRec<D, 0, int>::run(box + P.cap, off, ls, t);
       } else {
         long long off = 0;
 #pragma unroll
         for (int d = 0; d < D; ++d) off += (long long)i0[d] * P.stride[d];
         g[0] = InterpRec<D, 0, long long>::run(io.w, off, gs, t);
-        if (MODE == C_JVP) iv = InterpRec<D, 0, long long>::run(io.v, off, gs, t);
+        if (TWO) iv = InterpRec<D, 0, long long>::run(io.v, off, gs, t);
       }
       wq = P.wq[m];
     }
+    if (MODE == C_K0) {
+      acc = fma(wq, g[0], acc);                                      // Wt interp(f): no power
+      continue;
+    }
     double pw[1];
-    pow_fast_n<true, 1>(g, MODE == C_EM ? P.theta - 1.0 : P.theta, PT, pw);
+    pow_fast_n<true, 1>(g, MODE == C_K2 ? 2.0 * (P.theta - 1.0) : (MODE == C_EM || MODE == C_K1 ? P.theta - 1.0 : P.theta), PT, pw);
     if (MODE == C_JVP) acc = fma(wq * (pw[0] / g[0]), iv, acc);      // W g^(theta-1) interp(v)
+    else if (MODE == C_K1 || MODE == C_K2) acc = fma(wq * pw[0], iv, acc);   // Wt g^(p (theta-1)) interp(f)
     else acc = fma(wq, pw[0], acc);
   }
 #pragma unroll
@@ -292,7 +308,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
   if (wave != 0) return;
   const double e = (red[0] + red[1]) + (red[2] + red[3]);
 
-  if (MODE == C_JVP) {
+  if (TWO || MODE == C_K0) {
     if (lane == 0) {
       double r = io.c2_in[p] * e;
       if (io.minus_identity) r -= io.v[p];

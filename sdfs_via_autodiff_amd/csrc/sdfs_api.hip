@@ -226,6 +226,17 @@ struct sdfs_handle {
   bool cont = false;
   ContDesc cd;
   double cont_gamma = 0.0;           // gamma as given (the descriptor carries 1 - gamma): the series of cont_sim.hpp
+  // its tilted expectation K (sdfs_cont_set_tilt_dev, cont_price.hpp): a copy of w, the per-point factor d2 and the tilted
+  // node weights stand beside the cached linearisation c1 / c2 and never replace it
+  struct {
+    int power = -1;                                           // -1: no tilt set
+    std::vector<double> weight, eta0;                         // W_m and eta_0m as the handle was created with
+    double* w = nullptr; double* d2 = nullptr;                // the tilt's w, d2
+    double* wq = nullptr;                                     // W_m exp(kappa_lambda s_lambda eta_0m)
+    std::vector<double> wq_host;                              // its staging (kept alive across the async copy)
+    double* pa = nullptr; double* pb = nullptr;               // P_n ping-pong of the horizon loop
+    double* part = nullptr;                                   // per-workgroup partials of one horizon
+  } ctilt;
 
   // single-index dense form (sdfs_create_dense): H materialised, one GEMV per application
   bool dense = false;
@@ -606,8 +617,8 @@ struct Apply {
   double gate_tol = 0.0;
   int minus_identity = 0;                       // J.v: out = J v - v
   double* dotp = nullptr;                       // ... and its last pass writes per-workgroup partial sums of <out, in>, <out, out>
-  const double* lc1 = nullptr;                  // J.v scalings in place of the cached c1 / c2 (the tilted expectation's d1 / d2)
-  const double* lc2 = nullptr;
+  const double* lc1 = nullptr;                  // J.v scalings in place of the cached c1 / c2 (the tilted expectation's d1 / d2;
+  const double* lc2 = nullptr;                  // on a continuous handle the tilt's copy of w and its d2, cont_price.hpp)
   int prec = PREC_F64;
   const double* dot_with = nullptr;             // small-grid plan: the last pass also sums <out, dot_with> (needs dotp)
   // large-grid Anderson: the streamed last pass of T also does the push (LineIO::and_*); *tiles = the partial sums it
@@ -763,9 +774,18 @@ int launch_cont(sdfs_handle* h, int mode, const ContIO& io, const Counter& c) {
   return launch_kernel(h, cont_kernel<D, C_JVP>, grid, block, 2 * lds, c, h->cd, io);
 }
 
+// ... and of its tilted expectation (cont_price.hpp) for the SDF power p: p = 0 stages f alone, p = 1, 2 stage w and f
+template <int D>
+int launch_cont_tilted(sdfs_handle* h, int power, const ContDesc& cd, const ContIO& io, const Counter& c) {
+  const dim3 grid((unsigned)cd.N), block(256);
+  const size_t lds = (size_t)(cd.cap + cd.ucap) * sizeof(double);
+  if (power == 0) return launch_kernel(h, cont_kernel<D, C_K0>, grid, block, lds, c, cd, io);
+  if (power == 1) return launch_kernel(h, cont_kernel<D, C_K1>, grid, block, 2 * lds, c, cd, io);
+  return launch_kernel(h, cont_kernel<D, C_K2>, grid, block, 2 * lds, c, cd, io);
+}
+
 int run_cont(sdfs_handle* h, const Apply& a) {
   int rc = 0;
-  if (a.mode != MODE_T && (rc = ensure_lin(h))) return rc;
   if (a.in == a.out) return fail(h, SDFS_ERR_ARG, "the continuous operator cannot run in place");
   ContIO io;
   memset(&io, 0, sizeof io);
@@ -773,6 +793,20 @@ int run_cont(sdfs_handle* h, const Apply& a) {
   const double n8 = 8.0 * (double)h->cd.N;
   const double corners = (double)(1 << h->cd.D);
   double bytes = 2 * n8, flops = (double)h->cd.N * h->cd.M * (2.0 * corners + 2.0 * h->cd.D + 2.0);
+  if (a.lc2) {
+    // the tilted expectation: lc1 = the tilt's w, lc2 = d2; the node weights of the tilt replace the descriptor's, and the
+    // cached linearisation is neither read nor written
+    const int power = h->ctilt.power;
+    if (a.mode != MODE_JVP || power < 0 || !a.lc1) return fail(h, SDFS_ERR_ARG, "a tilted application is a J.v request after sdfs_cont_set_tilt_dev");
+    ContDesc cd = h->cd;
+    cd.wq = h->ctilt.wq;
+    io.w = power ? a.lc1 : a.in; io.v = a.in; io.c2_in = a.lc2;
+    bytes += (power ? 2 : 1) * n8;
+    if (power) flops *= 1.5;
+    const Counter c(power == 0 ? "cont:K0" : (power == 1 ? "cont:K1" : "cont:K2"), bytes, flops);
+    return cd.D == 4 ? launch_cont_tilted<4>(h, power, cd, io, c) : launch_cont_tilted<6>(h, power, cd, io, c);
+  }
+  if (a.mode != MODE_T && (rc = ensure_lin(h))) return rc;
   const char* tag = "cont:T";
   if (a.mode == MODE_T) { io.w = a.in; io.old = a.old; io.resid = a.resid; if (a.resid) bytes += n8; }
   else if (a.mode == MODE_T_LIN) {
@@ -2982,6 +3016,9 @@ int sdfs_create_continuous(int model, int ndim, const int64_t* shapes, const dou
   double *eta = nullptr, *wqd = nullptr;
   if ((rc = upload(h, &eta, nodes, (size_t)M * ndim)) || (rc = upload(h, &wqd, wq.data(), (size_t)M))) return bail(rc);
   cd.eta = eta; cd.wq = wqd;
+  h->ctilt.weight.resize((size_t)M);         // the raw weights and eta_0: what a tilt forms its node weights from
+  for (int64_t m = 0; m < M; ++m) h->ctilt.weight[(size_t)m] = weights ? weights[m] : 1.0 / (double)M;
+  h->ctilt.eta0.assign(nodes, nodes + M);
   for (int d = 0; d < ndim; ++d) {
     double mx = 0.0;
     for (int64_t m = 0; m < M; ++m) mx = std::max(mx, std::fabs(nodes[(size_t)d * M + m]));
@@ -4159,4 +4196,5 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
 }  // extern "C"
 
 #include "cont_sim.hpp"    // continuous-state paths (sdfs_cont_sdf_mean_dev, sdfs_cont_sim_*), built on the definitions above
+#include "cont_price.hpp"  // continuous-state pricing (sdfs_cont_set_tilt_dev ... sdfs_cont_tilted_horizons_dev), likewise
 #include "batch_api.hpp"   // the batch API (sdfs_batch_*), built on the definitions above

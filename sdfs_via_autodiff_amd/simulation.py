@@ -23,7 +23,8 @@ import math
 
 import numpy as np
 
-from .pricing import _AXIS_Q, _shapes, _check_grid, _kappa, stationary_weights, claim_prices
+from .pricing import (_AXIS_Q, _shapes, _check_grid, _kappa, _count, _check_w_star, _cont_model_request, stationary_weights,
+                      claim_prices)
 from .sensitivity import _kind, _operator, _device_grid
 
 SERIES = ("dc", "m", "rf", "rc", "xc", "wc")
@@ -50,12 +51,6 @@ def cdf_tables(model, shapes, arrays=None):
         cdf.append(c)
         cdf0.append(c0)
     return cdf, cdf0
-
-
-def _count(x, name, lo, hi):
-    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not lo <= int(x) <= hi:
-        raise ValueError(f"{name} must be an integer in {lo} ... {hi}, got {x!r}")
-    return int(x)
 
 
 def _summary(a):
@@ -89,16 +84,6 @@ def _result(names, st, P):
         m = per_path[nm]["mean"]
         pooled[nm] = {"mean": float(m.mean()), "se": float(m.std(ddof=1) / math.sqrt(P)) if P > 1 else float("nan")}
     return {"series": names, "per_path": per_path, "summary": summary, "pooled": pooled}
-
-
-def _check_w_star(w_star):
-    import torch
-    if isinstance(w_star, torch.Tensor):
-        w_ok = bool(torch.all(w_star > 1.0))
-    else:
-        w_ok = bool(np.all(np.asarray(w_star, dtype=np.float64) > 1.0))
-    if not w_ok:
-        raise ValueError("w_star must exceed 1 at every grid point (the log return needs ln(w - 1))")
 
 
 def _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol, return_paths, members=1, check_kappa=None):
@@ -197,45 +182,28 @@ CONT_REC_BYTES = 16               # per grid point: {w, −ln E_x[M]}
 def _cont_request(model, grids, w_star, n_paths, n_periods, burn_in, seed, path_offset, step_offset, start, operator, d,
                   return_paths):
     """The checked request of ``simulate_continuous``; raises before any device call."""
-    kind = _kind(model)[0]                                 # (TypeError for anything but an SSY or a GCY)
-    nd = 4 if kind == "ssy" else 6
-    try:
-        grids = tuple(np.ascontiguousarray(np.asarray(g, dtype=np.float64)) for g in grids)
-    except (TypeError, ValueError):
-        raise ValueError("grids must be a sequence of 1-D axis grids") from None
-    if len(grids) != nd:
-        raise ValueError(f"{kind.upper()} has {nd} state variables, got {len(grids)} grids")
-    for a, g in enumerate(grids):
-        if g.ndim != 1 or g.size < 2 or not np.all(np.isfinite(g)) or not np.all(np.diff(g) > 0):
-            raise ValueError(f"grids[{a}] must be a finite increasing 1-D grid of at least 2 points")
-    shapes = tuple(g.size for g in grids)
-    _check_grid(w_star, shapes, "w_star")
-    P, T, B, off, sd, _, _ = _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, "stationary", 1e-10,
-                                      return_paths)
-    s0 = _count(step_offset, "step_offset", 0, (1 << 32) - 1)
-    if s0 + B + T >= 1 << 32:
-        raise ValueError(f"step_offset + burn_in + n_periods = {s0 + B + T} >= 2^32: step numbers are 32-bit")
-    if start is not None:
-        try:
-            start = np.ascontiguousarray(np.asarray(start, dtype=np.float64))
-        except (TypeError, ValueError):
-            raise ValueError("start must be None, one state (D,) or one state per path (n_paths, D)") from None
-        if start.shape not in ((nd,), (P, nd)):
-            raise ValueError(f"start has shape {start.shape}: one state ({nd},) or one per path ({P}, {nd})")
-        if not np.all(np.isfinite(start)):
-            raise ValueError("start must be finite")
-    if operator is not None:
-        from .continuous import ContinuousOperator
-        if not isinstance(operator, ContinuousOperator):
-            raise TypeError(f"operator must be a ContinuousOperator, not {type(operator).__name__}")
-        if operator.params != tuple(float(p) for p in model.params) or operator.shapes != shapes or \
-                not all(np.array_equal(a, b) for a, b in zip(operator.grids, grids)):
-            raise ValueError("operator was built on other parameters or grids than (model, grids)")
-    else:
-        d = _count(d, "d", 1, 64)
-        if d ** nd > 1 << 24:
-            raise ValueError(f"d = {d}: the tensor rule has {d ** nd} > 2^24 nodes")
-    _check_w_star(w_star)
+    req = {}
+
+    def counts(nd, shapes):
+        P, T, B, off, sd, _, _ = _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, "stationary", 1e-10,
+                                          return_paths)
+        s0 = _count(step_offset, "step_offset", 0, (1 << 32) - 1)
+        if s0 + B + T >= 1 << 32:
+            raise ValueError(f"step_offset + burn_in + n_periods = {s0 + B + T} >= 2^32: step numbers are 32-bit")
+        st = start
+        if st is not None:
+            try:
+                st = np.ascontiguousarray(np.asarray(st, dtype=np.float64))
+            except (TypeError, ValueError):
+                raise ValueError("start must be None, one state (D,) or one state per path (n_paths, D)") from None
+            if st.shape not in ((nd,), (P, nd)):
+                raise ValueError(f"start has shape {st.shape}: one state ({nd},) or one per path ({P}, {nd})")
+            if not np.all(np.isfinite(st)):
+                raise ValueError("start must be finite")
+        req.update(P=P, T=T, B=B, off=off, sd=sd, s0=s0, start=st)
+
+    kind, grids, shapes, d = _cont_model_request(model, grids, w_star, operator, d, counts)
+    P, T, B, off, sd, s0, start = (req[k] for k in ("P", "T", "B", "off", "sd", "s0", "start"))
     return kind, grids, shapes, P, T, B, off, sd, s0, start, d
 
 
