@@ -345,6 +345,19 @@ int sdfs_cont_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const doub
 int sdfs_cont_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* states, int64_t nq, int64_t n_save,
                                   const int64_t* save_at, double* const* save_dev, double* price_host, double* bracket_host);
 
+/* The parameter tangent of the continuous-state operator (handles of sdfs_create_continuous only, else
+ * SDFS_ERR_UNSUPPORTED; fp64): out = dT(w; p)[dparams], the derivative of T at the fixed grid function w along the
+ * direction dparams (HOST, 13 / 18 doubles in sdfs_create_continuous's parameter order; every parameter, the persistences
+ * included), with the handle's grids, nodes and weights held fixed -- jax.jvp of the reference's T with respect to the
+ * parameters with `grids, nodes, weights` closed over.  build_grid depends on the parameters too: the movement of the
+ * grid is NOT part of this derivative.  The tangent passes through the multilinear interpolant (the slope of w^ along the
+ * direction each node moves; zero where map_coordinates clamps the coordinate, one-sided where a node sits on a grid
+ * line) and through ln w^ (theta is an exponent).  One launch on the gather path T takes; fixed-order reduction, no
+ * atomics: two runs give identical bits.  Tw_dev (may be NULL) receives T w.  Like sdfs_param_tangent_dev the call
+ * linearises at w, so sdfs_apply_jvp_dev and sdfs_solve_linear_dev can follow: dw-star/dp = (I - J)^{-1} out.
+ * SDFS_ERR_ARG: NULL w / dparams / out, a non-finite direction, or w, out, Tw not pairwise distinct. */
+int sdfs_cont_param_tangent_dev(sdfs_handle* h, const double* w_dev, const double* dparams, double* out_dev, double* Tw_dev);
+
 /* max|T(w) - w| of the most recent apply that computed it. */
 int sdfs_residual(sdfs_handle* h, double* sup_norm);
 

@@ -115,6 +115,7 @@ SYMBOLS = {
     "sdfs_cont_solve_tilted_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _P, _I64, _D]),
     "sdfs_cont_tilted_horizons_dev": (C.c_int, [_P, C.c_int64, _D, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_P),
                                                 _D, _D]),
+    "sdfs_cont_param_tangent_dev": (C.c_int, [_P, _P, _D, _P, _P]),
     "sdfs_residual": (C.c_int, [_P, _D]),
     "sdfs_solve": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _I64, _I64, _D]),
     "sdfs_solve_dev": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _I64, _I64, _D]),

@@ -234,6 +234,24 @@ class ContinuousOperator(KoopmansOperator):
               self._h)
         return price, bracket
 
+    # -- parameter tangent (sensitivity.wc_ratio_sensitivities_continuous) -------------------------------
+    def cont_param_tangent_dev(self, w_ptr, dparams, out_ptr, Tw_ptr=None):
+        """out = dT(w; p)[dparams] on device pointers (sdfs_cont_param_tangent_dev): the tangent of T at the fixed grid
+        function w along a direction of the 13 / 18 parameters (the order of ``params``; every parameter, the
+        persistences included), with this operator's grids, nodes and weights held fixed.  ``build_grid`` depends on the
+        parameters too; the movement of the grid is not part of this derivative.  Linearises at w, so ``jvp_dev`` and
+        ``solve_linear_dev`` can follow.  Tw_ptr (optional) receives T(w)."""
+        check(lib.sdfs_cont_param_tangent_dev(self._h, w_ptr, self._dparams(dparams), out_ptr, Tw_ptr), self._h)
+
+    def cont_param_tangent(self, w, dparams):
+        """``cont_param_tangent_dev`` with host ndarrays in and out."""
+        import torch
+        (wd,) = self._to_dev(self._host_in(w))
+        out = torch.empty_like(wd)
+        self.cont_param_tangent_dev(wd.data_ptr(), dparams, out.data_ptr())
+        self.synchronize()
+        return out.cpu().numpy()
+
 
 def T_fun_factory(params, method="quadrature", batch_size=10000, device=0):
     """Function factory for the operator T; ``params`` as in the reference:

@@ -88,10 +88,36 @@ struct ContIO {
 // in io.c2_in.  p = 1, 2 stage and interpolate w (io.w) and f (io.v) as C_JVP stages w and v, one pow_fast_n per node;
 // p = 0 stages f alone (io.w = io.v = f), with T's LDS and no power.  The epilogue is J.v's: out = d2 * e (- f).
 // C_K2 takes one power with the exponent 2 (theta - 1): squaring the theta - 1 power measured the same.
-enum ContMode { C_T = 0, C_TLIN = 1, C_JVP = 2, C_EM = 3, C_K0 = 4, C_K1 = 5, C_K2 = 6 };
+//
+// C_PTAN: the tangent of T at a fixed w along a direction of the parameters, grids / nodes / weights held fixed:
+//   dT(x) = dbeta u + beta u [ (dC/C + de/e) / theta - dtheta ln Kg / theta^2 ],   Kg = C e,  u = Kg^(1/theta),
+//   de/e  = sum_m omega_m [ dtheta (s_lambda eta_0m + ln g_m) + theta ds_lambda eta_0m + theta dg_m / g_m ] / e,
+//   omega_m = W_m exp(theta s_lambda eta_0m) g_m^theta,  g_m = interp(w)(c(m)),  dg_m = sum_d (d interp(w) / d c_d) dc_d(m),
+//   dc_d(m) = da_d + dk_d eta_dm where 0 <= c_d(m) < n_d - 1 and 0 where the coordinate is clamped.
+// dg is forward mode on the fold T has (DualRec); T's box, one field staged.  The pre-contracted path keeps the tangent
+// of the inner-pair contraction in the second U array (where J.v keeps its direction): cap + 2 ucap doubles of LDS.
+// The node sum carries omega and omega * [...], reduced in T's fixed order.  The epilogue also writes T_LIN's c2 (the
+// same expressions on the same e: the same bits) and, if asked, T w.
+// C_PTANL: C_PTAN with ln g_m taken from the power (pow_log_n below: ln 2 times the log2 g that g^theta forms anyway)
+// instead of libm's log: 0.85 - 0.92 of C_PTAN's time (profiles/continuous_sensitivity_times.txt), the host's default.
+enum ContMode { C_T = 0, C_TLIN = 1, C_JVP = 2, C_EM = 3, C_K0 = 4, C_K1 = 5, C_K2 = 6, C_PTAN = 7, C_PTANL = 8 };
 
 // modes that stage and interpolate a second field (io.v) beside io.w
 constexpr bool cont_two_fields(int mode) { return mode == C_JVP || mode == C_K1 || mode == C_K2; }
+
+// C_PTAN's request: the direction in the descriptor's own terms (d rho_d, d xcoef_d, d sconst_d, d phi_d per dimension;
+// d s_lambda = sconst[0], d rho_lambda = rho[0]) and the optional T w
+struct ContTan {
+  double rho[CMAXD], xcoef[CMAXD], sconst[CMAXD], phi[CMAXD];
+  double gamma, mu_c, phi_c, theta, beta;
+  double* Tw;
+};
+struct ContNoTan {};                             // what the other forms take in its place: nothing
+template <int MODE> struct ContTanSel { using type = ContNoTan; };
+template <> struct ContTanSel<C_PTAN> { using type = ContTan; };
+template <> struct ContTanSel<C_PTANL> { using type = ContTan; };
+constexpr bool cont_ptan(int mode) { return mode == C_PTAN || mode == C_PTANL; }
+template <int MODE> using ContTanOf = typename ContTanSel<MODE>::type;
 
 template <int D, int d, typename Idx>
 struct InterpRec {
@@ -110,6 +136,94 @@ struct InterpRec<D, D, Idx> {
   }
 };
 
+// InterpRec in forward mode: (v, dv) with dv = sum_d (dv / dt_d) td[d], plus the leaves' own tangents fd[] when FD.
+// v is InterpRec's, operation for operation.
+template <int D, int d, typename Idx, bool FD>
+struct DualRec {
+  static __device__ __forceinline__ void run(const double* __restrict__ f, const double* __restrict__ fd, Idx off,
+                                             const Idx (&step)[D], const double (&t)[D], const double (&td)[D],
+                                             double& v, double& dv) {
+    double v0, v1, d0, d1;
+    DualRec<D, d + 1, Idx, FD>::run(f, fd, off, step, t, td, v0, d0);
+    DualRec<D, d + 1, Idx, FD>::run(f, fd, off + step[d], step, t, td, v1, d1);
+    const double diff = v1 - v0;
+    v = fma(t[d], diff, v0);
+    if (!FD && d == D - 1) dv = td[d] * diff;                       // (the leaves' tangents are zero)
+    else dv = fma(td[d], diff, fma(t[d], d1 - d0, d0));
+  }
+};
+template <int D, typename Idx, bool FD>
+struct DualRec<D, D, Idx, FD> {
+  static __device__ __forceinline__ void run(const double* __restrict__ f, const double* __restrict__ fd, Idx off,
+                                             const Idx (&)[D], const double (&)[D], const double (&)[D], double& v, double& dv) {
+    v = f[off];
+    dv = FD ? fd[off] : 0.0;
+  }
+};
+
+// x^y (|y| large: pow_fast_n<true>) together with ln x = ln 2 * log2 x, from the log2 x = hi + lo the power forms: the
+// straight-line path of pow_fast_try<true, N> (pass_kernel.hpp), operation for operation, with hi and lo kept.  Anything
+// outside that path (a wave with a lane that is no positive normal number, |y log2 x| >= 1020) takes pow_fast_n and log.
+#define CONT_FORJ _Pragma("unroll") for (int j = 0; j < N; ++j)
+template <int N>
+__device__ __forceinline__ void pow_log_n(const double (&x)[N], double y, const PowLane& T, double (&res)[N], double (&lnx)[N]) {
+#pragma clang fp contract(off)
+  constexpr int OFFH = (int)(POW_OFF >> 32);
+  constexpr double SHIFT = 0x1.8p46;
+  constexpr double LN2 = 0x1.62e42fefa39efp-1;
+  int i4[N], ji[N];
+  double kd[N], z[N], invc[N], lchi[N], lclo[N], r[N], t1[N], q[N], hi[N], d[N], e[N], lo[N], ehi[N], elo[N], f[N], t[N], p[N];
+  bool rare = false;
+  CONT_FORJ {
+    const int hx = __double2hiint(x[j]);
+    const int tmph = hx - OFFH;
+    rare |= !__builtin_amdgcn_class(x[j], 0x100);
+    i4[j] = tmph >> 12;
+    kd[j] = (double)(tmph >> 20);
+    z[j] = __hiloint2double(hx - (tmph & (int)0xfff00000), __double2loint(x[j]));
+  }
+  CONT_FORJ invc[j] = gather_hib(T.invc, i4[j]);
+  CONT_FORJ lchi[j] = gather64b(T.lchi, i4[j]);
+  CONT_FORJ lclo[j] = gather_hib(T.lclo, i4[j]);
+  CONT_FORJ r[j] = fma(z[j], invc[j], -1.0);
+  CONT_FORJ t1[j] = kd[j] + lchi[j];
+  CONT_FORJ q[j] = fma_sc(r[j], POW_L8, POW_L7);
+  CONT_FORJ q[j] = fma_sc(q[j], r[j], POW_L6);
+  CONT_FORJ q[j] = fma_sc(q[j], r[j], POW_L5);
+  CONT_FORJ q[j] = fma_sc(q[j], r[j], POW_L4);
+  CONT_FORJ q[j] = fma_sc(q[j], r[j], POW_L3);
+  CONT_FORJ q[j] = fma_sc(q[j], r[j], POW_L2);
+  CONT_FORJ hi[j] = fma(r[j], POW_INVLN2_HI, t1[j]);
+  CONT_FORJ d[j] = t1[j] - hi[j];
+  CONT_FORJ e[j] = fma(r[j], POW_INVLN2_HI, d[j]);
+  CONT_FORJ lo[j] = fma(r[j] * r[j], q[j], e[j] + fma(r[j], POW_INVLN2_LO, lclo[j]));
+  CONT_FORJ lnx[j] = fma(hi[j], LN2, lo[j] * LN2);
+  CONT_FORJ ehi[j] = y * hi[j];
+  CONT_FORJ elo[j] = fma(y, lo[j], fma(y, hi[j], -ehi[j]));
+  CONT_FORJ rare |= !(fabs(ehi[j]) < 1020.0);
+  CONT_FORJ {
+    double kk = ehi[j] + SHIFT;
+    ji[j] = __double2loint(kk);
+    kk -= SHIFT;
+    f[j] = (ehi[j] - kk) + elo[j];
+  }
+  CONT_FORJ t[j] = gather64b(T.e2t, ji[j] << 2);
+  CONT_FORJ p[j] = fma_sc(f[j], POW_E6, POW_E5);
+  CONT_FORJ p[j] = fma_sc(p[j], f[j], POW_E4);
+  CONT_FORJ p[j] = fma_sc(p[j], f[j], POW_E3);
+  CONT_FORJ p[j] = fma_sc(p[j], f[j], POW_E2);
+  CONT_FORJ p[j] = fma_sc(p[j], f[j], POW_E1);
+  CONT_FORJ {
+    const double v = fma(t[j], p[j] * f[j], t[j]);
+    res[j] = __hiloint2double(__double2hiint(v) + ((ji[j] >> 6) << 20), __double2loint(v));
+  }
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(rare) != 0ULL, 0)) {
+    pow_fast_n<true, N>(x, y, T, res);
+    CONT_FORJ lnx[j] = log(x[j]);
+  }
+}
+#undef CONT_FORJ
+
 // map_coordinates(order=1, mode='nearest') clips both corner indices into the grid, which equals
 // interpolating at the coordinate clipped to [0, n-1]; with the lower corner capped at n-2 the upper
 // corner is always the next point (at the top edge t = 1), so corner steps are plain strides and the
@@ -125,9 +239,10 @@ __device__ __forceinline__ void interp_cell(const ContDesc& P, const double (&c)
 }
 
 template <int D, int MODE>
-__global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContIO io) {
+__global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContIO io, const ContTanOf<MODE> tan) {
   constexpr bool TWO = cont_two_fields(MODE);
-  __shared__ double red[4];
+  constexpr bool PTAN = cont_ptan(MODE);
+  __shared__ double red[PTAN ? 8 : 4];
   if (io.gate != nullptr) {
     const unsigned long long g = *io.gate;
     if (g <= (unsigned long long)__double_as_longlong(io.gate_tol)) return;
@@ -137,6 +252,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
 
   // this block's grid point and the affine map node -> next-state coordinates
   double x[D], a[D], k[D];
+  [[maybe_unused]] double ad[PTAN ? D : 1], kd[PTAN ? D : 1];    // C_PTAN: the tangents of a and k
   {
     long long r = p;
 #pragma unroll
@@ -156,8 +272,24 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
       }
       a[d] = (mean - P.lo[d]) * P.inv_step[d];
       k[d] = vol * P.inv_step[d];
+      if constexpr (PTAN) {
+        double dmean = tan.rho[d] * x[d];
+        double dvol = tan.sconst[d];
+#pragma unroll
+        for (int e = 0; e < D; ++e) {
+          if (P.xdim[d] == e) dmean += tan.xcoef[d] * x[e];
+          if (P.voldim[d] == e) dvol = tan.phi[d] * exp(x[e]);
+        }
+        ad[d] = dmean * P.inv_step[d];
+        kd[d] = dvol * P.inv_step[d];
+      }
     }
   }
+  // C_PTAN: the tangent of the coordinate c = a + k eta, zero where map_coordinates clamps it
+  [[maybe_unused]] auto ctan = [&](int d, double c, double eta) -> double {
+    if constexpr (PTAN) return (c >= 0.0 && c < (double)(P.n[d] - 1)) ? fma(kd[d], eta, ad[d]) : 0.0;
+    else return 0.0;
+  };
 
   // box of the grid that holds every next state of this point: [blo, blo + bext) per dimension
   extern __shared__ double box[];
@@ -211,14 +343,17 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
       const int ja = (int)__umulhi((unsigned)jj, P.tmagic), jb = jj - ja * tq;
       int il[2];
       double tt[2];
+      [[maybe_unused]] double ttd[2];
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int d = D - 2 + q;
-        const double c = fma(k[d], P.eta[(long long)d * P.M + (long long)(q ? jb : ja) * P.tstride[d]], a[d]);
+        const double eta = P.eta[(long long)d * P.M + (long long)(q ? jb : ja) * P.tstride[d]];
+        const double c = fma(k[d], eta, a[d]);
         const double cc = fmin(fmax(c, 0.0), (double)(P.n[d] - 1));
         const int i0 = min((int)cc, P.n[d] - 2);
         il[q] = min(max(i0 - blo[d], 0), bext[d] - 2);
         tt[q] = cc - (double)(blo[d] + il[q]);
+        if constexpr (PTAN) ttd[q] = ctan(d, c, eta);
       }
       const int base = o * inner_v + il[0] * ls[D - 2] + il[1];
       {
@@ -232,43 +367,60 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
         const double v1 = fma(tt[1], bv[base + ls[D - 2] + 1] - bv[base + ls[D - 2]], bv[base + ls[D - 2]]);
         Uv[e] = fma(tt[0], v1 - v0, v0);
       }
+      if constexpr (PTAN) {                                          // the tangent of Uw[e]: its t's move, the box does not
+        const double d0 = box[base + 1] - box[base], d1 = box[base + ls[D - 2] + 1] - box[base + ls[D - 2]];
+        const double v0 = fma(tt[1], d0, box[base]), v1 = fma(tt[1], d1, box[base + ls[D - 2]]);
+        const double v0d = ttd[1] * d0, v1d = ttd[1] * d1;
+        Uv[e] = fma(ttd[0], v1 - v0, fma(tt[0], v1d - v0d, v0d));
+      }
     }
     __syncthreads();
   }
 
   const PowLane PT = pow_lane_init(lane);
   double acc = 0.0;
+  [[maybe_unused]] double accl = 0.0;            // (accl: C_PTAN's sum of omega * [...])
   const int trips = (P.M + 255) >> 8;            // uniform: pow_fast_n needs whole waves
   for (int it = 0; it < trips; ++it) {
     const int m = it * 256 + tid;
     const bool valid = m < P.M;
     double g[1] = {1.0}, iv = 0.0, wq = 0.0;
+    [[maybe_unused]] double gd = 0.0, eta0 = 0.0;   // C_PTAN: the tangent of g, the node of dimension 0
     if (valid && tensor) {
       // digits of m in base tq: j_0 fastest; the inner pair selects the column of U
       int r = m, off = 0;
       double to[DO > 0 ? DO : 1];
+      [[maybe_unused]] double tod[DO > 0 ? DO : 1];
 #pragma unroll
       for (int d = 0; d < DO; ++d) {
         const int rq = (int)__umulhi((unsigned)r, P.tmagic);
         const int j = r - rq * tq;
         r = rq;
-        const double c = fma(k[d], P.eta[(long long)d * P.M + (long long)j * P.tstride[d]], a[d]);
+        const double eta = P.eta[(long long)d * P.M + (long long)j * P.tstride[d]];
+        const double c = fma(k[d], eta, a[d]);
         const double cc = fmin(fmax(c, 0.0), (double)(P.n[d] - 1));
         const int i0 = min((int)cc, P.n[d] - 2);
         const int il = min(max(i0 - blo[d], 0), bext[d] - 2);
         to[d] = cc - (double)(blo[d] + il);
         off += il * lsU[d];
+        if constexpr (PTAN) { tod[d] = ctan(d, c, eta); if (d == 0) eta0 = eta; }
       }
       const int jb = (int)__umulhi((unsigned)r, P.tmagic), ja = r - jb * tq;   // j_{D-1}, j_{D-2}
       off += ja * tq + jb;
-      g[0] = InterpRec<DO, 0, int>::run(Uw, off, lsU, to);
+      if constexpr (PTAN) DualRec<DO, 0, int, true>::run(Uw, Uv, off, lsU, to, tod, g[0], gd);
+      else g[0] = InterpRec<DO, 0, int>::run(Uw, off, lsU, to);
       if (TWO) iv = InterpRec<DO, 0, int>::run(Uv, off, lsU, to);
       wq = P.wq[m];
     } else if (valid) {
       double c[D], t[D];
+      [[maybe_unused]] double td[D];
       int i0[D];
 #pragma unroll
-      for (int d = 0; d < D; ++d) c[d] = fma(k[d], P.eta[(long long)d * P.M + m], a[d]);
+      for (int d = 0; d < D; ++d) {
+        const double eta = P.eta[(long long)d * P.M + m];
+        c[d] = fma(k[d], eta, a[d]);
+        if constexpr (PTAN) { td[d] = ctan(d, c[d], eta); if (d == 0) eta0 = eta; }
+      }
       interp_cell<D>(P, c, i0, t);
       if (staged) {
         int off = 0;
@@ -280,13 +432,15 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
           t[d] += (double)(i0[d] - blo[d] - il);
           off += il * ls[d];
         }
-        g[0] = InterpRec<D, 0, int>::run(box, off, ls, t);
+        if constexpr (PTAN) DualRec<D, 0, int, false>::run(box, nullptr, off, ls, t, td, g[0], gd);
+        else g[0] = InterpRec<D, 0, int>::run(box, off, ls, t);
         if (TWO) iv = InterpRec<D, 0, int>::run(box + P.cap, off, ls, t);
       } else {
         long long off = 0;
 #pragma unroll
         for (int d = 0; d < D; ++d) off += (long long)i0[d] * P.stride[d];
-        g[0] = InterpRec<D, 0, long long>::run(io.w, off, gs, t);
+        if constexpr (PTAN) DualRec<D, 0, long long, false>::run(io.w, nullptr, off, gs, t, td, g[0], gd);
+        else g[0] = InterpRec<D, 0, long long>::run(io.w, off, gs, t);
         if (TWO) iv = InterpRec<D, 0, long long>::run(io.v, off, gs, t);
       }
       wq = P.wq[m];
@@ -296,14 +450,29 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
       continue;
     }
     double pw[1];
-    pow_fast_n<true, 1>(g, MODE == C_K2 ? 2.0 * (P.theta - 1.0) : (MODE == C_EM || MODE == C_K1 ? P.theta - 1.0 : P.theta), PT, pw);
+    [[maybe_unused]] double lg[1];
+    if constexpr (MODE == C_PTANL) pow_log_n<1>(g, P.theta, PT, pw, lg);
+    else pow_fast_n<true, 1>(g, MODE == C_K2 ? 2.0 * (P.theta - 1.0) : (MODE == C_EM || MODE == C_K1 ? P.theta - 1.0 : P.theta), PT, pw);
+    if constexpr (MODE == C_PTAN) lg[0] = log(g[0]);
     if (MODE == C_JVP) acc = fma(wq * (pw[0] / g[0]), iv, acc);      // W g^(theta-1) interp(v)
     else if (MODE == C_K1 || MODE == C_K2) acc = fma(wq * pw[0], iv, acc);   // Wt g^(p (theta-1)) interp(f)
     else acc = fma(wq, pw[0], acc);
+    if constexpr (PTAN) {
+      // dtheta (s_lambda eta_0 + ln g) + theta ds_lambda eta_0 + theta dg / g
+      const double L = fma(tan.theta, fma(P.sconst[0], eta0, lg[0]), P.theta * fma(tan.sconst[0], eta0, gd / g[0]));
+      accl = fma(wq * pw[0], L, accl);
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if (lane == 0) red[wave] = acc;
+  if constexpr (PTAN) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) accl += __shfl_xor(accl, o);
+  }
+  if (lane == 0) {
+    red[wave] = acc;
+    if constexpr (PTAN) red[4 + wave] = accl;
+  }
   __syncthreads();
   if (wave != 0) return;
   const double e = (red[0] + red[1]) + (red[2] + red[3]);
@@ -336,6 +505,22 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
   const double Kg[1] = {C * e};
   double u[1];
   pow_fast_n<false, 1>(Kg, P.inv_theta, PT, u);                       // every lane of wave 0, same value
+  if constexpr (PTAN) {
+    if (lane == 0) {
+      const double el = (red[4] + red[5]) + (red[6] + red[7]);
+      const double omg = P.one_m_gamma, rho0 = P.rho[0];
+      const double ln_c = omg * (P.mu_c + zval) + 0.5 * omg * omg * sig_c * sig_c + P.theta_rho0 * x[0];
+      const double dsig_c = tan.phi_c * exp(hcval);
+      const double dln_c = omg * tan.mu_c - tan.gamma * (P.mu_c + zval) + omg * sig_c * (omg * dsig_c - tan.gamma * sig_c) +
+                           (tan.theta * rho0 + P.theta * tan.rho[0]) * x[0];
+      const double ln_kg = ln_c + log(e);
+      const double bu = P.beta * u[0];
+      io.out[p] = tan.beta * u[0] + bu * ((dln_c + el / e) * P.inv_theta - tan.theta * ln_kg * P.inv_theta * P.inv_theta);
+      io.c2_out[p] = P.beta * C * u[0] / Kg[0];                       // (T_LIN's expression on T_LIN's e)
+      if (tan.Tw != nullptr) tan.Tw[p] = 1.0 + P.beta * u[0];
+    }
+    return;
+  }
   if (lane == 0) {
     const double tw = 1.0 + P.beta * u[0];
     io.out[p] = tw;

@@ -360,8 +360,8 @@ int sdfs_cont_sdf_mean_dev(sdfs_handle* h, const double* w, double* em) {
   const size_t lds = (size_t)(cd.cap + cd.ucap) * sizeof(double);       // T's: the staged box and its pre-contracted form
   const Counter c("cont:EM", 16.0 * (double)cd.N, (double)cd.N * cd.M * (2.0 * (double)(1 << cd.D) + 2.0 * cd.D + 2.0));
   const dim3 grid((unsigned)cd.N), block(256);
-  return cd.D == 4 ? launch_kernel(h, cont_kernel<4, C_EM>, grid, block, lds, c, cd, io)
-                   : launch_kernel(h, cont_kernel<6, C_EM>, grid, block, lds, c, cd, io);
+  return cd.D == 4 ? launch_kernel(h, cont_kernel<4, C_EM>, grid, block, lds, c, cd, io, ContNoTan{})
+                   : launch_kernel(h, cont_kernel<6, C_EM>, grid, block, lds, c, cd, io, ContNoTan{});
 }
 
 int sdfs_cont_sim_records_dev(sdfs_handle* h, const double* w, const double* em, double* rec) {

@@ -998,6 +998,8 @@ pass_kernel(const PassDesc P, const PassIO io) {
   }
 }
 
+// (not a template: defined once, in sdfs_api.hip's translation unit; cont_ptan.hip leaves it out)
+#ifndef SDFS_NO_DEBUG_POW_KERNEL
 // test hook: out[i] = pow_fast(x[i], y) (n padded so that whole waves run); deg = 6 / 7: the pre-scaled routine powy
 __global__ void __launch_bounds__(256) debug_pow_kernel(const double* __restrict__ x, double y,
                                                         double* __restrict__ out, long long n, int deg) {
@@ -1017,6 +1019,7 @@ __global__ void __launch_bounds__(256) debug_pow_kernel(const double* __restrict
   }
   if (i < n) out[i] = r[0];
 }
+#endif
 
 typedef void (*pass_fn)(const PassDesc, const PassIO);
 

@@ -226,6 +226,7 @@ struct sdfs_handle {
   bool cont = false;
   ContDesc cd;
   double cont_gamma = 0.0;           // gamma as given (the descriptor carries 1 - gamma): the series of cont_sim.hpp
+  double cont_psi = 0.0;             // psi as given: d theta of cont_sens.hpp
   // its tilted expectation K (sdfs_cont_set_tilt_dev, cont_price.hpp): a copy of w, the per-point factor d2 and the tilted
   // node weights stand beside the cached linearisation c1 / c2 and never replace it
   struct {
@@ -769,9 +770,9 @@ int launch_cont(sdfs_handle* h, int mode, const ContIO& io, const Counter& c) {
   const dim3 grid((unsigned)h->cd.N), block(256);
   // the staged box of the iterate + its pre-contracted form (x2 in the J.v kernel: the direction too)
   const size_t lds = (size_t)(h->cd.cap + h->cd.ucap) * sizeof(double);
-  if (mode == MODE_T) return launch_kernel(h, cont_kernel<D, C_T>, grid, block, lds, c, h->cd, io);
-  if (mode == MODE_T_LIN) return launch_kernel(h, cont_kernel<D, C_TLIN>, grid, block, lds, c, h->cd, io);
-  return launch_kernel(h, cont_kernel<D, C_JVP>, grid, block, 2 * lds, c, h->cd, io);
+  if (mode == MODE_T) return launch_kernel(h, cont_kernel<D, C_T>, grid, block, lds, c, h->cd, io, ContNoTan{});
+  if (mode == MODE_T_LIN) return launch_kernel(h, cont_kernel<D, C_TLIN>, grid, block, lds, c, h->cd, io, ContNoTan{});
+  return launch_kernel(h, cont_kernel<D, C_JVP>, grid, block, 2 * lds, c, h->cd, io, ContNoTan{});
 }
 
 // ... and of its tilted expectation (cont_price.hpp) for the SDF power p: p = 0 stages f alone, p = 1, 2 stage w and f
@@ -779,9 +780,9 @@ template <int D>
 int launch_cont_tilted(sdfs_handle* h, int power, const ContDesc& cd, const ContIO& io, const Counter& c) {
   const dim3 grid((unsigned)cd.N), block(256);
   const size_t lds = (size_t)(cd.cap + cd.ucap) * sizeof(double);
-  if (power == 0) return launch_kernel(h, cont_kernel<D, C_K0>, grid, block, lds, c, cd, io);
-  if (power == 1) return launch_kernel(h, cont_kernel<D, C_K1>, grid, block, 2 * lds, c, cd, io);
-  return launch_kernel(h, cont_kernel<D, C_K2>, grid, block, 2 * lds, c, cd, io);
+  if (power == 0) return launch_kernel(h, cont_kernel<D, C_K0>, grid, block, lds, c, cd, io, ContNoTan{});
+  if (power == 1) return launch_kernel(h, cont_kernel<D, C_K1>, grid, block, 2 * lds, c, cd, io, ContNoTan{});
+  return launch_kernel(h, cont_kernel<D, C_K2>, grid, block, 2 * lds, c, cd, io, ContNoTan{});
 }
 
 int run_cont(sdfs_handle* h, const Apply& a) {
@@ -2978,7 +2979,7 @@ int sdfs_create_continuous(int model, int ndim, const int64_t* shapes, const dou
     // dims  : h_lam, h_c, h_z, z  (ssy_wc_ratio_continuous.py:66-87)
     const double* q = params;
     h->beta = q[0]; h->theta = (1 - q[1]) / (1 - 1 / q[2]);
-    cd.one_m_gamma = 1 - q[1]; cd.mu_c = q[3]; cd.phi_c = q[6]; h->cont_gamma = q[1];
+    cd.one_m_gamma = 1 - q[1]; cd.mu_c = q[3]; cd.phi_c = q[6]; h->cont_gamma = q[1]; h->cont_psi = q[2];
     cd.rho[0] = q[9]; cd.sconst[0] = q[12];
     cd.rho[1] = q[8]; cd.sconst[1] = q[11];
     cd.rho[2] = q[7]; cd.sconst[2] = q[10];
@@ -2991,7 +2992,7 @@ int sdfs_create_continuous(int model, int ndim, const int64_t* shapes, const dou
     // dims  : h_lam, h_c, h_z, h_zpi, z, z_pi  (gcy_wc_ratio_continuous.py:78-116)
     const double* q = params;
     h->beta = q[0]; h->theta = (1 - q[2]) / (1 - 1 / q[1]);
-    cd.one_m_gamma = 1 - q[2]; cd.mu_c = q[5]; cd.phi_c = q[6]; h->cont_gamma = q[2];
+    cd.one_m_gamma = 1 - q[2]; cd.mu_c = q[5]; cd.phi_c = q[6]; h->cont_gamma = q[2]; h->cont_psi = q[1];
     cd.rho[0] = q[3]; cd.sconst[0] = q[4];
     cd.rho[1] = q[10]; cd.sconst[1] = q[11];
     cd.rho[2] = q[12]; cd.sconst[2] = q[13];
@@ -4197,4 +4198,5 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
 
 #include "cont_sim.hpp"    // continuous-state paths (sdfs_cont_sdf_mean_dev, sdfs_cont_sim_*), built on the definitions above
 #include "cont_price.hpp"  // continuous-state pricing (sdfs_cont_set_tilt_dev ... sdfs_cont_tilted_horizons_dev), likewise
+#include "cont_sens.hpp"   // continuous-state parameter tangent (sdfs_cont_param_tangent_dev), likewise
 #include "batch_api.hpp"   // the batch API (sdfs_batch_*), built on the definitions above

@@ -211,14 +211,14 @@ def _count(x, name, lo, hi):
     return int(x)
 
 
-def _check_w_star(w_star):
+def _check_w_star(w_star, why="the log return needs ln(w - 1)"):
     import torch
     if isinstance(w_star, torch.Tensor):
         w_ok = bool(torch.all(w_star > 1.0))
     else:
         w_ok = bool(np.all(np.asarray(w_star, dtype=np.float64) > 1.0))
     if not w_ok:
-        raise ValueError("w_star must exceed 1 at every grid point (the log return needs ln(w - 1))")
+        raise ValueError(f"w_star must exceed 1 at every grid point ({why})")
 
 
 # -- the continuous-state model -----------------------------------------------------------------------
@@ -228,10 +228,11 @@ def _check_w_star(w_star):
 # d2(x) = [β^θ (w(x) − 1)^(1−θ)]^p exp(κ_c (μ_c + z) + ½ κ_c² σ_c(x)² + κ_λ ρ_λ h_λ): the K above with the quadrature in
 # place of the chain, and w − 1 where that one has Tw − 1 (``ContinuousOperator.cont_set_tilt_dev`` …).
 
-def _cont_model_request(model, grids, w_star, operator, d, between=None):
+def _cont_model_request(model, grids, w_star, operator, d, between=None, why_w=None):
     """The checks of (model, grids, w_star, operator, d) that ``simulate_continuous`` and the ``*_continuous`` pricing
     functions share, none of which touches a device: (kind, grids, shapes, d).  ``between(nd, shapes)`` runs after the
-    grid and shape checks and before those of the operator -- the place of a caller's own argument checks."""
+    grid and shape checks and before those of the operator -- the place of a caller's own argument checks.  ``why_w``: the caller's reason for
+    w_star > 1, for the error text."""
     kind = _kind(model)[0]                                 # (TypeError for anything but an SSY or a GCY)
     nd = _NDIM[kind]
     try:
@@ -258,7 +259,10 @@ def _cont_model_request(model, grids, w_star, operator, d, between=None):
         d = _count(d, "d", 1, 64)
         if d ** nd > 1 << 24:
             raise ValueError(f"d = {d}: the tensor rule has {d ** nd} > 2^24 nodes")
-    _check_w_star(w_star)
+    if why_w is None:
+        _check_w_star(w_star)
+    else:
+        _check_w_star(w_star, why_w)
     return kind, grids, shapes, d
 
 

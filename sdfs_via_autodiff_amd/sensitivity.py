@@ -373,6 +373,68 @@ def wc_ratio_sensitivities(model, shapes, w_star, wrt=None, rtol=1e-10, atol=0.0
     return out
 
 
+def wc_ratio_sensitivities_continuous(model, grids, w_star, wrt=None, *, rtol=1e-10, atol=0.0, operator=None, d=5, device=0):
+    """``wc_ratio_sensitivities`` for the continuous-state model: {name: dw*/dp_name} (host arrays of the grid's shape)
+    at a converged fixed point ``w_star`` on ``grids`` (as ``wc_ratio_continuous`` returns them), plus
+    ``"_info": {name: (BiCGSTAB iterations, final relative residual)}``.  Per parameter one tangent of T
+    (``ContinuousOperator.cont_param_tangent_dev``) and one solve of (I − J(w*)) x = ∂T/∂p; ``SdfsError`` if a solve
+    breaks down or stops above max(rtol |rhs|₂, atol).
+
+    What is differentiated is the operator a ``ContinuousOperator`` represents, T(w; p) with its grids, nodes and weights
+    held fixed -- ``jax.jvp`` of the reference's ``T`` with respect to the parameters, ``grids, nodes, weights`` closed
+    over.  ``build_grid`` depends on the parameters too; the movement of the grid is NOT part of this derivative.  There
+    is no Rouwenhorst matrix here, so every parameter is admitted, the persistences included.
+
+    wrt: Greek names of ``SSY_PARAMS`` / ``GCY_PARAMS`` (default: all of them).  operator: a ``ContinuousOperator`` on
+    these parameters and grids, whose nodes and weights define the expectation; otherwise one is built with
+    ``qnwnorm([d] * D)`` on ``device``.  Every ValueError / TypeError is raised before any device work."""
+    import math
+    import torch
+    from .pricing import _cont_model_request, _cont_operator, _cont_sync
+    allp = _kind(model)[4]                                         # (TypeError for anything but an SSY or a GCY)
+    req = {}
+
+    def own(nd, shapes):
+        if wrt is None:
+            names = allp
+        elif isinstance(wrt, str):
+            names = (wrt,)
+        else:
+            try:
+                names = tuple(wrt)
+            except TypeError:
+                raise TypeError(f"wrt must be None, a parameter name or a sequence of names, got {wrt!r}") from None
+        for nm in names:
+            if nm not in allp:
+                raise ValueError(f"unknown {type(model).__name__} parameter {nm!r} (one of {', '.join(allp)})")
+        req["names"] = names
+        for what, v, lo_ok in (("rtol", rtol, False), ("atol", atol, True)):
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{what} must be a number, got {v!r}") from None
+            if not math.isfinite(f) or f < 0.0 or (f == 0.0 and not lo_ok):
+                raise ValueError(f"{what} must be {'non-negative' if lo_ok else 'positive'} and finite, got {v!r}")
+            req[what] = f
+
+    _, grids, _, d = _cont_model_request(model, grids, w_star, operator, d, own,
+                                          why_w="a fixed point of T is 1 + β(…)^(1/θ) > 1; the tangent takes ln of its interpolant")
+    names = req["names"]
+    op = _cont_operator(model, grids, operator, d, device)
+    w = _device_grid(op, w_star, "w_star")
+    rhs, x = torch.empty_like(w), torch.empty_like(w)
+    _cont_sync(op)
+    out, info = {}, {}
+    for nm in names:
+        dp = np.zeros(len(allp))
+        dp[allp.index(nm)] = 1.0
+        op.cont_param_tangent_dev(w.data_ptr(), dp, rhs.data_ptr())
+        info[nm] = op.solve_linear_dev(rhs.data_ptr(), x.data_ptr(), False, req["rtol"], req["atol"])   # (ends synchronised)
+        out[nm] = x.cpu().numpy()
+    out["_info"] = info
+    return out
+
+
 def wc_ratio_gradient(model, shapes, w_star, g, rtol=1e-10, atol=0.0, persistence=False):
     """{name: d<g, w*>/dp_name} for every supported parameter at a converged ``w_star``: one transposed solve
     lambda = (I - J(w*)^T)^{-1} g, then <lambda, dT/dp_k> per parameter (a tangent of T each, no further solve).
