@@ -23,7 +23,9 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
+from . import pricing, sensitivity as sens, simulation as sim
 from ._lib import lib
+from ._requests import LAYOUT, _check_n_max, _path_request, _perron_left, _weights
 from .discretize import discretize_gcy, discretize_ssy
 from .models import GCY, SSY
 from .operators import KoopmansOperator, _as_f64
@@ -46,7 +48,9 @@ def _check_algorithm(algorithm):
     if algorithm not in ALGORITHMS:
         raise ValueError(f"algorithm {algorithm!r}: the batched solve supports \"successive_approx\" and \"newton\"")
 
-_KINDS = {"ssy": (_lib.SDFS_MODEL_SSY, 4, 13, 10), "gcy": (_lib.SDFS_MODEL_GCY, 6, 18, 15)}   # id, ndim, nparams, narrays
+# id, ndim, nparams, narrays
+_KINDS = {k: (mid, LAYOUT[k].ndim, len(LAYOUT[k].params), LAYOUT[k].narrays)
+          for k, mid in (("ssy", _lib.SDFS_MODEL_SSY), ("gcy", _lib.SDFS_MODEL_GCY))}
 
 
 def batch_lds_bytes(kind, shapes):
@@ -80,7 +84,6 @@ def batch_cdf_tables(kind, shapes, arrays):
     """(cdf (B, Σ n_a²), cdf0 (B, Σ n_a)): per member the tables of ``simulation.cdf_tables``, axis after axis (the
     cumulative rows row-major), from the batch's stacked arrays (array i: (B, size)).  ValueError when a member's chain
     does not factorise.  Host only."""
-    from . import pricing
     shapes = tuple(int(s) for s in shapes)
     arrays = [np.asarray(a, dtype=np.float64) for a in arrays]
     B = arrays[0].shape[0]
@@ -88,14 +91,14 @@ def batch_cdf_tables(kind, shapes, arrays):
     cdf0 = np.empty((B, int(sum(shapes))))
     for b in range(B):
         o = o0 = 0
-        for a, (qi, n) in enumerate(zip(pricing._AXIS_Q[kind], shapes)):
+        for a, (qi, n) in enumerate(zip(LAYOUT[kind].transitions, shapes)):
             Q = arrays[qi][b].reshape(-1, n, n)
             if np.max(np.abs(Q - Q[:1])) > 1e-14:
                 raise ValueError(f"member {b}, axis {a}: the conditional transition tensor differs between its slices, so "
                                  "the chain does not factorise")
             c = np.cumsum(Q[0], axis=1)
             c[:, -1] = 2.0
-            c0 = np.cumsum(pricing._perron_left(Q[0]))
+            c0 = np.cumsum(_perron_left(Q[0]))
             c0[-1] = 2.0
             cdf[b, o:o + n * n] = c.ravel()
             cdf0[b, o0:o0 + n] = c0
@@ -333,11 +336,10 @@ class BatchOperator:
 
     def _stationary_weights(self):
         """(B, Σ n_a): the stationary marginals of every member's chain, axis-major (as ``pricing.stationary_weights``)."""
-        from . import pricing
         rows = []
         for b in range(self.B):                            # (a batch handle's tensors are unconditional: one matrix per axis)
-            rows.append(np.concatenate([pricing._perron_left(self._arrays[qi][b].reshape(-1, n, n)[0])
-                                        for qi, n in zip(pricing._AXIS_Q[self.kind], self.shapes)]))
+            rows.append(np.concatenate([_perron_left(self._arrays[qi][b].reshape(-1, n, n)[0])
+                                        for qi, n in zip(LAYOUT[self.kind].transitions, self.shapes)]))
         return np.ascontiguousarray(np.stack(rows))
 
     def price_dev(self, w_ptr, kappa, kappa_ts, weights, n_max, EM_ptr, EM2_ptr, pd_ptr, ER_ptr, moments_ptr, horizons_ptr,
@@ -378,7 +380,7 @@ class BatchOperator:
         vectors.  Returns (moments (B, 12), horizons (B, n_max, 4), grids dict or None, n_iter, n_apply, n_horizons,
         rel_resid, resid_T, status)."""
         import torch
-        n_max = _check_n_max(n_max)
+        n_max = _check_n_max(n_max, 0)
         rtol, atol = _check_rtol(rtol, atol)
         kap = _per_member(kappa, self.B, "kappa", optional=True)
         kts = _per_member(kappa_ts, self.B, "kappa_ts")
@@ -448,9 +450,8 @@ class BatchOperator:
         (B, 3 nser + 1, P) or None, "index" (B, P, T+1, d) and "paths" (B, nser, P, T) or None, "status", "n_iter" and
         "rel_resid" of the claim solve."""
         import torch
-        from . import simulation as sim
-        P, T, Bn, off, sd, rtol, fixed = sim._request(self.shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol,
-                                                      return_paths, members=self.B)
+        P, T, Bn, off, sd, rtol, fixed = _path_request(self.shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol,
+                                                       return_paths, members=self.B)
         if Bn + T >= (1 << 32) - 8:
             raise ValueError(f"burn_in + n_periods = {Bn + T} >= 2^32 - 8")
         records = _check_records(records)
@@ -605,13 +606,11 @@ def gradient_batch(models, shapes, w_star, g, rtol=1e-10, atol=0.0, persistence=
     caller's objective and is treated as constant.  ``persistence=True``: all 13 / 18 parameters, else the 9 / 12 that
     leave the transition matrices alone.  Shapes beyond one CU run ``wc_ratio_gradient`` member by member
     (``plan == "loop"``).  Returns a BatchGradient."""
-    from . import sensitivity as sens
     if method != "rouwenhorst":
         raise ValueError(f"parameter tangents are implemented for Rouwenhorst grids only, not {method!r}")
     models, kind, shapes, ndim, B, w = _batch_request(models, shapes, w_star)
     g = _grid_or_batch(g, B, shapes, "g")
-    _, supported, _, _, allp = sens._kind(models[0])
-    names = tuple(allp if persistence else supported)
+    names = tuple(LAYOUT[kind].params if persistence else LAYOUT[kind].supported)
     grad = np.zeros((B, len(names)))
     if batch_lds_bytes(kind, shapes) is not None:
         op = BatchOperator.from_models(models, shapes, method, device)
@@ -681,12 +680,6 @@ def _per_member(x, B, what, optional=False):
     return np.ascontiguousarray(a)
 
 
-def _check_n_max(n_max):
-    if isinstance(n_max, bool) or not isinstance(n_max, (int, np.integer)) or not 0 <= int(n_max) <= 1 << 24:
-        raise ValueError(f"n_max must be an integer in 0 ... 2^24, got {n_max!r}")
-    return int(n_max)
-
-
 def _check_rtol(rtol, atol):
     rtol, atol = float(rtol), float(atol)
     if not (rtol >= 0.0 and np.isfinite(rtol)) or not (atol >= 0.0 and np.isfinite(atol)):
@@ -721,9 +714,8 @@ def _axis_weights_array(weights, B, shapes):
 
 def _member_weights(models, kind, shapes, weights, method):
     """The per-axis weight vectors of every member as (B, Σ n_a): None -> the stationary marginals of each member's
-    chain; one per-axis list (entries as ``pricing._weights`` takes them: a state index or a vector) for all; or a list
+    chain; one per-axis list (entries as ``term_structure`` takes them: a state index or a vector) for all; or a list
     of B such lists."""
-    from . import pricing
     B = len(models)
     disc = discretize_ssy if kind == "ssy" else discretize_gcy
     if weights is None:
@@ -736,7 +728,7 @@ def _member_weights(models, kind, shapes, weights, method):
                 raise ValueError(f"weights needs one entry per axis ({len(shapes)}) or one per-axis list per member ({B}), "
                                  f"got {len(weights)} entries")
             weights = [weights] * B
-        per = [pricing._weights(kind, shapes, g, m) for g, m in zip(weights, models)]
+        per = [_weights(kind, shapes, g, m) for g, m in zip(weights, models)]
     return np.ascontiguousarray(np.stack([np.concatenate(p) for p in per])), per
 
 
@@ -750,9 +742,8 @@ def price_batch(models, shapes, w_star, kappa=None, n_max=0, kappa_ts=0.0, weigh
     stationary marginals, one per-axis list for all, or a list of B such lists; an entry is a state index or a vector).
     Shapes beyond one CU run ``sdf_moments``, ``claim_prices`` and ``term_structure`` member by member
     (``plan == "loop"``).  Returns a BatchPrices."""
-    from . import pricing
     models, kind, shapes, ndim, B, w = _batch_request(models, shapes, w_star)
-    n_max = _check_n_max(n_max)
+    n_max = _check_n_max(n_max, 0)
     rtol, atol = _check_rtol(rtol, atol)
     kap = _per_member(kappa, B, "kappa", optional=True)
     kts = _per_member(kappa_ts, B, "kappa_ts")
@@ -840,8 +831,6 @@ def _check_records(records):
 
 def _sim_fields(names, mom, stats, index, paths):
     """The fields of a BatchSimulation from (B, nstat, 3) moments, (B, nstat, P) statistics or None, and the stored paths."""
-    from . import simulation as sim
-
     def triple(k):
         return {"n": mom[:, k, 0].copy(), "mean": mom[:, k, 1].copy(), "se": mom[:, k, 2].copy()}
 
@@ -864,10 +853,9 @@ def simulate_batch(models, shapes, w_star, n_paths, n_periods, *, burn_in=0, see
     memory (both give the same bits).  ``return_per_path`` adds the (B, P) statistics, ``return_paths`` the indices and
     series (B·P·T <= 2^25).  Shapes beyond one CU run ``simulate`` member by member (``plan == "loop"``), the moments
     formed on the host.  Returns a BatchSimulation."""
-    from . import simulation as sim
     models, kind, shapes, ndim, B, w = _batch_request(models, shapes, w_star)
-    P, T, Bn, off, sd, rtol, fixed = sim._request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol, return_paths,
-                                                  members=B)
+    P, T, Bn, off, sd, rtol, fixed = _path_request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol, return_paths,
+                                                   members=B)
     records = _check_records(records)
     kap = _per_member(kappa, B, "kappa", optional=True)
     names = sim.SERIES_KAPPA if kap is not None else sim.SERIES

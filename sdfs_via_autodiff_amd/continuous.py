@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 from ._lib import lib, check
 from .models import SSY, GCY
-from .operators import KoopmansOperator, _as_f64
+from .operators import KoopmansOperator, _as_f64, _save_list
 from .solvers import solver
 
 
@@ -187,33 +187,20 @@ class ContinuousOperator(KoopmansOperator):
         check(lib.sdfs_cont_sim_paths_dev(self._h, rec_ptr, C.byref(d), stats_ptr, clamped_ptr, final_state_ptr, states_ptr,
                                           series_ptr), self._h)
 
-
     # -- asset prices (pricing.*_continuous) -------------------------------------------------------------
-    def cont_set_tilt_dev(self, w_ptr, sdf_power, kappa_lam, kappa_c):
-        """Form K = K(sdf_power, kappa_lam, kappa_c) at the grid function w (sdfs_cont_set_tilt_dev; w_ptr may be None
-        for sdf_power 0).  w is copied; the cached linearisation stays as it is."""
-        check(lib.sdfs_cont_set_tilt_dev(self._h, w_ptr, int(sdf_power), float(kappa_lam), float(kappa_c)), self._h)
-
-    def cont_apply_tilted_dev(self, f_ptr, out_ptr):
-        """out = K f on device pointers, two distinct grids (sdfs_cont_apply_tilted_dev)."""
-        check(lib.sdfs_cont_apply_tilted_dev(self._h, f_ptr, out_ptr), self._h)
-
-    def cont_solve_tilted_dev(self, rhs_ptr, x_ptr, rtol=1e-10, atol=0.0, max_iter=0):
-        """x = (I - K)^{-1} rhs (sdfs_cont_solve_tilted_dev).  Returns (iterations, relative residual)."""
-        o = _lib.default_opts()
-        o.inner_rtol, o.inner_atol, o.inner_max_iter = float(rtol), float(atol), int(max_iter)
-        it, rel = C.c_int64(), C.c_double()
-        check(lib.sdfs_cont_solve_tilted_dev(self._h, C.byref(o), rhs_ptr, x_ptr, C.byref(it), C.byref(rel)), self._h)
-        return it.value, rel.value
+    # ``set_tilt_dev``, ``apply_tilted_dev`` and ``solve_tilted_dev`` of this operator call these entry points (w is
+    # copied, the cached linearisation stays as it is); the ``cont_*`` names are the same methods.
+    _TILT = (lib.sdfs_cont_set_tilt_dev, lib.sdfs_cont_apply_tilted_dev, lib.sdfs_cont_solve_tilted_dev)
+    cont_set_tilt_dev = KoopmansOperator.set_tilt_dev
+    cont_apply_tilted_dev = KoopmansOperator.apply_tilted_dev
+    cont_solve_tilted_dev = KoopmansOperator.solve_tilted_dev
 
     def cont_tilted_horizons_dev(self, n_max, states=None, save_at=(), save_ptrs=()):
         """P_n = K P_{n-1}, P_0 = 1, for n = 1 ... n_max on the device (sdfs_cont_tilted_horizons_dev).  states: (nq, D)
         query states (None: none).  P_n lands in save_ptrs[j] at n = save_at[j].  Returns (price (n_max, nq): P_n
         interpolated at the states, bracket (n_max, 2): min and max of P_n / P_{n-1} over the grid)."""
         n_max = int(n_max)
-        save_at = [int(n) for n in save_at]
-        if len(save_ptrs) != len(save_at):
-            raise ValueError(f"{len(save_at)} save horizons but {len(save_ptrs)} save pointers")
+        ns, sat, sp = _save_list(save_at, save_ptrs)
         nd = len(self.shapes)
         if states is None:
             xq = np.empty((nd, 0))
@@ -223,9 +210,6 @@ class ContinuousOperator(KoopmansOperator):
                 raise ValueError(f"states must have shape (nq, {nd}), got {st.shape}")
             xq = np.ascontiguousarray(st.T)
         nq = xq.shape[1]
-        ns = len(save_at)
-        sat = (C.c_int64 * max(ns, 1))(*save_at)
-        sp = (C.c_void_p * max(ns, 1))(*[int(p) for p in save_ptrs])
         rows = min(max(n_max, 1), 1 << 24)
         price, bracket = np.empty((rows, nq)), np.empty((rows, 2))
         dp = C.POINTER(C.c_double)

@@ -2,7 +2,8 @@
 // sdfs_cont_solve_tilted_dev, sdfs_cont_tilted_horizons_dev).
 //
 // Not a header of its own: sdfs_api.hip includes it once, after cont_sim.hpp, and it uses sdfs_handle, launch_kernel,
-// Counter, check, fail, apply, linear_solve and cont_handle_ok of those files.
+// Counter, check, fail, apply, cont_handle_ok and the pricing helpers stream_grid, tilted_solve, save_list_ok and
+// horizon_loop of those files.
 //
 // The tilted expectation K(p, kappa_lambda, kappa_c) is the C_K0 / C_K1 / C_K2 form of cont_kernel (cont_kernel.hpp):
 // the node loop of J.v on the tilted node weights, with the exponent p (theta - 1) on the interpolant of w and the
@@ -122,10 +123,6 @@ int cont_tilt_ok(sdfs_handle* h, const char* fn, bool need_tilt) {
   return 0;
 }
 
-int cont_stream_grid(const sdfs_handle* h, long long n) {
-  return (int)std::max<long long>(1, std::min<long long>((n + CPRICE_BLOCK - 1) / CPRICE_BLOCK, (long long)h->num_cus * 16));
-}
-
 // device buffers of one call, released however it ends
 struct ContScratch {
   std::vector<void*> p;
@@ -159,7 +156,7 @@ int sdfs_cont_set_tilt_dev(sdfs_handle* h, const double* w, int sdf_power, doubl
   HIPCHK(h, hipMemcpyAsync(Ct.wq, Ct.wq_host.data(), sizeof(double) * (size_t)cd.M, hipMemcpyHostToDevice, h->stream));
   if (w) HIPCHK(h, hipMemcpyAsync(Ct.w, w, sizeof(double) * (size_t)cd.N, hipMemcpyDeviceToDevice, h->stream));
   const double n8 = 8.0 * (double)cd.N;
-  if ((rc = launch_kernel(h, k_cont_tilt_d2, dim3(cont_stream_grid(h, cd.N)), dim3(CPRICE_BLOCK), 0,
+  if ((rc = launch_kernel(h, k_cont_tilt_d2, dim3(stream_grid(h, cd.N, CPRICE_BLOCK)), dim3(CPRICE_BLOCK), 0,
                           Counter("cprice:d2", (sdf_power ? 2 : 1) * n8, 0), cd, sdf_power, kappa_lam, kappa_c,
                           sdf_power ? (const double*)Ct.w : nullptr, Ct.d2)))
     return rc;
@@ -181,11 +178,7 @@ int sdfs_cont_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const doub
                                double* final_rel_resid) {
   int rc = check(h); if (rc) return rc;
   if ((rc = cont_tilt_ok(h, "sdfs_cont_solve_tilted_dev", true))) return rc;
-  if (!rhs || !x) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
-  sdfs_opts o;
-  if (opts) o = *opts; else sdfs_default_opts(&o);
-  o.krylov_f32 = 0;                        // (fp64 whatever the options say)
-  return linear_solve(h, o, MODE_JVP, rhs, x, n_iter, final_rel_resid, h->ctilt.w, h->ctilt.d2, "tilted continuous");
+  return tilted_solve(h, opts, rhs, x, n_iter, final_rel_resid, h->ctilt.w, h->ctilt.d2, "tilted continuous");
 }
 
 int sdfs_cont_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* states, int64_t nq, int64_t n_save,
@@ -196,13 +189,7 @@ int sdfs_cont_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* s
   if (nq < 0 || nq > (1LL << 24) || (nq > 0 && (!states || !price_host)))
     return fail(h, SDFS_ERR_ARG, "nq = %lld query states: 0 ... 2^24, with states and price_host", (long long)nq);
   if (!bracket_host) return fail(h, SDFS_ERR_ARG, "NULL bracket_host");
-  if (n_save < 0 || (n_save > 0 && (!save_at || !save_dev))) return fail(h, SDFS_ERR_ARG, "bad save list");
-  for (int64_t j = 0; j < n_save; ++j) {
-    if (save_at[j] < 1 || save_at[j] > n_max || (j > 0 && save_at[j] <= save_at[j - 1]))
-      return fail(h, SDFS_ERR_ARG, "save_at must rise strictly within 1 ... n_max (save_at[%lld] = %lld)", (long long)j,
-                  (long long)save_at[j]);
-    if (!save_dev[j]) return fail(h, SDFS_ERR_ARG, "save_dev[%lld] is NULL", (long long)j);
-  }
+  if ((rc = save_list_ok(h, n_max, n_save, save_at, save_dev))) return rc;
   const ContDesc& cd = h->cd;
   for (int64_t i = 0; i < nq * cd.D; ++i)
     if (!std::isfinite(states[i])) return fail(h, SDFS_ERR_ARG, "states[%lld] is not finite", (long long)i);
@@ -217,39 +204,25 @@ int sdfs_cont_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* s
     HIPCHK(h, hipMemcpyAsync(xq, states, sizeof(double) * (size_t)nq * cd.D, hipMemcpyHostToDevice, h->stream));
   }
   const long long N = cd.N;
-  const int fgrid = cont_stream_grid(h, N);
-  const int rgrid = std::min(fgrid, CPRICE_MAX_BLOCKS);
+  const int rgrid = std::min(stream_grid(h, N, CPRICE_BLOCK), CPRICE_MAX_BLOCKS);
   const dim3 qgrid((unsigned)((nq + 255) / 256));
   const int cid = h->profiling ? counter_id(h, "cprice:horizon_reduce", 16.0 * (double)N, 0) : -1;
-  hipLaunchKernelGGL(k_cont_fill, dim3(fgrid), dim3(CPRICE_BLOCK), 0, h->stream, Ct.pa, N, 1.0);
-  HIPCHK(h, hipGetLastError());
-  double* prev = Ct.pa;
-  double* cur = Ct.pb;
-  int64_t js = 0;
-  for (int64_t n = 1; n <= n_max; ++n) {
-    Apply a(MODE_JVP, prev, cur, prev);
-    a.lc1 = Ct.w; a.lc2 = Ct.d2;
-    if ((rc = apply(h, a))) return rc;
+  rc = horizon_loop(h, N, n_max, k_cont_fill, CPRICE_BLOCK, Ct.pa, Ct.pb, Ct.w, Ct.d2, n_save, save_at, save_dev,
+                    [&](int64_t n, const double* cur, const double* prev) {
     {
       ProfScope ps(h, cid);
-      hipLaunchKernelGGL(k_cont_horizon_reduce, dim3(rgrid), dim3(CPRICE_BLOCK), 0, h->stream, N, (const double*)cur,
-                         (const double*)prev, Ct.part);
+      hipLaunchKernelGGL(k_cont_horizon_reduce, dim3(rgrid), dim3(CPRICE_BLOCK), 0, h->stream, N, cur, prev, Ct.part);
     }
     hipLaunchKernelGGL(k_cont_horizon_finish, dim3(1), dim3(64), 0, h->stream, (const double*)Ct.part, rgrid,
                        res + CPRICE_NRED * (n - 1));
     if (nq > 0) {
-      if (cd.D == 4) hipLaunchKernelGGL((lin_interp_kernel<4>), qgrid, dim3(256), 0, h->stream, cd, (const double*)cur, (const double*)xq,
+      if (cd.D == 4) hipLaunchKernelGGL((lin_interp_kernel<4>), qgrid, dim3(256), 0, h->stream, cd, cur, (const double*)xq,
                                         (long long)nq, pq + (size_t)(n - 1) * (size_t)nq);
-      else hipLaunchKernelGGL((lin_interp_kernel<6>), qgrid, dim3(256), 0, h->stream, cd, (const double*)cur, (const double*)xq,
+      else hipLaunchKernelGGL((lin_interp_kernel<6>), qgrid, dim3(256), 0, h->stream, cd, cur, (const double*)xq,
                               (long long)nq, pq + (size_t)(n - 1) * (size_t)nq);
     }
-    HIPCHK(h, hipGetLastError());
-    if (js < n_save && save_at[js] == n) {
-      HIPCHK(h, hipMemcpyAsync(save_dev[js], cur, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, h->stream));
-      ++js;
-    }
-    std::swap(prev, cur);
-  }
+  });
+  if (rc) return rc;
   std::vector<double> hres((size_t)CPRICE_NRED * n_max);
   HIPCHK(h, hipMemcpyAsync(hres.data(), res, sizeof(double) * hres.size(), hipMemcpyDeviceToHost, h->stream));
   if (nq > 0) HIPCHK(h, hipMemcpyAsync(price_host, pq, sizeof(double) * (size_t)nq * (size_t)n_max, hipMemcpyDeviceToHost, h->stream));

@@ -369,7 +369,7 @@ int sdfs_cont_sim_records_dev(sdfs_handle* h, const double* w, const double* em,
   if ((rc = cont_handle_ok(h, "sdfs_cont_sim_records_dev"))) return rc;
   if (!w || !em || !rec) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
   const long long N = h->cd.N;
-  const int grid = (int)std::min<long long>((N + CSIM_BLOCK - 1) / CSIM_BLOCK, (long long)h->num_cus * 16);
+  const int grid = stream_grid(h, N, CSIM_BLOCK);
   return launch_kernel(h, k_cont_sim_records, dim3(grid), dim3(CSIM_BLOCK), 0, Counter("csim:records", 32.0 * (double)N, 0), N, w, em,
                        reinterpret_cast<double2*>(rec));
 }

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <map>
 #include <mutex>
@@ -2905,6 +2906,11 @@ int krylov_step_t(sdfs_handle* h, int step, long long n, void* const* v, double*
   HIPCHK(h, hipGetLastError());
   return 0;
 }
+
+// workgroups of a grid-stride pass over n points: one per `block` points, at most 16 per CU
+int stream_grid(const sdfs_handle* h, long long n, int block) {
+  return (int)std::min<long long>((n + block - 1) / block, (long long)h->num_cus * 16);
+}
 }  // namespace
 
 // ===========================================================================
@@ -3332,7 +3338,7 @@ int sdfs_param_tangent_gen_dev(sdfs_handle* h, const double* w, const double* dp
   memset(&g, 0, sizeof g);
   g.n = h->N; g.ndim = h->ndim;
   for (int a = 0; a < h->ndim; ++a) { g.ext[a] = h->shape[a]; g.a3s[a] = h->sens.a3s[a]; }
-  const int grid = (int)std::min<long long>((h->N + SENS_BLOCK - 1) / SENS_BLOCK, (long long)h->num_cus * 16);
+  const int grid = stream_grid(h, h->N, SENS_BLOCK);
   const double n8 = 8.0 * (double)h->N;
   if (need_jv) {
     g.ax_tab = h->sens.ax_a1;
@@ -3382,7 +3388,7 @@ int linear_solve(sdfs_handle* h, const sdfs_opts& o, int mode, const double* rhs
   if ((rc = ensure_scalars(h))) return rc;
   while (h->kry.size() < 7) { double* p = nullptr; if ((rc = dev_alloc(h, &p, (size_t)h->N))) return rc; h->kry.push_back(p); }
   const long long n = h->N;
-  const int grid = (int)std::min<long long>((n + SENS_BLOCK - 1) / SENS_BLOCK, (long long)h->num_cus * 16);
+  const int grid = stream_grid(h, n, SENS_BLOCK);
   // the loop solves (A - I) y = b: b = -rhs gives y = (I - A)^{-1} rhs
   hipLaunchKernelGGL(k_sens_neg, dim3(grid), dim3(SENS_BLOCK), 0, h->stream, rhs, h->kry[6], n);
   HIPCHK(h, hipGetLastError());
@@ -3444,6 +3450,53 @@ int price_grid(const sdfs_handle* h) {
   return (int)std::max<long long>(1, std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK,
                                                          std::min<long long>((long long)h->num_cus * 8, PRICE_MAX_BLOCKS)));
 }
+
+// -- shared with the continuous-state pricing entry points (cont_price.hpp) --
+// x = (I - K)^{-1} rhs, K the J.v kernels on the tilt's scalings (lc1, lc2); fp64 whatever the options say
+int tilted_solve(sdfs_handle* h, const sdfs_opts* opts, const double* rhs, double* x, int64_t* n_iter, double* final_rel_resid,
+                 const double* lc1, const double* lc2, const char* what) {
+  if (!rhs || !x) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
+  sdfs_opts o;
+  if (opts) o = *opts; else sdfs_default_opts(&o);
+  o.krylov_f32 = 0;
+  return linear_solve(h, o, MODE_JVP, rhs, x, n_iter, final_rel_resid, lc1, lc2, what);
+}
+
+// the save list of a horizon loop: horizons rising strictly within 1 ... n_max, a device grid for each
+int save_list_ok(sdfs_handle* h, int64_t n_max, int64_t n_save, const int64_t* save_at, double* const* save_dev) {
+  if (n_save < 0 || (n_save > 0 && (!save_at || !save_dev))) return fail(h, SDFS_ERR_ARG, "bad save list");
+  for (int64_t j = 0; j < n_save; ++j) {
+    if (save_at[j] < 1 || save_at[j] > n_max || (j > 0 && save_at[j] <= save_at[j - 1]))
+      return fail(h, SDFS_ERR_ARG, "save_at must rise strictly within 1 ... n_max (save_at[%lld] = %lld)", (long long)j,
+                  (long long)save_at[j]);
+    if (!save_dev[j]) return fail(h, SDFS_ERR_ARG, "save_dev[%lld] is NULL", (long long)j);
+  }
+  return 0;
+}
+
+// P_n = K P_{n-1}, P_0 = 1 (written by `fill`) for n = 1 ... n_max on the pair (prev, cur), K as in tilted_solve.  After
+// the product of horizon n, per_horizon(n, P_n, P_{n-1}) enqueues what the caller keeps of it; then P_n goes to
+// save_dev[j] where n = save_at[j].
+int horizon_loop(sdfs_handle* h, long long N, int64_t n_max, void (*fill)(double*, long long, double), int block, double* prev,
+                 double* cur, const double* lc1, const double* lc2, int64_t n_save, const int64_t* save_at, double* const* save_dev,
+                 const std::function<void(int64_t, const double*, const double*)>& per_horizon) {
+  hipLaunchKernelGGL(fill, dim3(stream_grid(h, N, block)), dim3(block), 0, h->stream, prev, N, 1.0);
+  HIPCHK(h, hipGetLastError());
+  int64_t js = 0;
+  for (int64_t n = 1; n <= n_max; ++n) {
+    Apply a(MODE_JVP, prev, cur, prev);
+    a.lc1 = lc1; a.lc2 = lc2;
+    if (int rc = apply(h, a)) return rc;
+    per_horizon(n, (const double*)cur, (const double*)prev);
+    HIPCHK(h, hipGetLastError());
+    if (js < n_save && save_at[js] == n) {
+      HIPCHK(h, hipMemcpyAsync(save_dev[js], cur, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, h->stream));
+      ++js;
+    }
+    std::swap(prev, cur);
+  }
+  return 0;
+}
 }  // namespace
 
 int sdfs_set_tilt_dev(sdfs_handle* h, const double* w, int sdf_power, double kappa_lam, double kappa_c) {
@@ -3482,7 +3535,7 @@ int sdfs_set_tilt_dev(sdfs_handle* h, const double* w, int sdf_power, double kap
     h->lin_stale = false;
   }
   const PriceGeom g = price_geom(h);
-  const int grid = (int)std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK, (long long)h->num_cus * 16);
+  const int grid = stream_grid(h, h->N, PRICE_BLOCK);
   const double* ez = xz != 0.0 ? (const double*)Pr.ez : nullptr;
   const double n8 = 8.0 * (double)h->N;
   // (power 0 reads no linearisation)
@@ -3510,11 +3563,7 @@ int sdfs_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const double* r
                           double* final_rel_resid) {
   int rc = check(h); if (rc) return rc;
   if ((rc = price_handle_ok(h, "sdfs_solve_tilted_dev", true))) return rc;
-  if (!rhs || !x) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
-  sdfs_opts o;
-  if (opts) o = *opts; else sdfs_default_opts(&o);
-  o.krylov_f32 = 0;                        // (fp64 whatever the options say)
-  return linear_solve(h, o, MODE_JVP, rhs, x, n_iter, final_rel_resid, h->price.d1, h->price.d2, "tilted");
+  return tilted_solve(h, opts, rhs, x, n_iter, final_rel_resid, h->price.d1, h->price.d2, "tilted");
 }
 
 int sdfs_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* const* weight_axes, int64_t n_save,
@@ -3523,13 +3572,7 @@ int sdfs_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* const*
   if ((rc = price_handle_ok(h, "sdfs_tilted_horizons_dev", true))) return rc;
   if (n_max < 1 || n_max > (1LL << 24)) return fail(h, SDFS_ERR_ARG, "n_max = %lld: 1 ... 2^24 horizons", (long long)n_max);
   if (!out_host) return fail(h, SDFS_ERR_ARG, "NULL out_host");
-  if (n_save < 0 || (n_save > 0 && (!save_at || !save_dev))) return fail(h, SDFS_ERR_ARG, "bad save list");
-  for (int64_t j = 0; j < n_save; ++j) {
-    if (save_at[j] < 1 || save_at[j] > n_max || (j > 0 && save_at[j] <= save_at[j - 1]))
-      return fail(h, SDFS_ERR_ARG, "save_at must rise strictly within 1 ... n_max (save_at[%lld] = %lld)", (long long)j,
-                  (long long)save_at[j]);
-    if (!save_dev[j]) return fail(h, SDFS_ERR_ARG, "save_dev[%lld] is NULL", (long long)j);
-  }
+  if ((rc = save_list_ok(h, n_max, n_save, save_at, save_dev))) return rc;
   PriceWeights wt;
   for (int a = 0; a < SENS_MAXD; ++a) for (int k = 0; k < SENS_MAXN; ++k) wt.t[a][k] = 0.0;
   for (int a = 0; a < h->ndim; ++a)
@@ -3549,30 +3592,16 @@ int sdfs_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* const*
   }
   const PriceGeom g = price_geom(h);
   const int rgrid = price_grid(h);
-  const int fgrid = (int)std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK, (long long)h->num_cus * 16);
   const int cid = h->profiling ? counter_id(h, "price:horizon_reduce", 16.0 * (double)h->N, 0) : -1;
-  hipLaunchKernelGGL(k_price_fill, dim3(fgrid), dim3(PRICE_BLOCK), 0, h->stream, Pr.pa, (long long)h->N, 1.0);
-  HIPCHK(h, hipGetLastError());
-  double* prev = Pr.pa;
-  double* cur = Pr.pb;
-  int64_t js = 0;
-  for (int64_t n = 1; n <= n_max; ++n) {
-    Apply a(MODE_JVP, prev, cur, prev);
-    a.lc1 = Pr.d1; a.lc2 = Pr.d2;
-    if ((rc = apply(h, a))) return rc;
+  rc = horizon_loop(h, h->N, n_max, k_price_fill, PRICE_BLOCK, Pr.pa, Pr.pb, Pr.d1, Pr.d2, n_save, save_at, save_dev,
+                    [&](int64_t n, const double* cur, const double* prev) {
     {
       ProfScope ps(h, cid);
-      hipLaunchKernelGGL(k_horizon_reduce, dim3(rgrid), dim3(PRICE_BLOCK), 0, h->stream, g, wt, (const double*)cur,
-                         (const double*)prev, Pr.part);
+      hipLaunchKernelGGL(k_horizon_reduce, dim3(rgrid), dim3(PRICE_BLOCK), 0, h->stream, g, wt, cur, prev, Pr.part);
     }
     hipLaunchKernelGGL(k_horizon_finish, dim3(1), dim3(64), 0, h->stream, (const double*)Pr.part, rgrid, Pr.res + PRICE_NSUM * (n - 1));
-    HIPCHK(h, hipGetLastError());
-    if (js < n_save && save_at[js] == n) {
-      HIPCHK(h, hipMemcpyAsync(save_dev[js], cur, sizeof(double) * (size_t)h->N, hipMemcpyDeviceToDevice, h->stream));
-      ++js;
-    }
-    std::swap(prev, cur);
-  }
+  });
+  if (rc) return rc;
   std::vector<double> res((size_t)PRICE_NSUM * n_max);
   HIPCHK(h, hipMemcpyAsync(res.data(), Pr.res, sizeof(double) * res.size(), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3634,7 +3663,7 @@ int sdfs_sim_records_dev(sdfs_handle* h, const double* w, const double* v, doubl
     for (size_t i = 0; i < zt.size(); ++i) zt[i] = S.mu_c + S.z[i];
     if ((rc = upload(h, &Sm.zt, zt.data(), zt.size()))) return rc;
   }
-  const int fgrid = (int)std::min<long long>((h->N + PRICE_BLOCK - 1) / PRICE_BLOCK, (long long)h->num_cus * 16);
+  const int fgrid = stream_grid(h, h->N, PRICE_BLOCK);
   hipLaunchKernelGGL(k_price_fill, dim3(fgrid), dim3(PRICE_BLOCK), 0, h->stream, Sm.one, (long long)h->N, 1.0);
   HIPCHK(h, hipGetLastError());
   // E_x[M] = K(1, theta, -gamma) 1: the product sdf_moments forms, bit for bit

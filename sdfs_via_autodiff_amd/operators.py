@@ -24,10 +24,27 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib, check
+from ._requests import LAYOUT
 
 
 def _as_f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+def _inner_opts(rtol, atol, max_iter):
+    """Default options with the stopping rule of a linear solve."""
+    o = _lib.default_opts()
+    o.inner_rtol, o.inner_atol, o.inner_max_iter = float(rtol), float(atol), int(max_iter)
+    return o
+
+
+def _save_list(save_at, save_ptrs):
+    """(count, ctypes horizons, ctypes device pointers) of the save list of a horizon loop."""
+    save_at = [int(n) for n in save_at]
+    if len(save_ptrs) != len(save_at):
+        raise ValueError(f"{len(save_at)} save horizons but {len(save_ptrs)} save pointers")
+    ns = len(save_at)
+    return ns, (C.c_int64 * max(ns, 1))(*save_at), (C.c_void_p * max(ns, 1))(*[int(p) for p in save_ptrs])
 
 
 # -- call tracing -----------------------------------------------------------------------------
@@ -180,8 +197,6 @@ class KoopmansOperator:
             raise ValueError(f"dparams has {len(dparams)} entries, the operator has {len(self.params)} parameters")
         return (C.c_double * len(dparams))(*dparams)
 
-    _TRANSITION_ARRAYS = {"ssy": (1, 3, 5, 7), "gcy": (1, 3, 5, 8, 11, 14)}
-
     def _dgen(self, dgen):
         """ctypes array of the per-axis generator pointers (None -> NULL), each 3 n_a doubles: sub, diag, super."""
         if len(dgen) != len(self.shapes):
@@ -210,7 +225,8 @@ class KoopmansOperator:
             check(lib.sdfs_param_tangent_dev(self._h, w_ptr, dp, ptrs, out_ptr, Tw_ptr), self._h)
         else:
             if darrays is not None:
-                trans = self._TRANSITION_ARRAYS.get(getattr(self, "model_name", None), ())
+                layout = LAYOUT.get(getattr(self, "model_name", None))
+                trans = layout.transitions if layout else ()
                 darrays = [None if i in trans else d for i, d in enumerate(darrays)]
             ptrs, keep = self._darrays(darrays)
             gptrs, gkeep = self._dgen(dgen)
@@ -221,29 +237,30 @@ class KoopmansOperator:
     def solve_linear_dev(self, rhs_ptr, x_ptr, transpose=False, rtol=1e-10, atol=0.0, max_iter=0):
         """x = (I - J)^{-1} rhs (transpose: (I - J^T)^{-1} rhs) at the cached linearisation (sdfs_solve_linear_dev).
         Returns (iterations, relative residual)."""
-        o = _lib.default_opts()
-        o.inner_rtol, o.inner_atol, o.inner_max_iter = float(rtol), float(atol), int(max_iter)
         it, rel = C.c_int64(), C.c_double()
-        check(lib.sdfs_solve_linear_dev(self._h, int(bool(transpose)), C.byref(o), rhs_ptr, x_ptr, C.byref(it),
-                                        C.byref(rel)), self._h)
+        check(lib.sdfs_solve_linear_dev(self._h, int(bool(transpose)), C.byref(_inner_opts(rtol, atol, max_iter)), rhs_ptr,
+                                        x_ptr, C.byref(it), C.byref(rel)), self._h)
         return it.value, rel.value
 
     # -- asset pricing: the tilted expectation K (pricing.py) ------------------------------------------------------
+    _TILT = (lib.sdfs_set_tilt_dev, lib.sdfs_apply_tilted_dev, lib.sdfs_solve_tilted_dev)   # (``ContinuousOperator`` has its own)
+
     def set_tilt_dev(self, w_ptr, sdf_power, kappa_lam, kappa_c):
-        """Form K = K(sdf_power, kappa_lam, kappa_c) linearised at w (sdfs_set_tilt_dev; w_ptr may be None for
-        sdf_power 0).  Replaces the cached linearisation with the one at w."""
-        check(lib.sdfs_set_tilt_dev(self._h, w_ptr, int(sdf_power), float(kappa_lam), float(kappa_c)), self._h)
+        """Form K = K(sdf_power, kappa_lam, kappa_c) at w (sdfs_set_tilt_dev; w_ptr may be None for sdf_power 0).  On the
+        discretised operator this linearises at w and replaces the cached linearisation; the continuous one
+        (sdfs_cont_set_tilt_dev) copies w and leaves the cached linearisation as it is."""
+        check(self._TILT[0](self._h, w_ptr, int(sdf_power), float(kappa_lam), float(kappa_c)), self._h)
 
     def apply_tilted_dev(self, f_ptr, out_ptr):
-        """out = K f on device pointers (sdfs_apply_tilted_dev)."""
-        check(lib.sdfs_apply_tilted_dev(self._h, f_ptr, out_ptr), self._h)
+        """out = K f on device pointers, two distinct grids (sdfs_apply_tilted_dev, sdfs_cont_apply_tilted_dev)."""
+        check(self._TILT[1](self._h, f_ptr, out_ptr), self._h)
 
     def solve_tilted_dev(self, rhs_ptr, x_ptr, rtol=1e-10, atol=0.0, max_iter=0):
-        """x = (I - K)^{-1} rhs (sdfs_solve_tilted_dev).  Returns (iterations, relative residual)."""
-        o = _lib.default_opts()
-        o.inner_rtol, o.inner_atol, o.inner_max_iter = float(rtol), float(atol), int(max_iter)
+        """x = (I - K)^{-1} rhs (sdfs_solve_tilted_dev, sdfs_cont_solve_tilted_dev).  Returns (iterations, relative
+        residual)."""
         it, rel = C.c_int64(), C.c_double()
-        check(lib.sdfs_solve_tilted_dev(self._h, C.byref(o), rhs_ptr, x_ptr, C.byref(it), C.byref(rel)), self._h)
+        check(self._TILT[2](self._h, C.byref(_inner_opts(rtol, atol, max_iter)), rhs_ptr, x_ptr, C.byref(it), C.byref(rel)),
+              self._h)
         return it.value, rel.value
 
     def tilted_horizons_dev(self, n_max, weight_axes=None, save_at=(), save_ptrs=()):
@@ -251,9 +268,7 @@ class KoopmansOperator:
         host vector per axis (product-form weights; None = uniform).  P_n lands in save_ptrs[j] at n = save_at[j].
         Returns an (n_max, 4) array: <g, P_n>, <g, -log P_n> / n, min and max of P_n / P_{n-1}."""
         n_max = int(n_max)
-        save_at = [int(n) for n in save_at]
-        if len(save_ptrs) != len(save_at):
-            raise ValueError(f"{len(save_at)} save horizons but {len(save_ptrs)} save pointers")
+        ns, sat, sp = _save_list(save_at, save_ptrs)
         keep, wp = [], None
         if weight_axes is not None:
             if len(weight_axes) != len(self.shapes):
@@ -264,9 +279,6 @@ class KoopmansOperator:
                     raise ValueError(f"weight_axes[{a}] has {g.size} entries, axis {a} has {n} states")
                 keep.append(g)
             wp = (C.POINTER(C.c_double) * len(keep))(*[g.ctypes.data_as(C.POINTER(C.c_double)) for g in keep])
-        ns = len(save_at)
-        sat = (C.c_int64 * max(ns, 1))(*save_at)
-        sp = (C.c_void_p * max(ns, 1))(*[int(p) for p in save_ptrs])
         out = np.empty((max(n_max, 1), 4))
         check(lib.sdfs_tilted_horizons_dev(self._h, n_max, wp, ns, sat, sp,
                                            out.ctypes.data_as(C.POINTER(C.c_double))), self._h)

@@ -28,21 +28,11 @@ opens them to ``wc_ratio_sensitivities`` / ``wc_ratio_gradient``.
 import numpy as np
 
 from .discretize import _rouwenhorst_grid, discretize_ssy, discretize_gcy
-from .models import SSY, GCY
-from .operators import KoopmansOperator
+from ._requests import (LAYOUT, SSY_PARAMS, GCY_PARAMS, _kind, _operator, _device_grid, _cont_grids, _cont_operator_or_d,
+                        _cont_operator, _check_w_star, _check_tolerance, _Fence)
 
-SSY_PARAMS = ("β", "γ", "ψ", "μ_c", "ρ", "φ_z", "φ_c", "ρ_z", "ρ_c", "ρ_λ", "s_z", "s_c", "s_λ")
-GCY_PARAMS = ("β", "ψ", "γ", "ρ_λ", "s_λ", "μ_c", "φ_c", "ρ", "ρ_π", "φ_z", "ρ_c", "s_c", "ρ_z", "s_z",
-              "ρ_ππ", "φ_zπ", "ρ_zπ", "s_zπ")
-SSY_SUPPORTED = ("β", "γ", "ψ", "μ_c", "φ_z", "φ_c", "s_z", "s_c", "s_λ")
-GCY_SUPPORTED = ("β", "ψ", "γ", "s_λ", "μ_c", "φ_c", "ρ_π", "φ_z", "s_c", "s_z", "φ_zπ", "s_zπ")
-SSY_PERSISTENCE = ("ρ", "ρ_z", "ρ_c", "ρ_λ")
-GCY_PERSISTENCE = ("ρ_λ", "ρ", "ρ_c", "ρ_z", "ρ_ππ", "ρ_zπ")
-# grid axis whose transition matrix a persistence moves: SSY (h_λ, h_c, h_z, z), GCY (z, z_π, h_z, h_c, h_zπ, h_λ)
-_SSY_AXIS = {"ρ_λ": 0, "ρ_c": 1, "ρ_z": 2, "ρ": 3}
-_GCY_AXIS = {"ρ": 0, "ρ_ππ": 1, "ρ_z": 2, "ρ_c": 3, "ρ_zπ": 4, "ρ_λ": 5}
-_SSY_TRANS = (1, 3, 5, 7)                      # transition array of each axis
-_GCY_TRANS = (1, 3, 5, 8, 11, 14)
+SSY_SUPPORTED, GCY_SUPPORTED = LAYOUT["ssy"].supported, LAYOUT["gcy"].supported
+SSY_PERSISTENCE, GCY_PERSISTENCE = tuple(LAYOUT["ssy"].persistence), tuple(LAYOUT["gcy"].persistence)
 
 
 def _check(names, supported, name, method, model):
@@ -147,8 +137,9 @@ def discretize_ssy_persistence_tangent(ssy, shapes, name, method="rouwenhorst"):
     _check_persistence(SSY_PARAMS, SSY_PERSISTENCE, name, method, "SSY")
     arr = discretize_ssy(ssy, shapes)
     dparams, d, dgen = _ssy_persistence(ssy, shapes, name, arr)
-    ax = _SSY_AXIS[name]
-    d[_SSY_TRANS[ax]] = _apply_generator(dgen[ax], arr[_SSY_TRANS[ax]])
+    ax = LAYOUT["ssy"].persistence[name]
+    qi = LAYOUT["ssy"].transitions[ax]
+    d[qi] = _apply_generator(dgen[ax], arr[qi])
     return dparams, _zeros_for_none(d, arr), dgen
 
 
@@ -160,7 +151,7 @@ def _ssy_persistence(ssy, shapes, name, arr):
     dparams = np.zeros(len(SSY_PARAMS))
     dparams[SSY_PARAMS.index(name)] = 1.0
     dgen = [None] * 4
-    ax = _SSY_AXIS[name]
+    ax = LAYOUT["ssy"].persistence[name]
     if name == "ρ_λ":
         d[0] = arr[0] * _grid_drho(ρ_λ)
         dgen[ax] = rouwenhorst_generator(n_h_λ, ρ_λ)
@@ -236,8 +227,9 @@ def discretize_gcy_persistence_tangent(gcy, shapes, name, method="rouwenhorst"):
     _check_persistence(GCY_PARAMS, GCY_PERSISTENCE, name, method, "GCY")
     arr = discretize_gcy(gcy, shapes)
     dparams, d, dgen = _gcy_persistence(gcy, shapes, name, arr)
-    ax = _GCY_AXIS[name]
-    d[_GCY_TRANS[ax]] = _apply_generator(dgen[ax], arr[_GCY_TRANS[ax]])
+    ax = LAYOUT["gcy"].persistence[name]
+    qi = LAYOUT["gcy"].transitions[ax]
+    d[qi] = _apply_generator(dgen[ax], arr[qi])
     return dparams, _zeros_for_none(d, arr), dgen
 
 
@@ -251,7 +243,7 @@ def _gcy_persistence(gcy, shapes, name, arr):
     dparams = np.zeros(len(GCY_PARAMS))
     dparams[GCY_PARAMS.index(name)] = 1.0
     dgen = [None] * 6
-    ax = _GCY_AXIS[name]
+    ax = LAYOUT["gcy"].persistence[name]
     z_π, σ_z, σ_zπ = arr[2], arr[6], arr[12]
     g_z = _unit_grid(n_z, ρ)                   # z_states[b, c, e, a] = σ_z[c] g_z[a] + ρ_π z_π[e, b] / (1 - ρ)
     g_zπ = _unit_grid(n_z_π, ρ_ππ)             # z_π_states[e, b] = σ_zπ[e] g_zπ[b]
@@ -288,63 +280,21 @@ def _gcy_persistence(gcy, shapes, name, arr):
 
 
 # -- fixed-point sensitivities ---------------------------------------------------------------------------------------
-def _kind(model):
-    if isinstance(model, SSY):
-        return "ssy", SSY_SUPPORTED, discretize_ssy, _ssy_tangent, SSY_PARAMS
-    if isinstance(model, GCY):
-        return "gcy", GCY_SUPPORTED, discretize_gcy, _gcy_tangent, GCY_PARAMS
-    raise TypeError(f"model must be an SSY or a GCY instance, not {type(model).__name__}")
-
-
-def _persistence_kind(model):
-    return (SSY_PERSISTENCE, _ssy_persistence) if isinstance(model, SSY) else (GCY_PERSISTENCE, _gcy_persistence)
-
-
-_ops = {}
-_OPS_MAX = 4
-
-
-def _operator(model, shapes):
-    """The device operator of (model, shapes), built once and reused; launches on torch's current stream so that
-    the torch work vectors and the library's kernels are ordered."""
-    import torch
-    kind, _, disc, _, _ = _kind(model)
-    key = (kind, tuple(int(s) for s in shapes), tuple(float(p) for p in model.params))
-    hit = _ops.get(key)
-    if hit is None:
-        if len(_ops) >= _OPS_MAX:
-            _ops.pop(next(iter(_ops)))
-        arr = disc(model, shapes)
-        hit = _ops[key] = (KoopmansOperator(kind, shapes, model.params, arr), arr)
-    op, arr = hit
-    op.set_stream(torch.cuda.current_stream(torch.device("cuda", op.device)).cuda_stream)
-    return op, arr
+_TANGENTS = {"ssy": (_ssy_tangent, _ssy_persistence), "gcy": (_gcy_tangent, _gcy_persistence)}
 
 
 def _directions(model, shapes, names, arr, persistence=False):
     """[(dparams, darrays, dgen)] of the named parameters; dgen is None for all but the persistences."""
-    kind, supported, _, tangent, allp = _kind(model)
-    pers, ptangent = _persistence_kind(model)
+    L = _kind(model)
+    tangent, ptangent = _TANGENTS[L.kind]
     out = []
     for nm in names:
-        if persistence and nm in pers:
+        if persistence and nm in L.persistence:
             out.append(ptangent(model, shapes, nm, arr))
         else:
-            _check(allp, supported, nm, "rouwenhorst", kind.upper())
+            _check(L.params, L.supported, nm, "rouwenhorst", L.kind.upper())
             out.append(tangent(model, shapes, nm, arr) + (None,))
     return out
-
-
-def _device_grid(op, x, what):
-    import torch
-    dev = torch.device("cuda", op.device)
-    if isinstance(x, torch.Tensor):
-        t = x.to(device=dev, dtype=torch.float64).contiguous()
-    else:
-        t = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64))).to(dev)
-    if tuple(t.shape) != op.shapes:
-        raise ValueError(f"{what} has shape {tuple(t.shape)}, the grid is {op.shapes}")
-    return t
 
 
 def wc_ratio_sensitivities(model, shapes, w_star, wrt=None, rtol=1e-10, atol=0.0, persistence=False):
@@ -354,13 +304,13 @@ def wc_ratio_sensitivities(model, shapes, w_star, wrt=None, rtol=1e-10, atol=0.0
     ``persistence=True`` admits the persistence parameters (``SSY_PERSISTENCE`` / ``GCY_PERSISTENCE``) in ``wrt``
     and makes the default every parameter of the model."""
     import torch
-    _, supported, _, _, allp = _kind(model)
-    pers = _persistence_kind(model)[0] if persistence else ()
-    default = allp if persistence else supported
+    L = _kind(model)
+    pers = L.persistence if persistence else ()
+    default = L.params if persistence else L.supported
     names = default if wrt is None else tuple([wrt] if isinstance(wrt, str) else wrt)
     for nm in names:                                               # (ValueError before any device work)
         if nm not in pers:
-            _check(allp, supported, nm, "rouwenhorst", type(model).__name__)
+            _check(L.params, L.supported, nm, "rouwenhorst", type(model).__name__)
     op, arr = _operator(model, shapes)
     dirs = _directions(model, shapes, names, arr, persistence)
     w = _device_grid(op, w_star, "w_star")
@@ -388,48 +338,34 @@ def wc_ratio_sensitivities_continuous(model, grids, w_star, wrt=None, *, rtol=1e
     wrt: Greek names of ``SSY_PARAMS`` / ``GCY_PARAMS`` (default: all of them).  operator: a ``ContinuousOperator`` on
     these parameters and grids, whose nodes and weights define the expectation; otherwise one is built with
     ``qnwnorm([d] * D)`` on ``device``.  Every ValueError / TypeError is raised before any device work."""
-    import math
     import torch
-    from .pricing import _cont_model_request, _cont_operator, _cont_sync
-    allp = _kind(model)[4]                                         # (TypeError for anything but an SSY or a GCY)
-    req = {}
-
-    def own(nd, shapes):
-        if wrt is None:
-            names = allp
-        elif isinstance(wrt, str):
-            names = (wrt,)
-        else:
-            try:
-                names = tuple(wrt)
-            except TypeError:
-                raise TypeError(f"wrt must be None, a parameter name or a sequence of names, got {wrt!r}") from None
-        for nm in names:
-            if nm not in allp:
-                raise ValueError(f"unknown {type(model).__name__} parameter {nm!r} (one of {', '.join(allp)})")
-        req["names"] = names
-        for what, v, lo_ok in (("rtol", rtol, False), ("atol", atol, True)):
-            try:
-                f = float(v)
-            except (TypeError, ValueError):
-                raise ValueError(f"{what} must be a number, got {v!r}") from None
-            if not math.isfinite(f) or f < 0.0 or (f == 0.0 and not lo_ok):
-                raise ValueError(f"{what} must be {'non-negative' if lo_ok else 'positive'} and finite, got {v!r}")
-            req[what] = f
-
-    _, grids, _, d = _cont_model_request(model, grids, w_star, operator, d, own,
-                                          why_w="a fixed point of T is 1 + β(…)^(1/θ) > 1; the tangent takes ln of its interpolant")
-    names = req["names"]
+    allp = _kind(model).params                                     # (TypeError for anything but an SSY or a GCY)
+    _, _, grids, shapes = _cont_grids(model, grids, w_star)
+    if wrt is None:
+        names = allp
+    elif isinstance(wrt, str):
+        names = (wrt,)
+    else:
+        try:
+            names = tuple(wrt)
+        except TypeError:
+            raise TypeError(f"wrt must be None, a parameter name or a sequence of names, got {wrt!r}") from None
+    for nm in names:
+        if nm not in allp:
+            raise ValueError(f"unknown {type(model).__name__} parameter {nm!r} (one of {', '.join(allp)})")
+    rtol, atol = _check_tolerance("rtol", rtol, False), _check_tolerance("atol", atol, True)
+    d = _cont_operator_or_d(model, grids, shapes, operator, d)
+    _check_w_star(w_star, "a fixed point of T is 1 + β(…)^(1/θ) > 1; the tangent takes ln of its interpolant")
     op = _cont_operator(model, grids, operator, d, device)
     w = _device_grid(op, w_star, "w_star")
     rhs, x = torch.empty_like(w), torch.empty_like(w)
-    _cont_sync(op)
+    _Fence(op).before_library()
     out, info = {}, {}
     for nm in names:
         dp = np.zeros(len(allp))
         dp[allp.index(nm)] = 1.0
         op.cont_param_tangent_dev(w.data_ptr(), dp, rhs.data_ptr())
-        info[nm] = op.solve_linear_dev(rhs.data_ptr(), x.data_ptr(), False, req["rtol"], req["atol"])   # (ends synchronised)
+        info[nm] = op.solve_linear_dev(rhs.data_ptr(), x.data_ptr(), False, rtol, atol)   # (ends synchronised)
         out[nm] = x.cpu().numpy()
     out["_info"] = info
     return out
@@ -440,8 +376,8 @@ def wc_ratio_gradient(model, shapes, w_star, g, rtol=1e-10, atol=0.0, persistenc
     lambda = (I - J(w*)^T)^{-1} g, then <lambda, dT/dp_k> per parameter (a tangent of T each, no further solve).
     ``persistence=True``: every parameter of the model, the persistences included."""
     import torch
-    _, supported, _, _, allp = _kind(model)
-    names = allp if persistence else supported
+    L = _kind(model)
+    names = L.params if persistence else L.supported
     op, arr = _operator(model, shapes)
     dirs = _directions(model, shapes, names, arr, persistence)
     w = _device_grid(op, w_star, "w_star")
@@ -458,9 +394,7 @@ def wc_ratio_gradient(model, shapes, w_star, g, rtol=1e-10, atol=0.0, persistenc
 
 
 # -- gradients from adjoint moments (the batch path: csrc/batch_adjoint.hpp) -------------------------------------------
-# (ip_beta, ip_gamma, ip_psi, ip_mu_c), (ia_hlam, ia_sigc, ia_z), (axis of h_lam, axis of h_c): the places `sens_tables`
-# of csrc/sdfs_api.hip reads
-_MOMENT_PLACES = {"ssy": ((0, 1, 2, 3), (0, 8, 6), (0, 1)), "gcy": ((0, 2, 1, 5), (13, 9, 0), (5, 3))}
+# (the places of the moment block: ``Layout.moments`` of _requests.py)
 
 
 def adjoint_moments_to_gradient(model, shapes, moments, persistence=True, method="rouwenhorst"):
@@ -476,9 +410,10 @@ def adjoint_moments_to_gradient(model, shapes, moments, persistence=True, method
     ``persistence=True``.  ValueError for a Tauchen grid."""
     if method != "rouwenhorst":
         raise ValueError(f"parameter tangents are implemented for Rouwenhorst grids only, not {method!r}")
-    kind, supported, disc, _, allp = _kind(model)
+    L = _kind(model)
+    kind, supported, disc, allp = L.kind, L.supported, L.discretize, L.params
     shapes = tuple(int(s) for s in shapes)
-    (ib, ig, ips, imu), (ia_hl, ia_sc, ia_z), (ax_l, ax_c) = _MOMENT_PLACES[kind]
+    (ib, ig, ips, imu), (ia_hl, ia_sc, ia_z), (ax_l, ax_c) = L.moments
     ndim = len(shapes)
     arr = disc(model, shapes)
     n_l, n_c, na3 = shapes[ax_l], shapes[ax_c], int(np.asarray(arr[ia_z]).size)
@@ -495,7 +430,7 @@ def adjoint_moments_to_gradient(model, shapes, moments, persistence=True, method
     θ = (1.0 - γ) / (1.0 - 1.0 / ψ)
     h_λ, σ_c, z = (np.asarray(arr[i], dtype=np.float64).ravel() for i in (ia_hl, ia_sc, ia_z))
     names = allp if persistence else supported
-    axis_of = _SSY_AXIS if kind == "ssy" else _GCY_AXIS
+    axis_of = L.persistence
     out = {}
     for nm, (dp, da, dgen) in zip(names, _directions(model, shapes, names, arr, persistence)):
         def d(i):

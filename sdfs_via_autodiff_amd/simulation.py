@@ -23,14 +23,15 @@ import math
 
 import numpy as np
 
-from .pricing import (_AXIS_Q, _shapes, _check_grid, _kappa, _count, _check_w_star, _cont_model_request, stationary_weights,
-                      claim_prices)
-from .sensitivity import _kind, _operator, _device_grid
+from ._requests import MAX_RETURNED  # noqa: F401  (path-steps of returned series; a name of this module)
+from ._requests import (LAYOUT, _kind, _shapes, _check_grid, _kappa, _count, _check_w_star, _path_request,
+                        _cont_grids, _cont_operator_or_d, _operator, _cont_operator, _device_grid, _Fence,
+                        stationary_weights)
+from .pricing import claim_prices
 
 SERIES = ("dc", "m", "rf", "rc", "xc", "wc")
 SERIES_KAPPA = SERIES + ("rd", "xd", "pd")
 STATS = ("mean", "std", "ac1")
-MAX_RETURNED = 1 << 25            # path-steps of returned series
 REC_BYTES = 64                    # per state
 
 
@@ -39,10 +40,10 @@ def cdf_tables(model, shapes, arrays=None):
     in fp64 with the last entry of every row set to 2.0.  ValueError (of ``stationary_weights``) when the chain does not
     factorise."""
     kind, shapes = _shapes(model, shapes)
-    arr = _kind(model)[2](model, shapes) if arrays is None else arrays
+    arr = LAYOUT[kind].discretize(model, shapes) if arrays is None else arrays
     pis = stationary_weights(model, shapes, arr)
     cdf, cdf0 = [], []
-    for qi, n, pi in zip(_AXIS_Q[kind], shapes, pis):
+    for qi, n, pi in zip(LAYOUT[kind].transitions, shapes, pis):
         Q = np.asarray(arr[qi], dtype=np.float64).reshape(-1, n, n)[0]
         c = np.cumsum(Q, axis=1)
         c[:, -1] = 2.0
@@ -86,40 +87,6 @@ def _result(names, st, P):
     return {"series": names, "per_path": per_path, "summary": summary, "pooled": pooled}
 
 
-def _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol, return_paths, members=1, check_kappa=None):
-    """The checked request of ``simulate`` (and of the batch's): (P, T, B, path_offset, seed, rtol, fixed start or None)."""
-    P = _count(n_paths, "n_paths", 1, 1 << 32)
-    T = _count(n_periods, "n_periods", 2, (1 << 32) - 1)
-    B = _count(burn_in, "burn_in", 0, (1 << 32) - 1)
-    off = _count(path_offset, "path_offset", 0, (1 << 32) - 1)
-    sd = _count(seed, "seed", 0, (1 << 64) - 1)
-    if off + P > 1 << 32:
-        raise ValueError(f"path_offset + n_paths = {off + P} > 2^32: path numbers are 32-bit")
-    if B + T >= 1 << 32:
-        raise ValueError(f"burn_in + n_periods = {B + T} >= 2^32: step numbers are 32-bit")
-    if check_kappa is not None:       # (where ``simulate`` has always checked its kappa: after the counts)
-        check_kappa()
-    rtol = float(rtol)
-    if not (rtol > 0.0 and math.isfinite(rtol)):
-        raise ValueError(f"rtol must be positive, got {rtol!r}")
-    if return_paths and members * P * T > MAX_RETURNED:
-        what = "n_paths * n_periods" if members == 1 else "members * n_paths * n_periods"
-        raise ValueError(f"return_paths: {what} = {members * P * T} > 2^25 path-steps")
-    if isinstance(start, str):
-        if start != "stationary":
-            raise ValueError(f"start must be 'stationary' or one state index per axis, got {start!r}")
-        fixed = None
-    else:
-        fixed = tuple(start)
-        if len(fixed) != len(shapes):
-            raise ValueError(f"start needs one state index per axis ({len(shapes)}), got {len(fixed)}")
-        for a, (s, n) in enumerate(zip(fixed, shapes)):
-            if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < n:
-                raise ValueError(f"start[{a}] = {s!r}: a state index of axis {a} lies in 0 ... {n - 1}")
-        fixed = tuple(int(s) for s in fixed)
-    return P, T, B, off, sd, rtol, fixed
-
-
 def simulate(model, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, path_offset=0, start="stationary",
              kappa=None, rtol=1e-10, return_paths=False):
     """Simulate ``n_paths`` paths (numbered path_offset … path_offset + n_paths − 1) of ``n_periods`` recorded steps
@@ -135,11 +102,11 @@ def simulate(model, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, pa
     import torch
     kind, shapes = _shapes(model, shapes)
     _check_grid(w_star, shapes, "w_star")
-    P, T, B, off, sd, rtol, fixed = _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol,
-                                             return_paths, check_kappa=lambda: kappa is None or _kappa(kappa))
+    P, T, B, off, sd, rtol, fixed = _path_request(shapes, n_paths, n_periods, burn_in, seed, path_offset, start, rtol,
+                                                  return_paths, check_kappa=lambda: kappa is None or _kappa(kappa))
     k = None if kappa is None else _kappa(kappa)
     _check_w_star(w_star)
-    arr = _kind(model)[2](model, shapes)
+    arr = _kind(model).discretize(model, shapes)
     cdf, cdf0 = cdf_tables(model, shapes, arr)          # (ValueError when the chain does not factorise)
     names = SERIES_KAPPA if k is not None else SERIES
     ns = len(names)
@@ -179,32 +146,19 @@ def simulate(model, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, pa
 CONT_REC_BYTES = 16               # per grid point: {w, −ln E_x[M]}
 
 
-def _cont_request(model, grids, w_star, n_paths, n_periods, burn_in, seed, path_offset, step_offset, start, operator, d,
-                  return_paths):
-    """The checked request of ``simulate_continuous``; raises before any device call."""
-    req = {}
-
-    def counts(nd, shapes):
-        P, T, B, off, sd, _, _ = _request(shapes, n_paths, n_periods, burn_in, seed, path_offset, "stationary", 1e-10,
-                                          return_paths)
-        s0 = _count(step_offset, "step_offset", 0, (1 << 32) - 1)
-        if s0 + B + T >= 1 << 32:
-            raise ValueError(f"step_offset + burn_in + n_periods = {s0 + B + T} >= 2^32: step numbers are 32-bit")
-        st = start
-        if st is not None:
-            try:
-                st = np.ascontiguousarray(np.asarray(st, dtype=np.float64))
-            except (TypeError, ValueError):
-                raise ValueError("start must be None, one state (D,) or one state per path (n_paths, D)") from None
-            if st.shape not in ((nd,), (P, nd)):
-                raise ValueError(f"start has shape {st.shape}: one state ({nd},) or one per path ({P}, {nd})")
-            if not np.all(np.isfinite(st)):
-                raise ValueError("start must be finite")
-        req.update(P=P, T=T, B=B, off=off, sd=sd, s0=s0, start=st)
-
-    kind, grids, shapes, d = _cont_model_request(model, grids, w_star, operator, d, counts)
-    P, T, B, off, sd, s0, start = (req[k] for k in ("P", "T", "B", "off", "sd", "s0", "start"))
-    return kind, grids, shapes, P, T, B, off, sd, s0, start, d
+def _cont_start(start, nd, P):
+    """The start of ``simulate_continuous``: None, or one state (nd,) or one per path (P, nd) as a float64 array."""
+    if start is None:
+        return None
+    try:
+        st = np.ascontiguousarray(np.asarray(start, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError("start must be None, one state (D,) or one state per path (n_paths, D)") from None
+    if st.shape not in ((nd,), (P, nd)):
+        raise ValueError(f"start has shape {st.shape}: one state ({nd},) or one per path ({P}, {nd})")
+    if not np.all(np.isfinite(st)):
+        raise ValueError("start must be finite")
+    return st
 
 
 def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, seed=0, path_offset=0, step_offset=0,
@@ -230,10 +184,15 @@ def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, 
     (tests/cont_sim_oracle.py is the numpy twin).  A path's result depends only on its number, the seed, step_offset,
     its start and the model.  DESIGN §4.14."""
     import torch
-    from .continuous import ContinuousOperator, qnwnorm
-    kind, grids, shapes, P, T, B, off, sd, s0, start, d = _cont_request(
-        model, grids, w_star, n_paths, n_periods, burn_in, seed, path_offset, step_offset, start, operator, d, return_paths)
-    nd = len(shapes)
+    _, nd, grids, shapes = _cont_grids(model, grids, w_star)
+    P, T, B, off, sd, _, _ = _path_request(shapes, n_paths, n_periods, burn_in, seed, path_offset, "stationary", 1e-10,
+                                           return_paths)
+    s0 = _count(step_offset, "step_offset", 0, (1 << 32) - 1)
+    if s0 + B + T >= 1 << 32:
+        raise ValueError(f"step_offset + burn_in + n_periods = {s0 + B + T} >= 2^32: step numbers are 32-bit")
+    start = _cont_start(start, nd, P)
+    d = _cont_operator_or_d(model, grids, shapes, operator, d)
+    _check_w_star(w_star)
     ns = len(SERIES)
     N = int(np.prod(shapes))
     need = N * (CONT_REC_BYTES + 16) + (3 * ns + 1) * P * 8 + P * 4 + 2 * P * nd * 8
@@ -245,10 +204,7 @@ def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, 
     if need > free:
         raise ValueError(f"the per-point records and outputs need {need / 2**30:.2f} GiB, {free / 2**30:.2f} GiB of "
                          "device memory is free")
-    op = operator
-    if op is None:
-        nodes, weights = qnwnorm([d] * nd)
-        op = ContinuousOperator(np.array(model.params), grids, np.ascontiguousarray(nodes.T), weights, device=devno)
+    op = _cont_operator(model, grids, operator, d, devno)
     w = _device_grid(op, w_star, "w_star")
     em = torch.empty_like(w)
     rec = torch.empty((N, 2), dtype=torch.float64, device=dev)
@@ -261,7 +217,7 @@ def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, 
     if return_paths:
         states = torch.empty((P, T + 1, nd), dtype=torch.float64, device=dev)
         ser = torch.empty((ns, P, T), dtype=torch.float64, device=dev)
-    torch.cuda.current_stream(dev).synchronize()           # (the library runs on the operator's own stream)
+    _Fence(op).before_library()
     op.cont_sdf_mean_dev(w.data_ptr(), em.data_ptr())
     op.cont_sim_records_dev(w.data_ptr(), em.data_ptr(), rec.data_ptr())
     op.cont_sim_paths_dev(rec.data_ptr(), sd, off, P, B, T, stats.data_ptr(), clamped.data_ptr(), final.data_ptr(),

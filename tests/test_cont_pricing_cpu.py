@@ -135,12 +135,13 @@ def request_case():
 def no_device(monkeypatch):
     """Any attempt to open the device fails the test."""
     import torch
-    from sdfs_via_autodiff_amd import pricing
+    from sdfs_via_autodiff_amd import _requests, pricing
 
     def boom(*a, **k):
         raise AssertionError("a bad request reached the device")
     monkeypatch.setattr(torch.cuda, "current_stream", boom)
-    monkeypatch.setattr(pricing, "_device_grid", boom)
+    for module in (_requests, pricing):             # (where it lives, and the name the pricing functions call)
+        monkeypatch.setattr(module, "_device_grid", boom)
     monkeypatch.setattr(S.ContinuousOperator, "__init__", boom)
 
 
@@ -223,6 +224,8 @@ def test_claim_prices_request_errors_raise_before_any_device_call(monkeypatch, r
 
 
 def test_simulate_continuous_shares_the_request_checks():
-    """One helper serves both callers (the errors of ``simulate_continuous`` themselves: tests/test_cont_simulation_cpu.py)."""
-    from sdfs_via_autodiff_amd import pricing, simulation
-    assert simulation._cont_model_request is pricing._cont_model_request
+    """The same request steps serve both callers (the errors of ``simulate_continuous`` themselves:
+    tests/test_cont_simulation_cpu.py)."""
+    from sdfs_via_autodiff_amd import _requests, pricing, simulation
+    for step in ("_cont_grids", "_cont_operator_or_d", "_check_w_star"):
+        assert getattr(simulation, step) is getattr(pricing, step) is getattr(_requests, step)

@@ -225,8 +225,8 @@ def test_jvp_equals_consumption_tilt_bitwise(S, kind, shapes, plan, marker, c_or
 def fixed_point(S, kind, shapes, m):
     """A tight Newton fixed point, computed on the operator pricing.py will use."""
     import torch
-    from sdfs_via_autodiff_amd import sensitivity as sens
-    op, _ = sens._operator(m, shapes)
+    from sdfs_via_autodiff_amd import _requests
+    op, _ = _requests._operator(m, shapes)
     w = torch.full(shapes, 800.0, dtype=torch.float64, device="cuda")
     _, info = op.solve_dev(w.data_ptr(), "newton", tol=1e-10, inner_rtol=1e-12, inner_atol=0.0)
     assert info["status"] == 0, info
@@ -337,8 +337,8 @@ def test_claim_prices_vs_dense_and_euler_equation(S):
     np.testing.assert_allclose(out["pd"].reshape(-1), v, rtol=1e-8)
     np.testing.assert_allclose(out["expected_return"].reshape(-1), er, rtol=1e-8)
     # Euler: K (1 + v) / v = 1 with the device's own K
-    from sdfs_via_autodiff_amd import sensitivity as sens
-    op, _ = sens._operator(m, shapes)
+    from sdfs_via_autodiff_amd import _requests
+    op, _ = _requests._operator(m, shapes)
     wd, vd = dev(w), dev(out["pd"])
     num, res = torch.add(vd, 1.0), torch.empty_like(vd)
     op.set_tilt_dev(wd.data_ptr(), 1, m.θ, kappa - m.γ)
@@ -456,8 +456,9 @@ def test_refusals(S):
     grids = S.build_grid(ssy, 3, 3, 3, 4)
     nodes, weights = S.qnwnorm([3] * 4)
     Tc = S.T_fun_factory((np.array(ssy.params), grids, nodes.T.copy(), weights), "quadrature", 3 * 3 * 3 * 4)
-    with pytest.raises(S.SdfsError, match="unsharded discretised"):
-        Tc.set_tilt_dev(None, 0, 0.0, 1.0)
+    # (``ContinuousOperator.set_tilt_dev`` is the tilt of the continuous-state model; the discrete entry point refuses its handle)
+    assert _lib.lib.sdfs_set_tilt_dev(Tc.handle, None, 0, 0.0, 1.0) == _lib.SDFS_ERR_UNSUPPORTED
+    assert "unsharded discretised" in _lib.last_error(Tc.handle)
     # sharded (one rank owning every index of its two axes)
     nd = len(shapes)
     arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in arr]

@@ -63,11 +63,11 @@ def fixed_point(S, kind, shapes, m=None, tag=None):
     """A tight Newton fixed point on the operator simulation.py uses (cached per grid; m, tag: another model than the
     default and its name in the cache)."""
     import torch
-    from sdfs_via_autodiff_amd import sensitivity as sens
+    from sdfs_via_autodiff_amd import _requests
     key = (kind, tuple(shapes)) if m is None else (kind, tuple(shapes), tag)
     if key not in _W:
         m = m or model_of(S, kind)
-        op, _ = sens._operator(m, shapes)
+        op, _ = _requests._operator(m, shapes)
         w = torch.full(shapes, 800.0, dtype=torch.float64, device="cuda")
         _, info = op.solve_dev(w.data_ptr(), "newton", tol=1e-10, inner_rtol=1e-12, inner_atol=0.0)
         assert info["status"] == 0, info
@@ -165,7 +165,7 @@ def test_every_lookahead_and_search_matches_the_twin(S, kind, shapes, n_periods,
     bit at the parent commit too).  The default form, which stores, gives the indices (exact) and series (1e-12) of
     these run lengths."""
     import torch
-    from sdfs_via_autodiff_amd import sensitivity as sens
+    from sdfs_via_autodiff_amd import _requests
     from sdfs_via_autodiff_amd.simulation import cdf_tables
     m = model_of(S, kind)
     w = fixed_point(S, kind, shapes)
@@ -175,7 +175,7 @@ def test_every_lookahead_and_search_matches_the_twin(S, kind, shapes, n_periods,
     assert np.array_equal(out["paths"]["index"], idx)
     for nm in out["series"]:
         assert close(out["paths"][nm], ser[nm], 1.0) <= 1e-12, nm
-    op, _ = sens._operator(m, shapes)
+    op, _ = _requests._operator(m, shapes)
     dev = torch.device("cuda", 0)
     wd = torch.from_numpy(w).to(dev)
     vd = torch.from_numpy(S.claim_prices(m, shapes, w, kappa)["pd"]).to(dev) if kappa is not None else None

@@ -41,6 +41,7 @@ def main(names, quick):
     import torch
     import sdfs_via_autodiff_amd as S
     from sdfs_via_autodiff_amd import sensitivity as sens
+    from sdfs_via_autodiff_amd import _requests
     dev = torch.device("cuda", 0)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     B = 64 if quick else 256
@@ -63,7 +64,7 @@ def main(names, quick):
         mom = torch.empty((B, op.adjoint_words()), dtype=torch.float64, device=dev)
         wh, gh = wstar.cpu().numpy(), g.cpu().numpy()
         torch.cuda.synchronize()
-        sens._OPS_MAX = max(sens._OPS_MAX, nloop)          # the loop's operator cache holds every member: no handle is built in the timed region
+        _requests._OPS_MAX = max(_requests._OPS_MAX, nloop)          # the loop's operator cache holds every member: no handle is built in the timed region
 
         def gradient_route():
             torch.cuda.synchronize()

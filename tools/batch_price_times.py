@@ -44,7 +44,7 @@ def med(ts):
 def main(names, quick, out_path):
     import torch
     import sdfs_via_autodiff_amd as S
-    from sdfs_via_autodiff_amd import sensitivity as sens
+    from sdfs_via_autodiff_amd import _requests
     lines = []
 
     def say(text=""):
@@ -75,7 +75,7 @@ def main(names, quick, out_path):
         kap, kts = np.full(B, KAPPA), np.zeros(B)
         gax = op._stationary_weights()
         torch.cuda.synchronize()
-        sens._OPS_MAX = max(sens._OPS_MAX, nloop)          # the loop's operator cache holds every member: no handle is built in the timed region
+        _requests._OPS_MAX = max(_requests._OPS_MAX, nloop)          # the loop's operator cache holds every member: no handle is built in the timed region
 
         def price_route(n_max):
             torch.cuda.synchronize()

@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import sdfs_via_autodiff_amd as S                                   # noqa: E402
-from sdfs_via_autodiff_amd import sensitivity as sens             # noqa: E402
+from sdfs_via_autodiff_amd import _requests  # noqa: E402
 from sdfs_via_autodiff_amd.simulation import cdf_tables           # noqa: E402
 
 GRIDS = {"ssy": ("ssy", (10, 10, 10, 20)), "gcy": ("gcy", (10, 10, 10, 10, 20, 20))}
@@ -116,7 +116,7 @@ def main(names, P, T, quick):
     # context: the discretised simulator, and the twin on the host
     shapes = (15,) * 4
     m = S.SSY()
-    op, _ = sens._operator(m, shapes)
+    op, _ = _requests._operator(m, shapes)
     w = torch.full(shapes, 800.0, dtype=torch.float64, device=dev)
     op.solve_dev(w.data_ptr(), "newton", tol=1e-10, inner_rtol=1e-12, inner_atol=0.0)
     rec = torch.empty((op.size, 8), dtype=torch.float64, device=dev)

@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sdfs_via_autodiff_amd as S                       # noqa: E402
-from sdfs_via_autodiff_amd import sensitivity as sens  # noqa: E402
+from sdfs_via_autodiff_amd import _requests  # noqa: E402
 
 
 def timed(fn, reps):
@@ -33,7 +33,7 @@ def main(extents):
     for n in extents:
         shapes = (n,) * 6
         m = S.GCY()
-        op, _ = sens._operator(m, shapes)
+        op, _ = _requests._operator(m, shapes)
         N = op.size
         w = torch.full(shapes, 800.0, dtype=torch.float64, device=dev)
         op.solve_dev(w.data_ptr(), "newton", tol=1e-10, inner_rtol=1e-12, inner_atol=0.0)
@@ -89,7 +89,7 @@ def main(extents):
                 print(f"  {k['name']:<22s} {1e3 * t:8.1f} us  {gbs:6.0f} GB/s = {gbs / copy_gbs:.2f} of the copy rate")
         op.set_profiling(False)
         del a, one, out, x, jv, w
-        sens._ops.clear()
+        _requests._ops.clear()
         torch.cuda.empty_cache()
 
 

@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import sdfs_via_autodiff_amd as S                                   # noqa: E402
-from sdfs_via_autodiff_amd import sensitivity as sens             # noqa: E402
+from sdfs_via_autodiff_amd import _requests  # noqa: E402
 from sdfs_via_autodiff_amd.simulation import cdf_tables           # noqa: E402
 
 GRIDS = {"ssy15": ("ssy", (15,) * 4), "gcy16": ("gcy", (16,) * 6), "gcy20": ("gcy", (20,) * 6)}
@@ -53,7 +53,7 @@ def main(names, P, T, quick):
     for nm in names:
         kind, shapes = GRIDS[nm]
         m = S.SSY() if kind == "ssy" else S.GCY()
-        op, _ = sens._operator(m, shapes)
+        op, _ = _requests._operator(m, shapes)
         N = op.size
         w = torch.full(shapes, 800.0, dtype=torch.float64, device=dev)
         op.solve_dev(w.data_ptr(), "newton", tol=1e-10, inner_rtol=1e-12, inner_atol=0.0)
@@ -74,7 +74,7 @@ def main(names, P, T, quick):
             torch.cuda.synchronize()
             op.set_profiling(False)
             del rec, stats, v, w
-            sens._ops.clear()
+            _requests._ops.clear()
             torch.cuda.empty_cache()
             continue
         a = torch.empty_like(w)
@@ -103,7 +103,7 @@ def main(names, P, T, quick):
                       f"{steps / (t * 1e-3) / 1e9:6.2f} G path-steps/s")
         op.set_profiling(False)
         del a, rec, stats, v, w
-        sens._ops.clear()
+        _requests._ops.clear()
         torch.cuda.empty_cache()
     if not quick:
         import sim_oracle as so
