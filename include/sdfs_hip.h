@@ -358,6 +358,35 @@ int sdfs_cont_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* s
  * SDFS_ERR_ARG: NULL w / dparams / out, a non-finite direction, or w, out, Tw not pairwise distinct. */
 int sdfs_cont_param_tangent_dev(sdfs_handle* h, const double* w_dev, const double* dparams, double* out_dev, double* Tw_dev);
 
+/* The transposed Jacobian of the continuous-state operator and the adjoint solve on it (handles of
+ * sdfs_create_continuous only, else SDFS_ERR_UNSUPPORTED; fp64).
+ *
+ *   out[j] = sum_x c2(x) u(x) sum_m W_m g_m(x)^(theta-1) phi_j(x'(x, m))   (- u[j] with minus_identity),
+ *
+ * at the cached linearisation (sdfs_linearize_dev or sdfs_cont_param_tangent_dev; left untouched), phi_j the multilinear
+ * hat weight of grid point j at the clamped next state: the cells and weights sdfs_apply_jvp_dev reads with, so out is the
+ * exact transpose of what that call computes: <u, J v> = <J^T u, v> to rounding.  A gather through an interpolant
+ * transposes into a scatter: one launch on the gather path T takes, out zeroed in-stream ahead of it, every
+ * contribution added with a hardware fp64 atomic add (LDS accumulators per grid point, then global memory); u is
+ * subtracted in one pass behind it, so out with minus_identity is one rounding away from out without.
+ *
+ * RESULTS ARE REPRODUCIBLE TO ROUNDING ONLY.  The last bits of out depend on the order in which the atomic adds arrive;
+ * two runs on the same input differ by a few units of rounding of the sum of the magnitudes.  These are the library's
+ * only entry points without bit-for-bit repeatability (every other reduction is finished in a fixed order), which is why
+ * they carry names of their own: sdfs_apply_vjp / sdfs_apply_vjp_dev / sdfs_solve_linear_dev(transpose != 0) keep
+ * returning SDFS_ERR_UNSUPPORTED on a continuous handle.
+ *
+ * out_dev must be ORDINARY device memory (hipMalloc; not fine-grained, host-pinned or managed memory: hardware
+ * floating-point atomics are not defined there).  SDFS_ERR_ARG: NULL u / out, u == out, or no linearisation yet. */
+int sdfs_cont_apply_vjp_dev(sdfs_handle* h, const double* u_dev, double* out_dev, int minus_identity);
+/* x = (I - J^T)^{-1} rhs at the cached linearisation by the device BiCGSTAB on the product above: the adjoint
+ * lambda = (I - J(w*)^T)^{-1} g of d<g, w*>/dp_k = <lambda, dT/dp_k> (sdfs_cont_param_tangent_dev), one solve for all
+ * parameters.  Stopping rule, opts, n_iter, final_rel_resid and SDFS_ERR_NUMERIC as sdfs_solve_linear_dev (fp64 only:
+ * opts.krylov_f32 != 0 is SDFS_ERR_ARG).  Reproducible to rounding only, as the product is; iteration counts may differ by
+ * one between runs where a residual sits on the tolerance.  SDFS_ERR_ARG: NULL rhs / x, or no linearisation yet. */
+int sdfs_cont_solve_adjoint_dev(sdfs_handle* h, const sdfs_opts* opts, const double* rhs_dev, double* x_dev, int64_t* n_iter,
+                                double* final_rel_resid);
+
 /* max|T(w) - w| of the most recent apply that computed it. */
 int sdfs_residual(sdfs_handle* h, double* sup_norm);
 

@@ -27,7 +27,8 @@ from .single_index import (DenseOperator, compute_H_single_index, discretize_sin
 from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_ratio_sensitivities,
                           wc_ratio_gradient, rouwenhorst_generator, discretize_ssy_persistence_tangent,
                           discretize_gcy_persistence_tangent, SSY_PERSISTENCE, GCY_PERSISTENCE,
-                          adjoint_moments_to_gradient, wc_ratio_sensitivities_continuous, SSY_PARAMS, GCY_PARAMS)
+                          adjoint_moments_to_gradient, wc_ratio_sensitivities_continuous, wc_ratio_gradient_continuous,
+                          SSY_PARAMS, GCY_PARAMS)
 from .pricing import (stationary_weights, sdf_moments, term_structure, claim_prices, sdf_moments_continuous,
                       term_structure_continuous, claim_prices_continuous)
 from .simulation import simulate, simulate_continuous
@@ -49,7 +50,7 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "discretize_ssy_tangent", "discretize_gcy_tangent", "wc_ratio_sensitivities", "wc_ratio_gradient",
            "rouwenhorst_generator", "discretize_ssy_persistence_tangent", "discretize_gcy_persistence_tangent",
            "SSY_PERSISTENCE", "GCY_PERSISTENCE", "adjoint_moments_to_gradient",
-           "wc_ratio_sensitivities_continuous", "SSY_PARAMS", "GCY_PARAMS",
+           "wc_ratio_sensitivities_continuous", "wc_ratio_gradient_continuous", "SSY_PARAMS", "GCY_PARAMS",
            "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate", "simulate_continuous",
            "sdf_moments_continuous", "term_structure_continuous", "claim_prices_continuous",
            "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes", "BatchGradient", "gradient_batch", "BatchPrices", "price_batch", "price_words_to_stats",

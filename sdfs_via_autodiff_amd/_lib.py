@@ -116,6 +116,8 @@ SYMBOLS = {
     "sdfs_cont_tilted_horizons_dev": (C.c_int, [_P, C.c_int64, _D, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_P),
                                                 _D, _D]),
     "sdfs_cont_param_tangent_dev": (C.c_int, [_P, _P, _D, _P, _P]),
+    "sdfs_cont_apply_vjp_dev": (C.c_int, [_P, _P, _P, C.c_int]),
+    "sdfs_cont_solve_adjoint_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _P, _I64, _D]),
     "sdfs_residual": (C.c_int, [_P, _D]),
     "sdfs_solve": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _I64, _I64, _D]),
     "sdfs_solve_dev": (C.c_int, [_P, C.c_int, C.POINTER(sdfs_opts), _P, _I64, _I64, _D]),

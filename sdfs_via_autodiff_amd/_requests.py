@@ -256,6 +256,40 @@ def _cont_operator_or_d(model, grids, shapes, operator, d):
     return d
 
 
+def _cont_wrt(model, wrt):
+    """The parameter names a continuous-state derivative is asked for: None -> all 13 / 18 (every parameter is admitted,
+    the persistences included), a name, or a sequence of names.  Returns (names, all parameter names)."""
+    allp = _kind(model).params                             # (TypeError for anything but an SSY or a GCY)
+    if wrt is None:
+        names = allp
+    elif isinstance(wrt, str):
+        names = (wrt,)
+    else:
+        try:
+            names = tuple(wrt)
+        except TypeError:
+            raise TypeError(f"wrt must be None, a parameter name or a sequence of names, got {wrt!r}") from None
+    for nm in names:
+        if nm not in allp:
+            raise ValueError(f"unknown {type(model).__name__} parameter {nm!r} (one of {', '.join(allp)})")
+    return names, allp
+
+
+def _check_finite_grid(x, shapes, what):
+    """x lives on the grid and is finite everywhere."""
+    import torch
+    _check_grid(x, shapes, what)
+    if isinstance(x, torch.Tensor):
+        ok = bool(torch.all(torch.isfinite(x)))
+    else:
+        try:
+            ok = bool(np.all(np.isfinite(np.asarray(x, dtype=np.float64))))
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be an array of real numbers") from None
+    if not ok:
+        raise ValueError(f"{what} must be finite at every grid point")
+
+
 # -- device-side helpers -------------------------------------------------------------------------------------------------
 _ops = {}
 _OPS_MAX = 4

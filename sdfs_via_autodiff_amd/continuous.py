@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 from ._lib import lib, check
 from .models import SSY, GCY
-from .operators import KoopmansOperator, _as_f64, _save_list
+from .operators import KoopmansOperator, _as_f64, _inner_opts, _save_list
 from .solvers import solver
 
 
@@ -235,6 +235,38 @@ class ContinuousOperator(KoopmansOperator):
         self.cont_param_tangent_dev(wd.data_ptr(), dparams, out.data_ptr())
         self.synchronize()
         return out.cpu().numpy()
+
+    # -- transposed Jacobian and adjoint solve (sensitivity.wc_ratio_gradient_continuous) ----------------
+    # These are the library's only calls whose last bits depend on the arrival order of atomic adds: two runs on the same
+    # input agree to rounding, not bit for bit.  ``vjp_dev`` / ``vjp`` / ``solve_linear_dev(transpose=True)`` of the base
+    # class keep refusing a continuous operator.
+    def cont_vjp_dev(self, u_ptr, out_ptr, minus_identity=False):
+        """out = J(w)ᵀ u (− u with minus_identity) at the cached linearisation, on device pointers, two distinct grids
+        (sdfs_cont_apply_vjp_dev): the exact transpose of what ``jvp_dev`` computes.  ``out_ptr`` must be ordinary device
+        memory (``torch.empty(..., device="cuda")`` is).  Accumulated with hardware fp64 atomic adds, so the result is
+        reproducible to rounding only, not bit for bit.  The cached linearisation is left as it is."""
+        check(lib.sdfs_cont_apply_vjp_dev(self._h, u_ptr, out_ptr, int(minus_identity)), self._h)
+
+    def cont_vjp(self, w, u):
+        """J(w)ᵀ u with host ndarrays in and out: linearises at w, then ``cont_vjp_dev`` (reproducible to rounding
+        only)."""
+        import torch
+        wd, ud = self._to_dev(self._host_in(w), self._host_in(u, "u"))
+        out = torch.empty_like(wd)
+        self.linearize_dev(wd.data_ptr())
+        self.cont_vjp_dev(ud.data_ptr(), out.data_ptr())
+        self.synchronize()
+        return out.cpu().numpy()
+
+    def cont_solve_adjoint_dev(self, rhs_ptr, x_ptr, rtol=1e-10, atol=0.0, max_iter=0):
+        """x = (I − J(w)ᵀ)⁻¹ rhs at the cached linearisation by the device BiCGSTAB on ``cont_vjp_dev``
+        (sdfs_cont_solve_adjoint_dev; the stopping rule of ``solve_linear_dev``).  Returns (iterations, final relative
+        residual); ``SdfsError`` on a breakdown or a stop above max(rtol |rhs|₂, atol).  Reproducible to rounding only:
+        the iterates inherit the arrival order of the product's atomic adds."""
+        it, rel = C.c_int64(), C.c_double()
+        check(lib.sdfs_cont_solve_adjoint_dev(self._h, C.byref(_inner_opts(rtol, atol, max_iter)), rhs_ptr, x_ptr,
+                                              C.byref(it), C.byref(rel)), self._h)
+        return it.value, rel.value
 
 
 def T_fun_factory(params, method="quadrature", batch_size=10000, device=0):

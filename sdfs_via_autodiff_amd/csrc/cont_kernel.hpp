@@ -100,7 +100,22 @@ struct ContIO {
 // same expressions on the same e: the same bits) and, if asked, T w.
 // C_PTANL: C_PTAN with ln g_m taken from the power (pow_log_n below: ln 2 times the log2 g that g^theta forms anyway)
 // instead of libm's log: 0.85 - 0.92 of C_PTAN's time (profiles/continuous_sensitivity_times.txt), the host's default.
-enum ContMode { C_T = 0, C_TLIN = 1, C_JVP = 2, C_EM = 3, C_K0 = 4, C_K1 = 5, C_K2 = 6, C_PTAN = 7, C_PTANL = 8 };
+//
+// C_VJP: the transpose of C_JVP at the same linearisation.  io.v = u, io.c2_in = c2, io.w = the linearisation
+// point; io.out already holds 0, written in-stream ahead of the launch (cont_vjp.hip, which also subtracts u behind it
+// for minus_identity), and the block of x adds
+//   out[j] += c2(x) u(x) sum_m W_m g_m(x)^(theta-1) phi_j(x'(x, m)),
+// phi_j the multilinear hat weight of corner j: the cell and the t of the forward fold, the staged path's correction of
+// t included, so this is the transpose of what C_JVP computes and not of an idealised operator.  Same prologue, box,
+// node loop and power as C_JVP; the second array of each LDS pair (box, U) is a zeroed accumulator where C_JVP stages
+// its direction.  Pre-contracted path: the node's coefficient is spread over the 2^(D-2) outer corners of the adjoint of
+// U; after a barrier the transposed inner-pair contraction carries it into the accumulator box (four cells per entry,
+// the forward tt weights); after another the box cells that received something are added to out.  Staged path: the 2^D
+// corner weights go to the accumulator box, flushed the same way.  Global path: they go to out directly.
+// Every accumulation is a hardware fp64 atomic add (ds_add_f64 / global_atomic_add_f64): THE LAST BITS OF THE RESULT
+// DEPEND ON THE ORDER IN WHICH THE ADDS ARRIVE -- the one form of this kernel, and the first call of the library, that
+// is reproducible to rounding only.  io.out must be ordinary (coarse-grained) device memory.
+enum ContMode { C_T = 0, C_TLIN = 1, C_JVP = 2, C_EM = 3, C_K0 = 4, C_K1 = 5, C_K2 = 6, C_PTAN = 7, C_PTANL = 8, C_VJP = 9 };
 
 // modes that stage and interpolate a second field (io.v) beside io.w
 constexpr bool cont_two_fields(int mode) { return mode == C_JVP || mode == C_K1 || mode == C_K2; }
@@ -118,6 +133,23 @@ template <> struct ContTanSel<C_PTAN> { using type = ContTan; };
 template <> struct ContTanSel<C_PTANL> { using type = ContTan; };
 constexpr bool cont_ptan(int mode) { return mode == C_PTAN || mode == C_PTANL; }
 template <int MODE> using ContTanOf = typename ContTanSel<MODE>::type;
+
+// The transpose of InterpRec: coef times the hat weight of every corner, added to f with hardware fp64 atomics.  The
+// weights are those of InterpRec's fold, fma(t, v1 - v0, v0) = (1 - t) v0 + t v1; corners of weight zero (a clamped
+// coordinate: t = 0 or 1) are skipped.
+template <int D, int d, typename Idx>
+struct ScatterRec {
+  static __device__ __forceinline__ void run(double* __restrict__ f, Idx off, const Idx (&step)[D], const double (&t)[D], double coef) {
+    ScatterRec<D, d + 1, Idx>::run(f, off, step, t, coef * (1.0 - t[d]));
+    ScatterRec<D, d + 1, Idx>::run(f, off + step[d], step, t, coef * t[d]);
+  }
+};
+template <int D, typename Idx>
+struct ScatterRec<D, D, Idx> {
+  static __device__ __forceinline__ void run(double* __restrict__ f, Idx off, const Idx (&)[D], const double (&)[D], double coef) {
+    if (coef != 0.0) unsafeAtomicAdd(f + off, coef);
+  }
+};
 
 template <int D, int d, typename Idx>
 struct InterpRec {
@@ -242,6 +274,8 @@ template <int D, int MODE>
 __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContIO io, const ContTanOf<MODE> tan) {
   constexpr bool TWO = cont_two_fields(MODE);
   constexpr bool PTAN = cont_ptan(MODE);
+  constexpr bool VJP = MODE == C_VJP;
+  constexpr int NBOX = (TWO || VJP) ? 2 : 1;     // arrays of each LDS pair: C_VJP's second one is the accumulator
   __shared__ double red[PTAN ? 8 : 4];
   if (io.gate != nullptr) {
     const unsigned long long g = *io.gate;
@@ -322,6 +356,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
       }
       box[e] = io.w[go];
       if (TWO) box[P.cap + e] = io.v[go];
+      if constexpr (VJP) box[P.cap + e] = 0.0;
     }
     __syncthreads();
   }
@@ -332,7 +367,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
   const int inner_v = bext[D - 1] * bext[D - 2];
   const int Vo = staged ? V / inner_v : 0;
   const bool tensor = staged && tq > 0 && (long long)Vo * tq2 <= (long long)P.ucap;
-  double* const Uw = box + (TWO ? 2 : 1) * P.cap;
+  double* const Uw = box + NBOX * P.cap;
   double* const Uv = Uw + P.ucap;
   int lsU[DO > 0 ? DO : 1];
   if (tensor) {
@@ -361,6 +396,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
         const double v1 = fma(tt[1], box[base + ls[D - 2] + 1] - box[base + ls[D - 2]], box[base + ls[D - 2]]);
         Uw[e] = fma(tt[0], v1 - v0, v0);
       }
+      if constexpr (VJP) Uv[e] = 0.0;
       if (TWO) {
         const double* bv = box + P.cap;
         const double v0 = fma(tt[1], bv[base + 1] - bv[base], bv[base]);
@@ -378,6 +414,8 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
   }
 
   const PowLane PT = pow_lane_init(lane);
+  [[maybe_unused]] double cu = 0.0;              // C_VJP: c2(x) u(x)
+  if constexpr (VJP) cu = io.c2_in[p] * io.v[p];
   double acc = 0.0;
   [[maybe_unused]] double accl = 0.0;            // (accl: C_PTAN's sum of omega * [...])
   const int trips = (P.M + 255) >> 8;            // uniform: pow_fast_n needs whole waves
@@ -386,6 +424,8 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
     const bool valid = m < P.M;
     double g[1] = {1.0}, iv = 0.0, wq = 0.0;
     [[maybe_unused]] double gd = 0.0, eta0 = 0.0;   // C_PTAN: the tangent of g, the node of dimension 0
+    [[maybe_unused]] double vt[VJP ? D : 1];        // C_VJP: the t's and the cell of the fold, kept for the scatter
+    [[maybe_unused]] long long voff = 0;
     if (valid && tensor) {
       // digits of m in base tq: j_0 fastest; the inner pair selects the column of U
       int r = m, off = 0;
@@ -410,6 +450,11 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
       if constexpr (PTAN) DualRec<DO, 0, int, true>::run(Uw, Uv, off, lsU, to, tod, g[0], gd);
       else g[0] = InterpRec<DO, 0, int>::run(Uw, off, lsU, to);
       if (TWO) iv = InterpRec<DO, 0, int>::run(Uv, off, lsU, to);
+      if constexpr (VJP) {
+        voff = off;
+#pragma unroll
+        for (int d = 0; d < DO; ++d) vt[d] = to[d];
+      }
       wq = P.wq[m];
     } else if (valid) {
       double c[D], t[D];
@@ -435,6 +480,7 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
         if constexpr (PTAN) DualRec<D, 0, int, false>::run(box, nullptr, off, ls, t, td, g[0], gd);
         else g[0] = InterpRec<D, 0, int>::run(box, off, ls, t);
         if (TWO) iv = InterpRec<D, 0, int>::run(box + P.cap, off, ls, t);
+        if constexpr (VJP) voff = off;
       } else {
         long long off = 0;
 #pragma unroll
@@ -442,6 +488,11 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
         if constexpr (PTAN) DualRec<D, 0, long long, false>::run(io.w, nullptr, off, gs, t, td, g[0], gd);
         else g[0] = InterpRec<D, 0, long long>::run(io.w, off, gs, t);
         if (TWO) iv = InterpRec<D, 0, long long>::run(io.v, off, gs, t);
+        if constexpr (VJP) voff = off;
+      }
+      if constexpr (VJP) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) vt[d] = t[d];
       }
       wq = P.wq[m];
     }
@@ -454,6 +505,23 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
     if constexpr (MODE == C_PTANL) pow_log_n<1>(g, P.theta, PT, pw, lg);
     else pow_fast_n<true, 1>(g, MODE == C_K2 ? 2.0 * (P.theta - 1.0) : (MODE == C_EM || MODE == C_K1 ? P.theta - 1.0 : P.theta), PT, pw);
     if constexpr (MODE == C_PTAN) lg[0] = log(g[0]);
+    if constexpr (VJP) {
+      // c2 u W g^(theta-1) onto the corners the forward fold read, with its weights
+      if (valid) {
+        const double coef = cu * (wq * (pw[0] / g[0]));
+        if (tensor) {
+          double to[DO > 0 ? DO : 1];
+#pragma unroll
+          for (int d = 0; d < DO; ++d) to[d] = vt[d];
+          ScatterRec<DO, 0, int>::run(Uv, (int)voff, lsU, to, coef);
+        } else if (staged) {
+          ScatterRec<D, 0, int>::run(box + P.cap, (int)voff, ls, vt, coef);
+        } else {
+          ScatterRec<D, 0, long long>::run(io.out, voff, gs, vt, coef);
+        }
+      }
+      continue;
+    }
     if (MODE == C_JVP) acc = fma(wq * (pw[0] / g[0]), iv, acc);      // W g^(theta-1) interp(v)
     else if (MODE == C_K1 || MODE == C_K2) acc = fma(wq * pw[0], iv, acc);   // Wt g^(p (theta-1)) interp(f)
     else acc = fma(wq, pw[0], acc);
@@ -462,6 +530,55 @@ __global__ void __launch_bounds__(256) cont_kernel(const ContDesc P, const ContI
       const double L = fma(tan.theta, fma(P.sconst[0], eta0, lg[0]), P.theta * fma(tan.sconst[0], eta0, gd / g[0]));
       accl = fma(wq * pw[0], L, accl);
     }
+  }
+  if constexpr (VJP) {
+    if (!staged) return;                         // (block-uniform: the global path has added to out already)
+    __syncthreads();
+    double* const ab = box + P.cap;              // the accumulator box
+    if (tensor) {
+      // the transposed inner-pair contraction: every adjoint entry of U feeds the four box cells its forward entry read
+      for (int e = tid; e < Vo * tq2; e += 256) {
+        const double ua = Uv[e];
+        if (ua == 0.0) continue;
+        const int o = (int)__umulhi((unsigned)e, P.tmagic2), jj = e - o * tq2;
+        const int ja = (int)__umulhi((unsigned)jj, P.tmagic), jb = jj - ja * tq;
+        int il[2];
+        double tt[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int d = D - 2 + q;
+          const double eta = P.eta[(long long)d * P.M + (long long)(q ? jb : ja) * P.tstride[d]];
+          const double c = fma(k[d], eta, a[d]);
+          const double cc = fmin(fmax(c, 0.0), (double)(P.n[d] - 1));
+          const int i0 = min((int)cc, P.n[d] - 2);
+          il[q] = min(max(i0 - blo[d], 0), bext[d] - 2);
+          tt[q] = cc - (double)(blo[d] + il[q]);
+        }
+        const int base = o * inner_v + il[0] * ls[D - 2] + il[1];
+        const double u0 = ua * (1.0 - tt[0]), u1 = ua * tt[0];
+        const double c00 = u0 * (1.0 - tt[1]), c01 = u0 * tt[1], c10 = u1 * (1.0 - tt[1]), c11 = u1 * tt[1];
+        if (c00 != 0.0) unsafeAtomicAdd(ab + base, c00);
+        if (c01 != 0.0) unsafeAtomicAdd(ab + base + 1, c01);
+        if (c10 != 0.0) unsafeAtomicAdd(ab + base + ls[D - 2], c10);
+        if (c11 != 0.0) unsafeAtomicAdd(ab + base + ls[D - 2] + 1, c11);
+      }
+      __syncthreads();
+    }
+    // the box cells that received something, added to out at the box's global offsets
+    for (int e = tid; e < V; e += 256) {
+      const double val = ab[e];
+      if (val == 0.0) continue;
+      int r = e;
+      long long go = 0;
+#pragma unroll
+      for (int d = D - 1; d >= 0; --d) {
+        const int q = r % bext[d];
+        r /= bext[d];
+        go += (long long)(blo[d] + q) * P.stride[d];
+      }
+      unsafeAtomicAdd(io.out + go, val);
+    }
+    return;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);

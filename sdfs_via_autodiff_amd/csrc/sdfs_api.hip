@@ -44,6 +44,10 @@
 
 using namespace sdfs;
 
+// the transpose of the continuous operator's J.v at the cached linearisation (cont_vjp.hip: the C_VJP form of cont_kernel
+// behind the initialisation of io.out; run_cont's MODE_VJP branch, cont_adjoint.hpp)
+namespace sdfs { hipError_t cont_vjp_launch(hipStream_t stream, const ContDesc& cd, const ContIO& io); }
+
 namespace {
 
 constexpr int MAXD = 6;
@@ -809,6 +813,17 @@ int run_cont(sdfs_handle* h, const Apply& a) {
     return cd.D == 4 ? launch_cont_tilted<4>(h, power, cd, io, c) : launch_cont_tilted<6>(h, power, cd, io, c);
   }
   if (a.mode != MODE_T && (rc = ensure_lin(h))) return rc;
+  if (a.mode == MODE_VJP) {
+    // J^T u at the cached linearisation: the scatter form (cont_vjp.hip) behind the in-stream zeroing of out, and
+    // "- u" behind that.  Atomic adds: reproducible to rounding only.  Bytes: u, c2, w read, out zeroed
+    // and read-modify-written (and u, out again for minus_identity); the atomic traffic depends on the boxes and is
+    // not counted.
+    io.w = h->c1; io.v = a.in; io.c2_in = h->c2;
+    const int cid = h->profiling ? counter_id(h, "cont:vjp", (a.minus_identity ? 9 : 6) * n8, 1.5 * flops) : -1;
+    ProfScope ps(h, cid);
+    HIPCHK(h, sdfs::cont_vjp_launch(h->stream, h->cd, io));
+    return 0;
+  }
   const char* tag = "cont:T";
   if (a.mode == MODE_T) { io.w = a.in; io.old = a.old; io.resid = a.resid; if (a.resid) bytes += n8; }
   else if (a.mode == MODE_T_LIN) {
@@ -1598,8 +1613,10 @@ long long last_pass_grid(sdfs_handle* h, const Apply& a) {
 // One application on `plan` (the whole grid, or a stage of a sharded handle): the continuous or the dense operator, or the
 // passes of the plan that serves the request
 int run_plan(sdfs_handle* h, Plan& plan, bool has_first, bool has_last, const Apply& a) {
-  if (a.mode == MODE_VJP) {
-    if (h->cont || h->dense) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product exists for the discretised operator only");
+  // (a continuous handle's transpose is the scatter form of its own kernel, reached through sdfs_cont_apply_vjp_dev /
+  // sdfs_cont_solve_adjoint_dev alone: sdfs_apply_vjp_dev and sdfs_solve_linear_dev refuse it before they get here)
+  if (a.mode == MODE_VJP && !h->cont) {
+    if (h->dense) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product exists for the discretised operator only");
     for (int ax = 0; ax < h->ndim; ++ax)
       if (!h->ax[ax].Qt) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product needs unconditional transition tensors "
                                      "(axis %s is conditional)", h->ax[ax].name);
@@ -3264,6 +3281,8 @@ int sdfs_apply_vjp_dev(sdfs_handle* h, const double* u, double* out, int minus_i
   if (!u || !out) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
   if (h->sharded) return fail(h, SDFS_ERR_ARG, "sharded handle: no vector-Jacobian product");
   if (!h->c1 || !h->c2 || h->lin_stale) return fail(h, SDFS_ERR_ARG, "sdfs_apply_vjp_dev before sdfs_linearize_dev");
+  // (a continuous handle has sdfs_cont_apply_vjp_dev, whose result is reproducible to rounding only: never behind this name)
+  if (h->cont) return fail(h, SDFS_ERR_UNSUPPORTED, "the vector-Jacobian product exists for the discretised operator only");
   Apply a(MODE_VJP, u, out, u);
   a.minus_identity = minus_identity;
   return apply(h, a);
@@ -4228,4 +4247,5 @@ int sdfs_describe_plan(const sdfs_handle* h, char* buf, int64_t cap) {
 #include "cont_sim.hpp"    // continuous-state paths (sdfs_cont_sdf_mean_dev, sdfs_cont_sim_*), built on the definitions above
 #include "cont_price.hpp"  // continuous-state pricing (sdfs_cont_set_tilt_dev ... sdfs_cont_tilted_horizons_dev), likewise
 #include "cont_sens.hpp"   // continuous-state parameter tangent (sdfs_cont_param_tangent_dev), likewise
+#include "cont_adjoint.hpp"   // continuous-state J^T u and adjoint solve (sdfs_cont_apply_vjp_dev, sdfs_cont_solve_adjoint_dev), likewise
 #include "batch_api.hpp"   // the batch API (sdfs_batch_*), built on the definitions above

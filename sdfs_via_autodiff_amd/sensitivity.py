@@ -29,7 +29,7 @@ import numpy as np
 
 from .discretize import _rouwenhorst_grid, discretize_ssy, discretize_gcy
 from ._requests import (LAYOUT, SSY_PARAMS, GCY_PARAMS, _kind, _operator, _device_grid, _cont_grids, _cont_operator_or_d,
-                        _cont_operator, _check_w_star, _check_tolerance, _Fence)
+                        _cont_operator, _cont_wrt, _check_finite_grid, _check_w_star, _check_tolerance, _Fence)
 
 SSY_SUPPORTED, GCY_SUPPORTED = LAYOUT["ssy"].supported, LAYOUT["gcy"].supported
 SSY_PERSISTENCE, GCY_PERSISTENCE = tuple(LAYOUT["ssy"].persistence), tuple(LAYOUT["gcy"].persistence)
@@ -339,20 +339,8 @@ def wc_ratio_sensitivities_continuous(model, grids, w_star, wrt=None, *, rtol=1e
     these parameters and grids, whose nodes and weights define the expectation; otherwise one is built with
     ``qnwnorm([d] * D)`` on ``device``.  Every ValueError / TypeError is raised before any device work."""
     import torch
-    allp = _kind(model).params                                     # (TypeError for anything but an SSY or a GCY)
-    _, _, grids, shapes = _cont_grids(model, grids, w_star)
-    if wrt is None:
-        names = allp
-    elif isinstance(wrt, str):
-        names = (wrt,)
-    else:
-        try:
-            names = tuple(wrt)
-        except TypeError:
-            raise TypeError(f"wrt must be None, a parameter name or a sequence of names, got {wrt!r}") from None
-    for nm in names:
-        if nm not in allp:
-            raise ValueError(f"unknown {type(model).__name__} parameter {nm!r} (one of {', '.join(allp)})")
+    _, _, grids, shapes = _cont_grids(model, grids, w_star)        # (TypeError for anything but an SSY or a GCY)
+    names, allp = _cont_wrt(model, wrt)
     rtol, atol = _check_tolerance("rtol", rtol, False), _check_tolerance("atol", atol, True)
     d = _cont_operator_or_d(model, grids, shapes, operator, d)
     _check_w_star(w_star, "a fixed point of T is 1 + β(…)^(1/θ) > 1; the tangent takes ln of its interpolant")
@@ -390,6 +378,53 @@ def wc_ratio_gradient(model, shapes, w_star, g, rtol=1e-10, atol=0.0, persistenc
     for nm, (dp, da, dg) in zip(names, dirs):
         op.param_tangent_dev(w.data_ptr(), dp, da, rhs.data_ptr(), tw.data_ptr(), dgen=dg)
         out[nm] = float(torch.dot(lv, rhs.view(-1)))
+    return out
+
+
+def wc_ratio_gradient_continuous(model, grids, w_star, g, wrt=None, *, rtol=1e-10, atol=0.0, operator=None, d=5, device=0):
+    """``wc_ratio_gradient`` for the continuous-state model: {name: d⟨g, w*⟩/dp_name} (floats) at a converged fixed point
+    ``w_star`` on ``grids`` (as ``wc_ratio_continuous`` returns them), plus ``"_info": (BiCGSTAB iterations, final
+    relative residual)`` of the adjoint solve and ``"_adjoint"``: λ as a host array of the grid's shape.  One
+    linearisation at w*, ONE transposed solve λ = (I − J(w*)ᵀ)⁻¹ g (``ContinuousOperator.cont_solve_adjoint_dev``), then
+    per parameter one tangent of T (``cont_param_tangent_dev``) and the dot product ⟨λ, ∂T/∂p⟩, no further solve --
+    where ``wc_ratio_sensitivities_continuous`` takes one solve per parameter.  ``SdfsError`` if the solve breaks down
+    or stops above max(rtol |g|₂, atol).
+
+    What is differentiated is the operator a ``ContinuousOperator`` represents, T(w; p) with its grids, nodes and weights
+    held fixed -- ``jax.vjp`` of the reference's ``T`` with respect to the parameters, ``grids, nodes, weights`` closed
+    over.  ``build_grid`` depends on the parameters too; the movement of the grid is NOT part of this derivative.  Every
+    parameter is admitted, the persistences included.
+
+    Jᵀ is applied with hardware fp64 atomic adds whose arrival order varies: two calls on the same input agree to
+    rounding (far inside the solve's tolerance), NOT bit for bit -- unlike every other analysis function here.
+
+    g: a finite array of the grid's shape.  wrt, operator, d, device: as in ``wc_ratio_sensitivities_continuous``.  Every
+    ValueError / TypeError is raised before any device work."""
+    import torch
+    _, _, grids, shapes = _cont_grids(model, grids, w_star)        # (TypeError for anything but an SSY or a GCY)
+    names, allp = _cont_wrt(model, wrt)
+    _check_finite_grid(g, shapes, "g")
+    rtol, atol = _check_tolerance("rtol", rtol, False), _check_tolerance("atol", atol, True)
+    d = _cont_operator_or_d(model, grids, shapes, operator, d)
+    _check_w_star(w_star, "a fixed point of T is 1 + β(…)^(1/θ) > 1; the tangent takes ln of its interpolant")
+    op = _cont_operator(model, grids, operator, d, device)
+    w = _device_grid(op, w_star, "w_star")
+    gd = _device_grid(op, g, "g")
+    lam, rhs = torch.empty_like(w), torch.empty_like(w)
+    fence = _Fence(op)
+    fence.before_library()
+    op.linearize_dev(w.data_ptr())
+    info = op.cont_solve_adjoint_dev(gd.data_ptr(), lam.data_ptr(), rtol, atol)   # (ends synchronised)
+    lv = lam.view(-1)
+    out = {}
+    for nm in names:
+        dp = np.zeros(len(allp))
+        dp[allp.index(nm)] = 1.0
+        op.cont_param_tangent_dev(w.data_ptr(), dp, rhs.data_ptr())
+        fence.before_torch()
+        out[nm] = float(torch.dot(lv, rhs.view(-1)))               # (.item(): torch's stream is drained again)
+    out["_info"] = info
+    out["_adjoint"] = lam.cpu().numpy()
     return out
 
 
