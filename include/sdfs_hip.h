@@ -314,6 +314,21 @@ typedef struct sdfs_cont_sim_desc {
  * synchronisation and no atomics; a path's output depends only on its number, the seed, s0, its start and the model. */
 int sdfs_cont_sim_paths_dev(sdfs_handle* h, const double* records_dev, const sdfs_cont_sim_desc* desc, double* stats_dev,
                             uint32_t* clamped_dev, double* final_state_dev, double* states_dev, double* series_dev);
+/* The same paths with the return series of a claim on G_c^kappa.  v_dev: the claim's price-dividend ratio
+ * on the grid (N doubles, positive; what sdfs_cont_solve_tilted_dev returns for K(1, theta, kappa - gamma), or any grid
+ * function).  sdfs_cont_sim_claim_records_dev writes one 32-byte record {w, -ln E_x[M], v, 0} per grid point into
+ * records_dev (N x 4 doubles, 32-byte aligned), and sdfs_cont_sim_claim_paths_dev interpolates its three fields with the
+ * same clamped cell and offsets: with v^ the interpolant of v,
+ *   rd_t = kappa dc_t + ln(1 + v^(x_t)) - ln v^(x_{t-1}),  xd_t = rd_t - rf_t,  pd_t = ln v^(x_t).
+ * stats_dev: 28 x n_paths doubles: mean, std, ac1 of dc, m, rf, rc, xc, wc, rd, xd, pd at rows 3k ... 3k+2, then the OLS
+ * slope of xd_t on pd_{t-1}.  series_dev: 9 x n_paths x T.  The six base series, the states, clamped_dev and
+ * final_state_dev have the bits sdfs_cont_sim_paths_dev gives for the same desc.  desc->lookahead: 0 or 1; desc->group: 0
+ * (the default), 4 or 8; kappa finite; anything else is SDFS_ERR_ARG before any launch. */
+int sdfs_cont_sim_claim_records_dev(sdfs_handle* h, const double* w_dev, const double* em_dev, const double* v_dev,
+                                    double* records_dev);
+int sdfs_cont_sim_claim_paths_dev(sdfs_handle* h, const double* records_dev, const sdfs_cont_sim_desc* desc, double kappa,
+                                  double* stats_dev, uint32_t* clamped_dev, double* final_state_dev, double* states_dev,
+                                  double* series_dev);
 
 /* Asset prices of the continuous-state model at w (handles of sdfs_create_continuous only, else
  * SDFS_ERR_UNSUPPORTED; fp64).  With the handle's nodes eta_m and weights W_m, x'_m = next_state(x, eta_m) and ^ the

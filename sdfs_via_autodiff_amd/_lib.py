@@ -110,6 +110,8 @@ SYMBOLS = {
     "sdfs_cont_sdf_mean_dev": (C.c_int, [_P, _P, _P]),
     "sdfs_cont_sim_records_dev": (C.c_int, [_P, _P, _P, _P]),
     "sdfs_cont_sim_paths_dev": (C.c_int, [_P, _P, C.POINTER(sdfs_cont_sim_desc), _P, _P, _P, _P, _P]),
+    "sdfs_cont_sim_claim_records_dev": (C.c_int, [_P, _P, _P, _P, _P]),
+    "sdfs_cont_sim_claim_paths_dev": (C.c_int, [_P, _P, C.POINTER(sdfs_cont_sim_desc), C.c_double, _P, _P, _P, _P, _P]),
     "sdfs_cont_set_tilt_dev": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double]),
     "sdfs_cont_apply_tilted_dev": (C.c_int, [_P, _P, _P]),
     "sdfs_cont_solve_tilted_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _P, _I64, _D]),

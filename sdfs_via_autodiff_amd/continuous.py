@@ -174,6 +174,12 @@ class ContinuousOperator(KoopmansOperator):
                            lookahead=0, group=0):
         """Paths of the continuous-state model from the records (sdfs_cont_sim_paths_dev).  start: one state for every
         path; start_ptr: a device array (n_paths, D), one state per path; neither: the zero state."""
+        d = self._cont_sim_desc(seed, path_offset, n_paths, burn_in, n_periods, step_offset, start, start_ptr, lookahead, group)
+        check(lib.sdfs_cont_sim_paths_dev(self._h, rec_ptr, C.byref(d), stats_ptr, clamped_ptr, final_state_ptr, states_ptr,
+                                          series_ptr), self._h)
+
+    @staticmethod
+    def _cont_sim_desc(seed, path_offset, n_paths, burn_in, n_periods, step_offset, start, start_ptr, lookahead, group):
         d = _lib.sdfs_cont_sim_desc()
         d.seed, d.path_offset, d.n_paths = int(seed), int(path_offset), int(n_paths)
         d.burn_in, d.n_periods, d.step_offset = int(burn_in), int(n_periods), int(step_offset)
@@ -184,8 +190,20 @@ class ContinuousOperator(KoopmansOperator):
             d.start_mode = 1
             for a, s in enumerate(start):
                 d.start[a] = float(s)
-        check(lib.sdfs_cont_sim_paths_dev(self._h, rec_ptr, C.byref(d), stats_ptr, clamped_ptr, final_state_ptr, states_ptr,
-                                          series_ptr), self._h)
+        return d
+
+    def cont_sim_claim_records_dev(self, w_ptr, em_ptr, v_ptr, rec_ptr):
+        """One 32-byte record {w, −ln E_x[M], v, 0} per grid point into rec_ptr (N x 4 doubles)."""
+        check(lib.sdfs_cont_sim_claim_records_dev(self._h, w_ptr, em_ptr, v_ptr, rec_ptr), self._h)
+
+    def cont_sim_claim_paths_dev(self, rec_ptr, kappa, seed, path_offset, n_paths, burn_in, n_periods, stats_ptr, clamped_ptr,
+                                 final_state_ptr, step_offset=0, start=None, start_ptr=None, states_ptr=None, series_ptr=None,
+                                 group=0):
+        """``cont_sim_paths_dev`` with the series rd, xd, pd of a claim on G_c^κ from the records of
+        ``cont_sim_claim_records_dev`` (sdfs_cont_sim_claim_paths_dev): 28 statistics rows, 9 stored series."""
+        d = self._cont_sim_desc(seed, path_offset, n_paths, burn_in, n_periods, step_offset, start, start_ptr, 0, group)
+        check(lib.sdfs_cont_sim_claim_paths_dev(self._h, rec_ptr, C.byref(d), float(kappa), stats_ptr, clamped_ptr,
+                                                final_state_ptr, states_ptr, series_ptr), self._h)
 
     # -- asset prices (pricing.*_continuous; DESIGN §4.15) -------------------------------------------------------------
     # ``set_tilt_dev``, ``apply_tilted_dev`` and ``solve_tilted_dev`` of this operator call these entry points (w is

@@ -1,5 +1,5 @@
 // cont_sim.hpp -- simulated paths of the continuous-state model at w* (sdfs_cont_sim_records_dev,
-// sdfs_cont_sim_paths_dev).
+// sdfs_cont_sim_paths_dev) and, further down, their claim form (sdfs_cont_sim_claim_*_dev).
 //
 // Not a header of its own: sdfs_api.hip includes it once, after the single-problem API, and it uses sdfs_handle,
 // launch_kernel, Counter, check and fail of that file.
@@ -138,16 +138,21 @@ __device__ __forceinline__ void csim_locate(const ContDesc& P, const double (&x)
 __device__ __forceinline__ double2 csim_lerp(double t, const double2 v0, const double2 v1) {
   return make_double2(fma(t, v1.x - v0.x, v0.x), fma(t, v1.y - v0.y, v0.y));
 }
+// (the fourth word of a claim record is padding)
+__device__ __forceinline__ double4 csim_lerp(double t, const double4 v0, const double4 v1) {
+  return make_double4(fma(t, v1.x - v0.x, v0.x), fma(t, v1.y - v0.y, v0.y), fma(t, v1.z - v0.z, v0.z), 0.0);
+}
 
 // {w, rf}(x) for KK states side by side: dimensions below D - GD are loops, the GD fastest one group of loads
-template <int D, int GD, int KK, int d>
-__device__ __forceinline__ void csim_fold(const double2* __restrict__ rec, const unsigned (&step)[D],
-                                          const ContSimState<D> (&s)[KK], const unsigned (&off)[KK], double2 (&r)[KK]) {
+// (V: double2 for the records; the claim form folds its own record type)
+template <int D, int GD, int KK, int d, class V>
+__device__ __forceinline__ void csim_fold(const V* __restrict__ rec, const unsigned (&step)[D],
+                                          const ContSimState<D> (&s)[KK], const unsigned (&off)[KK], V (&r)[KK]) {
   if constexpr (d == D) {
 #pragma unroll
     for (int j = 0; j < KK; ++j) r[j] = rec[off[j]];
   } else {
-    double2 v0[KK], v1[KK];
+    V v0[KK], v1[KK];
     if constexpr (d >= D - GD) {
       unsigned o1[KK];
 #pragma unroll
@@ -158,7 +163,7 @@ __device__ __forceinline__ void csim_fold(const double2* __restrict__ rec, const
 #pragma unroll 1
       for (int b = 0; b < 2; ++b) {
         unsigned o[KK];
-        double2 q[KK];
+        V q[KK];
 #pragma unroll
         for (int j = 0; j < KK; ++j) o[j] = off[j] + (b ? step[d] : 0u);
         csim_fold<D, GD, KK, d + 1>(rec, step, s, o, q);
@@ -311,6 +316,184 @@ k_cont_sim_records(long long n, const double* __restrict__ w, const double* __re
     rec[i] = make_double2(w[i], -log(em[i]));
 }
 
+// -- the claim form (sdfs_cont_sim_claim_*_dev) ------------------------------------------------------------
+// k_cont_sim_paths with a third interpolated field v, the price-dividend ratio of a claim on G_c^kappa, and its series
+//   rd_t = kappa dc_t + ln(1 + v(x_t)) - ln v(x_{t-1}),  xd_t = rd_t - rf_t,  pd_t = ln v(x_t);
+// the slope is that of xd_t on pd_{t-1}.  A kernel of its own, so that k_cont_sim_paths stays the code it was; what the
+// two share is csim_normals, csim_next, csim_locate, csim_fold and sim_acc, and a base series has the plain form's bits.
+// Nine series of five sums do not fit beside the normals' sincos in the 256 registers of two waves per SIMD, so the
+// claim form carries less from step to step than the plain form would:
+//   dc is formed from x_{t-1} as soon as xi is drawn, before the state advances (mu_c + z and phi_c exp(h_c) are not carried);
+//   xc and xd are shifted by the difference of their terms' shifts, which is their first value bit for bit;
+//   pd_{t-1} - pd_1 is both the previous shifted pd and the slope's regressor, so the regressor's sums are pd's own,
+//   corrected at the ends (csim_claim_finish);
+//   the storing form keeps no sums at all: it writes the series and then reads its own back in step order.
+constexpr int CSIM_NSER_CLAIM = 9;           // dc m rf rc xc wc rd xd pd
+constexpr int csim_claim_gd_default(int) { return 3; }   // groups of 8 corners in 4-D and in 6-D (the A/B of DESIGN 4.18)
+
+// the sums of the nine series and of the slope; s0 of xc and xd and pv of pd are formed where they are used
+struct ContSimClaimSums {
+  SimAcc acc[CSIM_NSER_CLAIM];
+  double sxy, dp0;                           // sum of (pd_{t-1} - pd_1)(xd_t - xd_1); pd_0 - pd_1
+};
+
+// step t's nine values v, pd_{t-1} = lvp
+template <bool FIRST>
+__device__ __forceinline__ void csim_claim_acc(ContSimClaimSums& c, const double (&v)[CSIM_NSER_CLAIM], double lvp) {
+#pragma clang fp contract(off)
+  if (!FIRST) {
+    c.acc[4].s0 = c.acc[3].s0 - c.acc[2].s0;
+    c.acc[7].s0 = c.acc[6].s0 - c.acc[2].s0;
+    c.acc[8].pv = lvp - c.acc[8].s0;
+  }
+  const double dx = FIRST ? 0.0 : c.acc[8].pv;
+#pragma unroll
+  for (int k = 0; k < CSIM_NSER_CLAIM; ++k) sim_acc<FIRST>(c.acc[k], v[k]);
+  if (FIRST) { c.sxy = 0.0; c.dp0 = lvp - v[8]; }
+  else c.sxy = fma(dx, c.acc[7].pv, c.sxy);
+}
+
+__device__ __forceinline__ void csim_claim_finish(const ContSimClaimSums& c, unsigned T, long long n_paths, long long pl,
+                                                  double* __restrict__ stats) {
+  const double Tn = (double)T;
+#pragma unroll
+  for (int k = 0; k < CSIM_NSER_CLAIM; ++k) {
+    const SimAcc& a = c.acc[k];
+    const double s0 = k == 4 ? c.acc[3].s0 - c.acc[2].s0 : (k == 7 ? c.acc[6].s0 - c.acc[2].s0 : a.s0);
+    const double mt = a.s1 / Tn;
+    const double den = a.s2 - a.s1 * mt;
+    const double num = a.sl - mt * (2.0 * a.s1 - a.pv) + (Tn - 1.0) * mt * mt;
+    stats[(size_t)(3 * k + 0) * n_paths + pl] = s0 + mt;
+    stats[(size_t)(3 * k + 1) * n_paths + pl] = sqrt(fmax(den, 0.0) / Tn);
+    stats[(size_t)(3 * k + 2) * n_paths + pl] = den > 0.0 ? num / den : __builtin_nan("");
+  }
+  // the regressor pd_{t-1} - pd_1, t = 1 ... T: dp0, then pd's shifted values but the last
+  const SimAcc& q = c.acc[8];
+  const double sx = c.dp0 + (q.s1 - q.pv), sxx = fma(c.dp0, c.dp0, q.s2 - q.pv * q.pv);
+  const double sy = c.acc[7].s1;
+  const double dxx = sxx - sx * (sx / Tn), dxy = c.sxy - sx * (sy / Tn);
+  stats[(size_t)(3 * CSIM_NSER_CLAIM) * n_paths + pl] = dxx > 0.0 ? dxy / dxx : __builtin_nan("");
+}
+
+// waves per SIMD the register allocation is held to: the plain form's two, but one where the 6-D form keeps its sums
+// in registers, which at two waves spills
+constexpr int csim_claim_waves(int D, bool store) { return D == 4 || store ? 2 : 1; }
+
+// rec: one 32-byte record {w, -ln E_x[M], v, 0} per grid point (k_cont_sim_claim_records), a corner one 32-byte load
+template <int D, int GD, bool STORE>
+__global__ void __launch_bounds__(CSIM_BLOCK) __attribute__((amdgpu_waves_per_eu(csim_claim_waves(D, STORE), 2)))
+k_cont_sim_claim_paths(const ContDesc P, const ContSimArgs a, const double4* __restrict__ rec, const double kappa,
+                       double* __restrict__ stats, unsigned* __restrict__ clamped, double* __restrict__ final_state,
+                       double* __restrict__ st_out, double* ser_out) {
+  static_assert(GD >= 1 && GD < D, "a group is a proper part of the corner set");
+  const long long pl = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pl >= a.n_paths) return;               // (no barrier below)
+  const unsigned p = (unsigned)(a.path0 + (unsigned long long)pl);
+  const unsigned T = a.n_periods, B = a.burn_in, s0 = a.step0;
+  unsigned step[D];
+#pragma unroll
+  for (int d = 0; d < D; ++d) step[d] = (unsigned)P.stride[d];
+
+  double x[D];
+#pragma unroll
+  for (int d = 0; d < D; ++d)
+    x[d] = a.start_mode == 0 ? 0.0 : (a.start_mode == 1 ? a.start[d] : a.start_dev[(size_t)pl * D + d]);
+  ContSimNormals nm;
+  for (unsigned k = 1; k <= B; ++k) {
+    csim_normals<D, false>(a, s0 + k, p, nm);
+    csim_next<D>(P, x, nm);
+  }
+
+  auto store_state = [&](unsigned t) {       // x_{B + t}
+    if (STORE) {
+#pragma unroll
+      for (int d = 0; d < D; ++d) st_out[((size_t)pl * (T + 1) + t) * D + d] = x[d];
+    }
+  };
+  auto fields = [&](ContSimState<D> (&s)[1]) {       // {w, rf, v, .}(x)
+    unsigned o[1];
+    double4 r[1];
+    csim_locate<D>(P, x, s[0]);
+    o[0] = s[0].off;
+    csim_fold<D, GD, 1, 0>(rec, step, s, o, r);
+    return r[0];
+  };
+
+  // x_B: the previous state of the first recorded step
+  double lw1, rf, lv;
+  {
+    ContSimState<D> s[1];
+    const double4 r = fields(s);
+    lw1 = log(r.x - 1.0); rf = r.y; lv = log(r.z);
+    store_state(0u);
+  }
+  const double pd0 = lv;
+
+  ContSimClaimSums sums;
+  unsigned nout = 0;
+
+  // recorded step t (1 ... T): draw, dc from x_{t-1}, advance, interpolate at x_t, the nine values
+  auto record = [&](auto first_tag, unsigned t) {
+#pragma clang fp contract(off)
+    constexpr bool FIRST = decltype(first_tag)::value;
+    csim_normals<D, true>(a, s0 + B + t, p, nm);
+    double zval = 0.0, hcval = 0.0;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      if (P.zdim == d) zval = x[d];
+      if (P.hcdim == d) hcval = x[d];
+    }
+    const double muz = P.mu_c + zval, sc = P.phi_c * exp(hcval);       // (csim_locate's, at x_{t-1})
+    const double dc = fma(sc, nm.xi, muz);
+    csim_next<D>(P, x, nm);
+    store_state(t);
+    ContSimState<D> s[1];
+    const double4 r = fields(s);
+    const double lw = log(r.x), lvt = log(r.z), l1v = log(1.0 + r.z);
+    const double rl = lw - lw1;
+    const double m = fma(a.theta - 1.0, rl, fma(-a.gamma, dc, fma(a.theta, s[0].hl, a.theta_ln_beta)));
+    const double rc = dc + rl;
+    const double rd = fma(kappa, dc, l1v - lv);
+    const double v[CSIM_NSER_CLAIM] = {dc, m, rf, rc, rc - rf, r.x, rd, rd - rf, lvt};
+    nout += s[0].out ? 1u : 0u;
+    if (STORE) {
+#pragma unroll
+      for (int k = 0; k < CSIM_NSER_CLAIM; ++k) ser_out[((size_t)k * a.n_paths + pl) * T + (t - 1)] = v[k];
+    } else {
+      csim_claim_acc<FIRST>(sums, v, lv);
+    }
+    lw1 = log(r.x - 1.0); rf = r.y; lv = lvt;
+  };
+
+  record(std::true_type{}, 1u);
+  for (unsigned t = 2; t <= T; ++t) record(std::false_type{}, t);
+
+  if (STORE) {                               // the sums from this lane's own stored series, in step order
+    double lvp = pd0;
+    auto replay = [&](auto first_tag, unsigned t) {
+      double v[CSIM_NSER_CLAIM];
+#pragma unroll
+      for (int k = 0; k < CSIM_NSER_CLAIM; ++k) v[k] = ser_out[((size_t)k * a.n_paths + pl) * T + (t - 1)];
+      csim_claim_acc<decltype(first_tag)::value>(sums, v, lvp);
+      lvp = v[8];
+    };
+    replay(std::true_type{}, 1u);
+    for (unsigned t = 2; t <= T; ++t) replay(std::false_type{}, t);
+  }
+  csim_claim_finish(sums, T, a.n_paths, pl, stats);
+  clamped[pl] = nout;
+#pragma unroll
+  for (int d = 0; d < D; ++d) final_state[(size_t)pl * D + d] = x[d];
+}
+
+__global__ void __launch_bounds__(CSIM_BLOCK)
+k_cont_sim_claim_records(long long n, const double* __restrict__ w, const double* __restrict__ em, const double* __restrict__ v,
+                         double4* __restrict__ rec) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    rec[i] = make_double4(w[i], -log(em[i]), v[i], 0.0);
+}
+
 }  // namespace sdfs
 
 namespace {
@@ -338,6 +521,17 @@ csim_fn csim_variant(int gd, int k, bool store) {
     if (gd == 4) return k == 1 ? csim_form<6, 4, 1>(store) : (k == 2 ? csim_form<6, 4, 2>(store) : nullptr);
   }
   return nullptr;
+}
+
+// the claim form: look-ahead 1, groups of 4 or 8 corners and, on the default group, with the paths stored
+typedef void (*csim_claim_fn)(const ContDesc, const ContSimArgs, const double4*, const double, double*, unsigned*, double*, double*,
+                              double*);
+
+template <int D>
+csim_claim_fn csim_claim_variant(int gd, bool store) {
+  constexpr int GD0 = csim_claim_gd_default(D);
+  if (store) return gd == GD0 ? k_cont_sim_claim_paths<D, GD0, true> : nullptr;
+  return gd == 2 ? k_cont_sim_claim_paths<D, 2, false> : (gd == 3 ? k_cont_sim_claim_paths<D, 3, false> : nullptr);
 }
 
 int cont_handle_ok(sdfs_handle* h, const char* fn) {
@@ -374,11 +568,15 @@ int sdfs_cont_sim_records_dev(sdfs_handle* h, const double* w, const double* em,
                        reinterpret_cast<double2*>(rec));
 }
 
-int sdfs_cont_sim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_cont_sim_desc* d, double* stats, uint32_t* clamped,
-                            double* final_state, double* states, double* series) {
+}  // extern "C"
+
+namespace {
+// the two path entry points: claim = false (sdfs_cont_sim_paths_dev), or the claim form with its kappa
+int csim_paths(sdfs_handle* h, const char* fn_name, bool claim, const double* rec, double kappa, const sdfs_cont_sim_desc* d, double* stats, uint32_t* clamped, double* final_state, double* states, double* series) {
   int rc = check(h); if (rc) return rc;
-  if ((rc = cont_handle_ok(h, "sdfs_cont_sim_paths_dev"))) return rc;
+  if ((rc = cont_handle_ok(h, fn_name))) return rc;
   if (!rec || !d || !stats || !clamped || !final_state) return fail(h, SDFS_ERR_ARG, "NULL records, desc, stats, clamped or final_state");
+  if (claim && !std::isfinite(kappa)) return fail(h, SDFS_ERR_ARG, "kappa is not finite");
   if (!states != !series) return fail(h, SDFS_ERR_ARG, "states and series are stored together: both NULL or neither");
   char msg[160];
   if (!sim_ranges_ok(msg, d->path_offset, d->n_paths, &d->step_offset, d->burn_in, d->n_periods, 0)) return fail(h, SDFS_ERR_ARG, "%s", msg);
@@ -388,13 +586,19 @@ int sdfs_cont_sim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_cont_s
   for (int ax = 0; ax < cd.D && d->start_mode == 1; ++ax)
     if (!std::isfinite(d->start[ax])) return fail(h, SDFS_ERR_ARG, "start[%d] is not finite", ax);
   const int k = d->lookahead ? d->lookahead : CSIM_K_DEFAULT;
-  const int g = d->group ? d->group : 1 << csim_gd_default(cd.D);
+  const int g = d->group ? d->group : 1 << (claim ? csim_claim_gd_default(cd.D) : csim_gd_default(cd.D));
   const int gd = g == 4 ? 2 : (g == 8 ? 3 : (g == 16 ? 4 : 0));
   const bool store = states != nullptr;
-  if (store && (k != CSIM_K_DEFAULT || gd != csim_gd_default(cd.D)))
+  if (store && (k != CSIM_K_DEFAULT || gd != (claim ? csim_claim_gd_default(cd.D) : csim_gd_default(cd.D))))
     return fail(h, SDFS_ERR_ARG, "stored paths run with the default lookahead and group");
-  const csim_fn fn = (k == 1 || k == 2 || k == 4) && gd ? (cd.D == 4 ? csim_variant<4>(gd, k, store) : csim_variant<6>(gd, k, store)) : nullptr;
-  if (!fn) return fail(h, SDFS_ERR_ARG, "lookahead = %d, group = %d: lookahead 1, 2 or 4 with groups of 4 or 8 corners, and in 6-D "
+  csim_claim_fn cfn = nullptr;
+  if (claim) {
+    if (k == 1) cfn = cd.D == 4 ? csim_claim_variant<4>(gd, store) : csim_claim_variant<6>(gd, store);
+    if (!cfn) return fail(h, SDFS_ERR_ARG, "lookahead = %d, group = %d: the claim form runs with lookahead 1 and groups of 4 or 8 corners",
+                          d->lookahead, d->group);
+  }
+  const csim_fn fn = !claim && (k == 1 || k == 2 || k == 4) && gd ? (cd.D == 4 ? csim_variant<4>(gd, k, store) : csim_variant<6>(gd, k, store)) : nullptr;
+  if (!fn && !cfn) return fail(h, SDFS_ERR_ARG, "lookahead = %d, group = %d: lookahead 1, 2 or 4 with groups of 4 or 8 corners, and in 6-D "
                        "lookahead 1 or 2 with groups of 16", d->lookahead, d->group);
   ContSimArgs a{};
   a.key0 = (unsigned)(d->seed & 0xffffffffu); a.key1 = (unsigned)(d->seed >> 32);
@@ -406,9 +610,35 @@ int sdfs_cont_sim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_cont_s
   a.theta = h->theta; a.theta_ln_beta = h->theta * std::log(h->beta); a.gamma = h->cont_gamma;
   const dim3 grid((unsigned)((d->n_paths + CSIM_BLOCK - 1) / CSIM_BLOCK));
   const double steps = (double)d->n_paths * (double)(d->burn_in + d->n_periods);
-  return launch_kernel(h, fn, grid, dim3(CSIM_BLOCK), 0,
-                       Counter("csim:paths", 16.0 * (double)(1 << cd.D) * (double)d->n_paths * (double)(d->n_periods + 1), steps), cd, a,
+  const double corners = (double)(1 << cd.D) * (double)d->n_paths * (double)(d->n_periods + 1);
+  if (cfn)
+    return launch_kernel(h, cfn, grid, dim3(CSIM_BLOCK), 0, Counter("csim:claim_paths", 32.0 * corners, steps), cd, a,
+                         reinterpret_cast<const double4*>(rec), kappa, stats, clamped, final_state, states, series);
+  return launch_kernel(h, fn, grid, dim3(CSIM_BLOCK), 0, Counter("csim:paths", 16.0 * corners, steps), cd, a,
                        reinterpret_cast<const double2*>(rec), stats, clamped, final_state, states, series);
+}
+}  // namespace
+
+extern "C" {
+
+int sdfs_cont_sim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_cont_sim_desc* d, double* stats, uint32_t* clamped,
+                            double* final_state, double* states, double* series) {
+  return csim_paths(h, "sdfs_cont_sim_paths_dev", false, rec, 0.0, d, stats, clamped, final_state, states, series);
+}
+
+int sdfs_cont_sim_claim_records_dev(sdfs_handle* h, const double* w, const double* em, const double* v, double* rec) {
+  int rc = check(h); if (rc) return rc;
+  if ((rc = cont_handle_ok(h, "sdfs_cont_sim_claim_records_dev"))) return rc;
+  if (!w || !em || !v || !rec) return fail(h, SDFS_ERR_ARG, "NULL grid pointer");
+  const long long N = h->cd.N;
+  const int grid = stream_grid(h, N, CSIM_BLOCK);
+  return launch_kernel(h, k_cont_sim_claim_records, dim3(grid), dim3(CSIM_BLOCK), 0, Counter("csim:claim_records", 56.0 * (double)N, 0),
+                       N, w, em, v, reinterpret_cast<double4*>(rec));
+}
+
+int sdfs_cont_sim_claim_paths_dev(sdfs_handle* h, const double* rec, const sdfs_cont_sim_desc* d, double kappa, double* stats,
+                                  uint32_t* clamped, double* final_state, double* states, double* series) {
+  return csim_paths(h, "sdfs_cont_sim_claim_paths_dev", true, rec, kappa, d, stats, clamped, final_state, states, series);
 }
 
 }  // extern "C"

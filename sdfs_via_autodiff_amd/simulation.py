@@ -17,7 +17,8 @@ Random numbers are Philox4x32-10 with counter (t, p, b, 0) for step t of path p,
 (sdfs_sim_records_dev, sdfs_sim_paths_dev), fp64.  DESIGN §4.8.
 
 ``simulate_continuous`` walks the continuous-state model instead (x_t = next_state(x_{t−1}, η_t), w* and −ln E_x[M]
-interpolated along the path): counter (t, p, b, 1), tests/cont_sim_oracle.py, sdfs_cont_sim_*_dev, DESIGN §4.14.
+interpolated along the path): counter (t, p, b, 1), tests/cont_sim_oracle.py, sdfs_cont_sim_*_dev, DESIGN §4.14.  With
+``kappa`` it interpolates the claim's v as well and adds rd, xd, pd (sdfs_cont_sim_claim_*_dev).
 """
 import math
 
@@ -26,8 +27,8 @@ import numpy as np
 from ._requests import MAX_RETURNED  # noqa: F401  (path-steps of returned series; a name of this module)
 from ._requests import (LAYOUT, _kind, _shapes, _check_grid, _kappa, _count, _check_w_star, _path_request,
                         _cont_grids, _cont_operator_or_d, _operator, _cont_operator, _device_grid, _Fence,
-                        stationary_weights)
-from .pricing import claim_prices
+                        _check_finite_grid, stationary_weights)
+from .pricing import claim_prices, _claim_prices
 
 SERIES = ("dc", "m", "rf", "rc", "xc", "wc")
 SERIES_KAPPA = SERIES + ("rd", "xd", "pd")
@@ -144,6 +145,7 @@ def simulate(model, shapes, w_star, n_paths, n_periods, *, burn_in=0, seed=0, pa
 
 
 CONT_REC_BYTES = 16               # per grid point: {w, −ln E_x[M]}
+CONT_CLAIM_REC_BYTES = 32         # ... with a claim: {w, −ln E_x[M], v, 0}
 
 
 def _cont_start(start, nd, P):
@@ -161,8 +163,19 @@ def _cont_start(start, nd, P):
     return st
 
 
+def _cont_pd(pd, kappa, shapes):
+    """The checks of a caller's price–dividend ratio: it needs ``kappa``, the grid's shape, finite and positive entries."""
+    if kappa is None:
+        raise ValueError("pd is the price–dividend ratio of a claim on G_c^κ: it needs kappa")
+    _check_finite_grid(pd, shapes, "pd")
+    import torch
+    ok = bool(torch.all(pd > 0)) if isinstance(pd, torch.Tensor) else bool(np.all(np.asarray(pd, dtype=np.float64) > 0.0))
+    if not ok:
+        raise ValueError("pd must be positive at every grid point (the series need ln v)")
+
+
 def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, seed=0, path_offset=0, step_offset=0,
-                        start=None, operator=None, d=5, return_paths=False, device=0):
+                        start=None, operator=None, d=5, return_paths=False, device=0, kappa=None, pd=None, rtol=1e-10):
     """Simulate ``n_paths`` paths (numbered path_offset … path_offset + n_paths − 1) of the continuous-state model:
     x_t = next_state(x_{t−1}, η_t) with standard normal η_t, the grid function ``w_star`` (on ``grids``, as
     ``wc_ratio_continuous`` returns them) and −ln E_x[M] interpolated multilinearly along the path, the coordinates
@@ -177,6 +190,15 @@ def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, 
     step_offset: the run's steps are numbered step_offset + 1 …, so that a run continued from ``final_state`` with
     step_offset = the steps already taken draws the random numbers the longer run would have drawn.
 
+    kappa: None, or the leverage of a claim on G_c^κ, which adds the series
+
+        rd_t = κ dc_t + ln(1 + v̂(x_t)) − ln v̂(x_{t−1}),  xd_t = rd_t − rf_t,  pd_t = ln v̂(x_t)
+
+    with v̂ the interpolant of the claim's price–dividend ratio v on the grid: ``claim_prices_continuous(...)["pd"]`` on the
+    same operator at ``rtol`` (ValueError "no finite price" when r(K) ≥ 1), or the grid function ``pd`` (positive; no
+    solve is run).  With a claim the slope is that of xd_t on pd_{t−1}, the result has the nine series of ``SERIES_KAPPA``
+    and "pd" = v on the grid; the six base series keep the bits of the run without a claim.  DESIGN §4.18.
+
     Returns the dict of ``simulate`` ("series", "per_path", "summary", "pooled") for dc, m, rf, rc, xc, wc (slope: xc_t
     on ln(ŵ(x_{t−1}) − 1)) and "clamped" = {"per_path": share of the recorded steps whose x_t lay outside the grid on
     some axis, "summary"}, "final_state" (P, D), "E_M" on the grid, and with ``return_paths`` "paths" = {"state":
@@ -185,17 +207,24 @@ def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, 
     its start and the model.  DESIGN §4.14."""
     import torch
     _, nd, grids, shapes = _cont_grids(model, grids, w_star)
-    P, T, B, off, sd, _, _ = _path_request(shapes, n_paths, n_periods, burn_in, seed, path_offset, "stationary", 1e-10,
-                                           return_paths)
+    P, T, B, off, sd, rtol, _ = _path_request(shapes, n_paths, n_periods, burn_in, seed, path_offset, "stationary", rtol,
+                                              return_paths, check_kappa=lambda: kappa is None or _kappa(kappa))
+    k = None if kappa is None else _kappa(kappa)
+    if pd is not None:
+        _cont_pd(pd, k, shapes)
     s0 = _count(step_offset, "step_offset", 0, (1 << 32) - 1)
     if s0 + B + T >= 1 << 32:
         raise ValueError(f"step_offset + burn_in + n_periods = {s0 + B + T} >= 2^32: step numbers are 32-bit")
     start = _cont_start(start, nd, P)
     d = _cont_operator_or_d(model, grids, shapes, operator, d)
     _check_w_star(w_star)
-    ns = len(SERIES)
+    names = SERIES_KAPPA if k is not None else SERIES
+    ns = len(names)
     N = int(np.prod(shapes))
-    need = N * (CONT_REC_BYTES + 16) + (3 * ns + 1) * P * 8 + P * 4 + 2 * P * nd * 8
+    # the records, w and E_M (with a claim also v, and the six work grids of its solve), the statistics, clamped, the
+    # final states and a start per path
+    grid_bytes = CONT_REC_BYTES + 16 if k is None else CONT_CLAIM_REC_BYTES + 24 + (48 if pd is None else 0)
+    need = N * grid_bytes + (3 * ns + 1) * P * 8 + P * 4 + 2 * P * nd * 8
     if return_paths:
         need += P * T * ns * 8 + P * (T + 1) * nd * 8
     devno = operator.device if operator is not None else int(device)
@@ -207,7 +236,11 @@ def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, 
     op = _cont_operator(model, grids, operator, d, devno)
     w = _device_grid(op, w_star, "w_star")
     em = torch.empty_like(w)
-    rec = torch.empty((N, 2), dtype=torch.float64, device=dev)
+    v = None
+    if k is not None:
+        v = _device_grid(op, pd, "pd") if pd is not None else \
+            _device_grid(op, _claim_prices(op, w, model.θ, model.γ, k, rtol, _Fence(op))["pd"], "pd")
+    rec = torch.empty((N, 2 if k is None else 4), dtype=torch.float64, device=dev)
     stats = torch.empty((3 * ns + 1, P), dtype=torch.float64, device=dev)
     clamped = torch.empty((P,), dtype=torch.int32, device=dev)
     final = torch.empty((P, nd), dtype=torch.float64, device=dev)
@@ -219,19 +252,26 @@ def simulate_continuous(model, grids, w_star, n_paths, n_periods, *, burn_in=0, 
         ser = torch.empty((ns, P, T), dtype=torch.float64, device=dev)
     _Fence(op).before_library()
     op.cont_sdf_mean_dev(w.data_ptr(), em.data_ptr())
-    op.cont_sim_records_dev(w.data_ptr(), em.data_ptr(), rec.data_ptr())
-    op.cont_sim_paths_dev(rec.data_ptr(), sd, off, P, B, T, stats.data_ptr(), clamped.data_ptr(), final.data_ptr(),
-                          step_offset=s0, start=start if start is not None and start.ndim == 1 else None,
-                          start_ptr=start_dev.data_ptr() if start_dev is not None else None,
-                          states_ptr=states.data_ptr() if states is not None else None,
-                          series_ptr=ser.data_ptr() if ser is not None else None)
+    kw = dict(step_offset=s0, start=start if start is not None and start.ndim == 1 else None,
+              start_ptr=start_dev.data_ptr() if start_dev is not None else None,
+              states_ptr=states.data_ptr() if states is not None else None,
+              series_ptr=ser.data_ptr() if ser is not None else None)
+    if k is None:
+        op.cont_sim_records_dev(w.data_ptr(), em.data_ptr(), rec.data_ptr())
+        op.cont_sim_paths_dev(rec.data_ptr(), sd, off, P, B, T, stats.data_ptr(), clamped.data_ptr(), final.data_ptr(), **kw)
+    else:
+        op.cont_sim_claim_records_dev(w.data_ptr(), em.data_ptr(), v.data_ptr(), rec.data_ptr())
+        op.cont_sim_claim_paths_dev(rec.data_ptr(), k, sd, off, P, B, T, stats.data_ptr(), clamped.data_ptr(),
+                                    final.data_ptr(), **kw)
     op.synchronize()
     share = clamped.cpu().numpy().astype(np.float64) / T
-    out = _result(SERIES, stats.cpu().numpy(), P)
+    out = _result(names, stats.cpu().numpy(), P)
     out.update({"clamped": {"per_path": share, "summary": _summary(share)}, "final_state": final.cpu().numpy(),
                 "E_M": em.cpu().numpy()})
+    if k is not None:
+        out["pd"] = v.cpu().numpy()
     if return_paths:
-        out["paths"] = _named_paths({"state": states.cpu().numpy()}, SERIES, ser.cpu().numpy())
+        out["paths"] = _named_paths({"state": states.cpu().numpy()}, names, ser.cpu().numpy())
     del rec
     return out
 
