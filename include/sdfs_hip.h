@@ -235,6 +235,25 @@ int sdfs_apply_tilted_dev(sdfs_handle* h, const double* f_dev, double* out_dev);
  * ignored: fp64).  SDFS_ERR_NUMERIC for a breakdown or a solve that stops above the tolerance. */
 int sdfs_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const double* rhs_dev, double* x_dev,
                           int64_t* n_iter, double* final_rel_resid);
+/* out = d(K f): the tangent of the tilt set by sdfs_set_tilt_dev along a direction that moves the
+ * parameters and state arrays (dparams, darrays: HOST, as sdfs_param_tangent_dev; dgen: per-axis left generators
+ * dQ = G Q or NULL, as sdfs_param_tangent_gen_dev), the tilt's exponents (dkappa_lam, dkappa_c), the linearisation point
+ * w by dw_dev and T w by dtw_dev (the total movement of T w; at a fixed point with dw = dw* / dp it is dw* too, and the
+ * two may be one pointer), and f by df_dev:
+ *   d(K f) = u2 .* K f + K (u1 .* f + df) + sum_k R .* (G_k along axis k on (K f / R)),
+ *   u1 = p (dtheta ln w + (theta-1) dw / w) + dkappa_lam h_lam + kappa_lam dh_lam,
+ *   u2 = p (theta dbeta / beta + dtheta ln beta - dtheta ln(Tw - 1) + (1-theta) dTw / (Tw - 1)) + kappa_c dkappa_c sigma_c^2
+ *        + kappa_c^2 sigma_c dsigma_c + dkappa_c (mu_c + z) + kappa_c (dmu_c + dz).
+ * w_dev is the w of the set_tilt; w_dev, dw_dev, dtw_dev are read for sdf_power >= 1 only (NULL then: SDFS_ERR_ARG) and
+ * may be NULL for power 0.  f_dev NULL: f = 1; df_dev NULL: df = 0; kf_dev: K f where the caller has it, NULL: one more
+ * product computes it.  out_dev is distinct from every input.  One tilted product per call (two with kf_dev NULL), two
+ * streaming passes and one per axis with a generator; two runs give identical bits.  SDFS_ERR_ARG before a set_tilt or
+ * for a non-finite exponent tangent; SDFS_ERR_UNSUPPORTED for a non-zero transition-array tangent in darrays (state it
+ * as dgen) and for a generator on a handle with a conditional transition tensor. */
+int sdfs_tilt_tangent_dev(sdfs_handle* h, const double* w_dev, const double* dw_dev, const double* dtw_dev,
+                          const double* dparams, const double* const* darrays, const double* const* dgen,
+                          double dkappa_lam, double dkappa_c, const double* f_dev, const double* df_dev,
+                          const double* kf_dev, double* out_dev);
 /* P_0 = 1, P_n = K P_{n-1} for n = 1 ... n_max on the device, no host synchronisation per horizon.  Row n-1 of out_host
  * (n_max x 4) = <g, P_n>, <g, -log P_n> / n, min and max of P_n / P_{n-1} over the grid (the Collatz-Wielandt bracket of
  * the spectral radius of K), with product-form weights g(x) = prod_a weight_axes[a][x_a] (HOST pointers, shapes[a]

@@ -29,8 +29,8 @@ from .sensitivity import (discretize_ssy_tangent, discretize_gcy_tangent, wc_rat
                           discretize_gcy_persistence_tangent, SSY_PERSISTENCE, GCY_PERSISTENCE,
                           adjoint_moments_to_gradient, wc_ratio_sensitivities_continuous, wc_ratio_gradient_continuous,
                           SSY_PARAMS, GCY_PARAMS)
-from .pricing import (stationary_weights, sdf_moments, term_structure, claim_prices, sdf_moments_continuous,
-                      term_structure_continuous, claim_prices_continuous)
+from .pricing import (stationary_weights, sdf_moments, term_structure, claim_prices, price_sensitivities,
+                      sdf_moments_continuous, term_structure_continuous, claim_prices_continuous)
 from .simulation import simulate, simulate_continuous
 from .batch import (BatchOperator, BatchResult, solve_batch, batch_lds_bytes, BatchGradient, gradient_batch, BatchPrices,
                     price_batch, price_words_to_stats, BatchSimulation, simulate_batch, batch_sim_lds_bytes,
@@ -52,7 +52,7 @@ __all__ = ["SSY", "GCY", "rouwenhorst", "tauchen", "discretize_ssy", "discretize
            "SSY_PERSISTENCE", "GCY_PERSISTENCE", "adjoint_moments_to_gradient",
            "wc_ratio_sensitivities_continuous", "wc_ratio_gradient_continuous", "SSY_PARAMS", "GCY_PARAMS",
            "stationary_weights", "sdf_moments", "term_structure", "claim_prices", "simulate", "simulate_continuous",
-           "sdf_moments_continuous", "term_structure_continuous", "claim_prices_continuous",
+           "sdf_moments_continuous", "term_structure_continuous", "claim_prices_continuous", "price_sensitivities",
            "BatchOperator", "BatchResult", "solve_batch", "batch_lds_bytes", "BatchGradient", "gradient_batch", "BatchPrices", "price_batch", "price_words_to_stats",
            "BatchSimulation", "simulate_batch", "batch_sim_lds_bytes", "batch_cdf_tables", "batch_sim_tables",
            "SdfsError", "LIB_PATH"]

@@ -104,7 +104,8 @@ SYMBOLS = {
     "sdfs_set_tilt_dev": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double]),
     "sdfs_apply_tilted_dev": (C.c_int, [_P, _P, _P]),
     "sdfs_solve_tilted_dev": (C.c_int, [_P, C.POINTER(sdfs_opts), _P, _P, _I64, _D]),
-    "sdfs_tilted_horizons_dev": (C.c_int, [_P, C.c_int64, C.POINTER(_D), C.c_int64, C.POINTER(C.c_int64), C.POINTER(_P), _D]),
+    "sdfs_tilt_tangent_dev": (C.c_int, [_P, _P, _P, _P, _D, C.POINTER(_D), C.POINTER(_D), C.c_double, C.c_double, _P, _P, _P, _P]),
+    "sdfs_tilted_horizons_dev":(C.c_int, [_P, C.c_int64, C.POINTER(_D), C.c_int64, C.POINTER(C.c_int64), C.POINTER(_P), _D]),
     "sdfs_sim_records_dev": (C.c_int, [_P, _P, _P, _P]),
     "sdfs_sim_paths_dev": (C.c_int, [_P, _P, C.POINTER(sdfs_sim_desc), _P, _P, _P]),
     "sdfs_cont_sdf_mean_dev": (C.c_int, [_P, _P, _P]),

@@ -34,6 +34,7 @@
 #include "krylov_kernels.hpp"
 #include "sens_kernels.hpp"
 #include "price_kernels.hpp"
+#include "price_sens.hpp"
 #include "sim_kernels.hpp"
 #include "sim_host.hpp"
 #include "batch_kernels.hpp"
@@ -207,6 +208,13 @@ struct sdfs_handle {
     double* pa = nullptr; double* pb = nullptr;               // P_n ping-pong of the horizon loop
     double* part = nullptr;                                   // per-workgroup partials of one horizon
     double* res = nullptr; long long res_cap = 0;             // PRICE_NSUM doubles per horizon
+    // the tilt's tangent (sdfs_tilt_tangent_dev)
+    double kappa_lam = 0, kappa_c = 0;                        // the exponents the scalings were built with
+    double* tw = nullptr;                                     // T w of the tilt's linearisation (power >= 1)
+    double* tv = nullptr; double* kf = nullptr;               // the product's direction u1 f + df; K f when the caller has none
+    std::vector<double> tz_host;                              // staging of the a3-shaped table of u2 (kept alive across the async copy)
+    double* tz = nullptr;                                     // device copy
+    double* zt = nullptr;                                     // mu_c + z in the a3 layout (k_tilt_tangent_generator), built on first use
   } price;
 
   // simulated paths (sdfs_sim_records_dev / sdfs_sim_paths_dev)
@@ -3549,8 +3557,9 @@ int sdfs_set_tilt_dev(sdfs_handle* h, const double* w, int sdf_power, double kap
   }
   if (w) {
     // linearise at w in fp64: c1 = w^(theta-1), c2 = beta^theta (Tw - 1)^(1-theta) (replaces the cached linearisation)
-    if ((rc = ensure_buf(h, &h->hostio3))) return rc;
-    if ((rc = apply(h, Apply(MODE_T_LIN, w, h->hostio3, w)))) return rc;
+    // (T w stays in the tilt's own buffer: sdfs_tilt_tangent_dev reads it)
+    if ((rc = ensure_buf(h, &Pr.tw))) return rc;
+    if ((rc = apply(h, Apply(MODE_T_LIN, w, Pr.tw, w)))) return rc;
     h->lin_stale = false;
   }
   const PriceGeom g = price_geom(h);
@@ -3566,6 +3575,7 @@ int sdfs_set_tilt_dev(sdfs_handle* h, const double* w, int sdf_power, double kap
                           g, el, ec, ez, sdf_power ? (const double*)h->c1 : nullptr, sdf_power ? (const double*)h->c2 : nullptr, Pr.d1, Pr.d2)))
     return rc;
   Pr.power = sdf_power;
+  Pr.kappa_lam = kappa_lam; Pr.kappa_c = kappa_c;
   return 0;
 }
 
@@ -3583,6 +3593,144 @@ int sdfs_solve_tilted_dev(sdfs_handle* h, const sdfs_opts* opts, const double* r
   int rc = check(h); if (rc) return rc;
   if ((rc = price_handle_ok(h, "sdfs_solve_tilted_dev", true))) return rc;
   return tilted_solve(h, opts, rhs, x, n_iter, final_rel_resid, h->price.d1, h->price.d2, "tilted");
+}
+
+int sdfs_tilt_tangent_dev(sdfs_handle* h, const double* w, const double* dw, const double* dtw, const double* dparams,
+                          const double* const* darrays, const double* const* dgen, double dkappa_lam, double dkappa_c,
+                          const double* f, const double* df, const double* kf, double* out) {
+  int rc = check(h); if (rc) return rc;
+  if ((rc = price_handle_ok(h, "sdfs_tilt_tangent_dev", true))) return rc;
+  if (!dparams || !out) return fail(h, SDFS_ERR_ARG, "NULL argument");
+  auto& S = h->sens;
+  auto& Pr = h->price;
+  const int P = Pr.power;
+  if (P >= 1 && (!w || !dw || !dtw))
+    return fail(h, SDFS_ERR_ARG, "sdf_power = %d needs w, its direction dw and the direction dtw of T w", P);
+  if (!std::isfinite(dkappa_lam) || !std::isfinite(dkappa_c)) return fail(h, SDFS_ERR_ARG, "non-finite tilt exponent tangent");
+  if (out == kf || out == f || out == df || (P >= 1 && (out == w || out == dw || out == dtw)))
+    return fail(h, SDFS_ERR_ARG, "out must be distinct from every input grid");
+  auto darr = [&](int i) -> const double* { return darrays ? darrays[i] : nullptr; };
+  for (int i : S.trans) {
+    const double* d = darr(i);
+    if (!d) continue;
+    for (long long k = 0; k < S.sizes[i]; ++k)
+      if (d[k] != 0.0) return fail(h, SDFS_ERR_UNSUPPORTED, "arrays[%d] is a transition array: its tangent must be zero "
+                                   "(a persistence parameter states dQ = G Q through dgen)", i);
+  }
+  bool any_gen = false;
+  if (dgen) {
+    for (int a = 0; a < h->ndim; ++a) {
+      if (!dgen[a]) continue;
+      any_gen = true;
+      for (int k = 1; k < 3 * h->shape[a] - 1; ++k)                // sub[0], super[n - 1]: ignored
+        if (!std::isfinite(dgen[a][k])) return fail(h, SDFS_ERR_ARG, "dgen[%d][%d] is not finite", a, k);
+    }
+  }
+  if (any_gen)
+    for (int a = 0; a < h->ndim; ++a)
+      if (h->ax[a].qcount != 1)
+        return fail(h, SDFS_ERR_UNSUPPORTED, "a generator tangent needs unconditional transition tensors "
+                                             "(axis %s is conditional)", h->ax[a].name);
+  // the direction's scalars and tables (sens_tables reads the same places of dparams / darrays)
+  const double th = h->theta, psi = S.psi, kl = Pr.kappa_lam, kc = Pr.kappa_c;
+  const double dg = dparams[S.ip_gamma], dpsi = dparams[S.ip_psi], dmu = dparams[S.ip_mu_c], dbeta = dparams[S.ip_beta];
+  const double dtheta = -dg / (1.0 - 1.0 / psi) - dpsi * th / (psi * (psi - 1.0));
+  const double* dhl = darr(S.ia_hlam);
+  const double* dsc = darr(S.ia_sigc);
+  const double* dz = darr(S.ia_z);
+  SensTab ul, uc;
+  for (int i = 0; i < SENS_MAXN; ++i) { ul.t[i] = 0.0; uc.t[i] = 0.0; }
+  for (size_t l = 0; l < S.hlam.size(); ++l) ul.t[l] = dkappa_lam * S.hlam[l] + kl * (dhl ? dhl[l] : 0.0);
+  for (size_t k = 0; k < S.sigc.size(); ++k)
+    uc.t[k] = kc * S.sigc[k] * (dkappa_c * S.sigc[k] + kc * (dsc ? dsc[k] : 0.0));
+  const double c0 = P * (th * dbeta / h->beta + dtheta * std::log(h->beta));
+  bool any_tz = dkappa_c != 0.0 || kc * dmu != 0.0;
+  if (dz && kc != 0.0) for (size_t i = 0; i < S.z.size() && !any_tz; ++i) any_tz = dz[i] != 0.0;
+  if ((rc = ensure_buf(h, &Pr.tv))) return rc;
+  if (any_tz) {
+    if (!Pr.tz && (rc = dev_alloc(h, &Pr.tz, S.z.size()))) return rc;
+    // (the previous call's epilogue may still read the table; its staging copy may still be in flight)
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    Pr.tz_host.resize(S.z.size());
+    for (size_t i = 0; i < S.z.size(); ++i) Pr.tz_host[i] = dkappa_c * (S.mu_c + S.z[i]) + kc * (dmu + (dz ? dz[i] : 0.0));
+    HIPCHK(h, hipMemcpyAsync(Pr.tz, Pr.tz_host.data(), sizeof(double) * S.z.size(), hipMemcpyHostToDevice, h->stream));
+  }
+  if (any_gen && kc != 0.0 && !Pr.zt) {
+    std::vector<double> zt(S.z.size());
+    for (size_t i = 0; i < zt.size(); ++i) zt[i] = S.mu_c + S.z[i];
+    if ((rc = upload(h, &Pr.zt, zt.data(), zt.size()))) return rc;
+  }
+  const PriceGeom g = price_geom(h);
+  const int grid = price_grid(h);
+  const double n8 = 8.0 * (double)h->N;
+  if (!kf) {                                             // K f by one more product (f = 1: a grid of ones first)
+    if ((rc = ensure_buf(h, &Pr.kf))) return rc;
+    if (out == Pr.kf) return fail(h, SDFS_ERR_ARG, "out must be distinct from every input grid");
+    const double* src = f;
+    if (!src) {
+      hipLaunchKernelGGL(k_price_fill, dim3(stream_grid(h, h->N, PRICE_BLOCK)), dim3(PRICE_BLOCK), 0, h->stream, Pr.tv, h->N, 1.0);
+      HIPCHK(h, hipGetLastError());
+      src = Pr.tv;
+    }
+    Apply a(MODE_JVP, src, Pr.kf, src);
+    a.lc1 = Pr.d1; a.lc2 = Pr.d2;
+    if ((rc = apply(h, a))) return rc;
+    kf = Pr.kf;
+  }
+  const double* tz = any_tz ? (const double*)Pr.tz : nullptr;
+  // the logarithms only where dtheta moves an exponent of w or of T w - 1
+  const bool lg = P >= 1 && dtheta != 0.0;
+  auto pro = k_tilt_tangent_prologue<0, false>;
+  auto epi = k_tilt_tangent_epilogue<0, false>;
+  if (P == 1) { pro = lg ? k_tilt_tangent_prologue<1, true> : k_tilt_tangent_prologue<1, false>;
+                epi = lg ? k_tilt_tangent_epilogue<1, true> : k_tilt_tangent_epilogue<1, false>; }
+  if (P == 2) { pro = lg ? k_tilt_tangent_prologue<2, true> : k_tilt_tangent_prologue<2, false>;
+                epi = lg ? k_tilt_tangent_epilogue<2, true> : k_tilt_tangent_epilogue<2, false>; }
+  const double pthm1 = P * (th - 1.0), p1mth = P * (1.0 - th), pdth = P * dtheta;
+  // counter names carry the number of grids a pass streams (the bytes of a name are set once, at its first launch)
+  const int n_pro = 1 + (f ? 1 : 0) + (df ? 1 : 0) + (P ? 2 : 0), n_epi = 3 + (P ? 2 : 0), n_gen = 3 + (P ? 1 : 0);
+  char nm_pro[32], nm_epi[32], nm_gen[32];
+  snprintf(nm_pro, sizeof nm_pro, "price:dtilt_pro%d%s", n_pro, lg ? "_log" : "");
+  snprintf(nm_epi, sizeof nm_epi, "price:dtilt_epi%d%s", n_epi, lg ? "_log" : "");
+  snprintf(nm_gen, sizeof nm_gen, "price:dtilt_gen%d", n_gen);
+  if ((rc = launch_kernel(h, pro, dim3(grid), dim3(PRICE_BLOCK), 0, Counter(nm_pro, n_pro * n8, 0),
+                          g, ul, pthm1, pdth, w, dw, f, df, Pr.tv)))
+    return rc;
+  {
+    Apply a(MODE_JVP, Pr.tv, out, Pr.tv);
+    a.lc1 = Pr.d1; a.lc2 = Pr.d2;
+    if ((rc = apply(h, a))) return rc;
+  }
+  if ((rc = launch_kernel(h, epi, dim3(grid), dim3(PRICE_BLOCK), 0,
+                          Counter(nm_epi, n_epi * n8, 0), g, uc, c0, p1mth, pdth, tz,
+                          (const double*)Pr.tw, dtw, kf, (const double*)out, out)))
+    return rc;
+  if (any_gen) {
+    SensTab qc;
+    for (int i = 0; i < SENS_MAXN; ++i) qc.t[i] = 0.0;
+    for (size_t k = 0; k < S.sigc.size(); ++k) qc.t[k] = 0.5 * kc * kc * S.sigc[k] * S.sigc[k];
+    auto fn = k_tilt_tangent_generator<0>;
+    if (P == 1) fn = k_tilt_tangent_generator<1>;
+    else if (P == 2) fn = k_tilt_tangent_generator<2>;
+    for (int a = 0; a < h->ndim; ++a) {
+      if (!dgen[a]) continue;
+      const int n = h->shape[a];
+      SensGen G;
+      memset(&G, 0, sizeof G);
+      for (int i = 0; i < n; ++i) {
+        G.sub[i] = i > 0 ? dgen[a][i] : 0.0;
+        G.diag[i] = dgen[a][n + i];
+        G.sup[i] = i < n - 1 ? dgen[a][2 * n + i] : 0.0;
+      }
+      unsigned inner = 1;
+      for (int b = h->ndim - 1; b > a; --b) inner *= (unsigned)h->shape[b];
+      // K f, out (and T w) read, out written; the two neighbours along the axis come from lines the sweep fetches anyway
+      if ((rc = launch_kernel(h, fn, dim3(grid), dim3(PRICE_BLOCK), 0, Counter(nm_gen, n_gen * n8, 0), g, G, qc, a,
+                              inner, p1mth, kc, (const double*)Pr.tw, kc != 0.0 ? (const double*)Pr.zt : nullptr, kf, out)))
+        return rc;
+    }
+  }
+  return 0;
 }
 
 int sdfs_tilted_horizons_dev(sdfs_handle* h, int64_t n_max, const double* const* weight_axes, int64_t n_save,

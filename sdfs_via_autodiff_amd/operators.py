@@ -263,6 +263,23 @@ class KoopmansOperator:
               self._h)
         return it.value, rel.value
 
+    def tilt_tangent_dev(self, w_ptr, dw_ptr, dtw_ptr, dparams, darrays, dgen, dkappa_lam, dkappa_c, f_ptr, df_ptr, kf_ptr,
+                         out_ptr):
+        """out = d(K f), the tangent of the tilt last set (sdfs_tilt_tangent_dev): along (dparams, darrays, dgen) as in
+        ``param_tangent_dev``, the tilt's exponents by (dkappa_lam, dkappa_c), w by dw, T w by dtw (its total movement; dw
+        and dtw may be one grid) and f by df.  w_ptr: the w of the ``set_tilt_dev``; w, dw, dtw may be None for
+        sdf_power 0.  f_ptr None: f = 1; df_ptr None: df = 0; kf_ptr: K f, None to have it computed."""
+        dp = self._dparams(dparams)
+        gptrs, gkeep = (None, None) if dgen is None else self._dgen(dgen)
+        if dgen is not None and darrays is not None:       # (the transition entries are what the generators state)
+            layout = LAYOUT.get(getattr(self, "model_name", None))
+            trans = layout.transitions if layout else ()
+            darrays = [None if i in trans else d for i, d in enumerate(darrays)]
+        ptrs, keep = self._darrays(darrays)
+        check(lib.sdfs_tilt_tangent_dev(self._h, w_ptr, dw_ptr, dtw_ptr, dp, ptrs, gptrs, float(dkappa_lam), float(dkappa_c),
+                                        f_ptr, df_ptr, kf_ptr, out_ptr), self._h)
+        del keep, gkeep
+
     def tilted_horizons_dev(self, n_max, weight_axes=None, save_at=(), save_ptrs=()):
         """P_n = K P_{n-1}, P_0 = 1, for n = 1 ... n_max on the device (sdfs_tilted_horizons_dev).  weight_axes: one
         host vector per axis (product-form weights; None = uniform).  P_n lands in save_ptrs[j] at n = save_at[j].

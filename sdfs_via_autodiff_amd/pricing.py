@@ -27,7 +27,8 @@ import numpy as np
 
 from ._requests import (_shapes, _check_grid, _kappa, _check_n_max, _check_save, _check_rtol, _check_w_star, _weights,
                         _cont_grids, _cont_operator_or_d, _operator, _cont_operator, _device_grid, _Fence,
-                        stationary_weights)
+                        _check_tolerance, LAYOUT, stationary_weights)
+from .sensitivity import _check, _directions
 from ._lib import SdfsError, SDFS_ERR_NUMERIC
 
 
@@ -133,6 +134,122 @@ def claim_prices(model, shapes, w_star, kappa, rtol=1e-10):
     return _claim_prices(op, _device_grid(op, w_star, "w_star"), model.θ, model.γ, k, rtol, _Fence())
 
 
+def price_sensitivities(model, shapes, w_star, kappa=None, wrt=None, rtol=1e-10, atol=0.0, persistence=False, dw=None):
+    """Parameter sensitivities of the prices at a converged fixed point ``w_star``:
+    {name: {"E_M", "log_rf", "max_sharpe"[, "pd", "expected_return", "log_premium"]}}, each the derivative of that field
+    of ``sdf_moments`` / ``claim_prices(kappa)`` with respect to the parameter (host arrays of the grid's shape;
+    "max_sharpe" is NaN where the bound is zero), plus ``"_info": {name: (iterations of the dw* solve or None, iterations
+    of the dv solve or None)}``.  ``kappa=None``: the SDF moments only.  ``wrt``, ``persistence``: as in
+    ``wc_ratio_sensitivities``.  ``dw``: the result of a previous ``wc_ratio_sensitivities`` call on the same point, which
+    skips those solves.  rtol / atol: the stopping rule of both solves.
+
+    Per parameter: dw*/dp (one solve of I − J), then the tangent of each tilt along the direction that moves the
+    parameter and w* together (``KoopmansOperator.tilt_tangent_dev``): dE_M = dK(1, θ, −γ)[1], dE_M² = dK(2, 2θ, −2γ)[1],
+    dv = (I − K)⁻¹ dK(1, θ, κ−γ)[1 + v] (one tilted solve), dE_R = (dK(0, 0, κ)[1 + v; dv] − E_R dv) / v.  E_M, E_M², v and
+    E_R are computed once.  The loops run tilt by tilt, so dw*/dp, dE_M / E_M and dv/dp of every requested parameter stay
+    on the device meanwhile: three grids per parameter.  ValueError ("no finite price: r(K) ≥ 1") exactly as ``claim_prices``."""
+    import torch
+    kind, shapes = _shapes(model, shapes)
+    L = LAYOUT[kind]
+    k = None if kappa is None else _kappa(kappa)
+    pers = L.persistence if persistence else ()
+    default = L.params if persistence else L.supported
+    names = default if wrt is None else tuple([wrt] if isinstance(wrt, str) else wrt)
+    for nm in names:                                               # (ValueError before any device work)
+        if nm not in pers:
+            _check(L.params, L.supported, nm, "rouwenhorst", type(model).__name__)
+    rtol, atol = _check_tolerance("rtol", rtol, False), _check_tolerance("atol", atol, True)
+    _check_grid(w_star, shapes, "w_star")
+    if dw is not None:
+        if not isinstance(dw, dict):
+            raise TypeError(f"dw must be the dict wc_ratio_sensitivities returns, not {type(dw).__name__}")
+        for nm in names:
+            if nm not in dw:
+                raise ValueError(f"dw has no entry for parameter {nm!r}")
+            _check_grid(dw[nm], shapes, f"dw[{nm!r}]")
+    op, arr = _operator(model, shapes)
+    dirs = _directions(model, shapes, names, arr, persistence)
+    w = _device_grid(op, w_star, "w_star")
+    θ, γ = model.θ, model.γ
+    (_, ig, ips, _), _, _ = L.moments
+    ψ = model.params[ips]
+    dθ = [-dp[ig] / (1.0 - 1.0 / ψ) - dp[ips] * θ / (ψ * (ψ - 1.0)) for dp, _, _ in dirs]
+    dγ = [dp[ig] for dp, _, _ in dirs]
+    rhs, tmp = torch.empty_like(w), torch.empty_like(w)
+    it_w, it_v = {}, {}
+
+    # dw*/dp (the tangents leave the cached linearisation at w*, which every tilt below restates)
+    dws = []
+    for nm, (dp, da, dg) in zip(names, dirs):
+        if dw is not None:
+            dws.append(_device_grid(op, dw[nm], f"dw[{nm!r}]"))
+            it_w[nm] = None
+            continue
+        x = torch.empty_like(w)
+        op.param_tangent_dev(w.data_ptr(), dp, da, rhs.data_ptr(), tmp.data_ptr(), dgen=dg)
+        it_w[nm] = op.solve_linear_dev(rhs.data_ptr(), x.data_ptr(), False, rtol, atol)[0]
+        dws.append(x)
+
+    def tangent(j, dkl, dkc, f, df, kf, out):
+        dp, da, dg = dirs[j]
+        x = dws[j].data_ptr()
+        op.tilt_tangent_dev(w.data_ptr(), x, x, dp, da, dg, dkl, dkc, f, df, kf.data_ptr(), out.data_ptr())
+
+    # The fields are formed on the device (the library launches on torch's current stream); what crosses to the host is
+    # the result alone.  rel[j] = dE_M / E_M stays for the Sharpe bound and the premium.
+    out = {nm: {} for nm in names}
+    one = torch.ones_like(w)
+    em, em2 = torch.empty_like(w), torch.empty_like(w)
+    op.set_tilt_dev(w.data_ptr(), 1, θ, -γ)
+    op.apply_tilted_dev(one.data_ptr(), em.data_ptr())
+    rel = []
+    for j, nm in enumerate(names):
+        tangent(j, dθ[j], -dγ[j], None, None, em, tmp)
+        out[nm]["E_M"] = tmp.cpu().numpy()
+        rel.append(tmp / em)
+        out[nm]["log_rf"] = (-rel[j]).cpu().numpy()
+    op.set_tilt_dev(w.data_ptr(), 2, 2.0 * θ, -2.0 * γ)
+    op.apply_tilted_dev(one.data_ptr(), em2.data_ptr())
+    q = em2 / (em * em)
+    s = torch.sqrt(torch.clamp(q - 1.0, min=0.0))
+    q.div_(2.0 * s)                                                   # (inf where the bound is zero: NaN below)
+    for j, nm in enumerate(names):
+        tangent(j, 2.0 * dθ[j], -2.0 * dγ[j], None, None, em2, tmp)
+        ms = q * (tmp / em2 - 2.0 * rel[j])
+        out[nm]["max_sharpe"] = torch.where(s > 0.0, ms, torch.full_like(ms, float("nan"))).cpu().numpy()
+    del em, em2, q, s
+    if k is not None:
+        v, num, er = torch.empty_like(w), torch.empty_like(w), torch.empty_like(w)
+        op.set_tilt_dev(w.data_ptr(), 1, θ, k - γ)
+        op.apply_tilted_dev(one.data_ptr(), rhs.data_ptr())
+        try:
+            op.solve_tilted_dev(rhs.data_ptr(), v.data_ptr(), rtol, atol)
+        except SdfsError as e:
+            if _numeric(e):
+                raise ValueError(f"no finite price: r(K) ≥ 1, or (I − K) too close to singular for the solve ({e})") from None
+            raise
+        if not bool(torch.all(v > 0)):
+            raise ValueError("no finite price: r(K) ≥ 1 (the solution of (I − K) v = K·1 is not strictly positive)")
+        torch.add(v, 1.0, out=num)
+        dvs = []
+        for j, nm in enumerate(names):                                 # K(1 + v) = v: no further product for K f
+            tangent(j, dθ[j], -dγ[j], num.data_ptr(), None, v, rhs)
+            dv = torch.empty_like(w)
+            it_v[nm] = op.solve_tilted_dev(rhs.data_ptr(), dv.data_ptr(), rtol, atol)[0]
+            out[nm]["pd"] = dv.cpu().numpy()
+            dvs.append(dv)
+        op.set_tilt_dev(None, 0, 0.0, k)
+        op.apply_tilted_dev(num.data_ptr(), er.data_ptr())
+        E_R = er / v
+        for j, nm in enumerate(names):
+            tangent(j, 0.0, 0.0, num.data_ptr(), dvs[j].data_ptr(), er, tmp)
+            dER = (tmp - E_R * dvs[j]) / v
+            out[nm]["expected_return"] = dER.cpu().numpy()
+            out[nm]["log_premium"] = (dER / E_R + rel[j]).cpu().numpy()
+    out["_info"] = {nm: (it_w[nm], it_v.get(nm)) for nm in names}
+    return out
+
+
 # -- the continuous-state model (DESIGN §4.15) -----------------------------------------------------------------------
 #
 # K(p, κ_λ, κ_c) f (x) = d2(x) · Σ_m W_m exp(κ_λ s_λ η_0m) · ŵ(x'_m)^(p(θ−1)) · f̂(x'_m) with the operator's nodes and
@@ -207,5 +324,5 @@ def claim_prices_continuous(model, grids, w_star, kappa, *, rtol=1e-10, operator
     return _claim_prices(op, _device_grid(op, w_star, "w_star"), model.θ, model.γ, k, rtol, _Fence(op))
 
 
-__all__ = ["stationary_weights", "sdf_moments", "term_structure", "claim_prices", "sdf_moments_continuous",
+__all__ = ["stationary_weights", "sdf_moments", "term_structure", "claim_prices", "price_sensitivities", "sdf_moments_continuous",
            "term_structure_continuous", "claim_prices_continuous"]
