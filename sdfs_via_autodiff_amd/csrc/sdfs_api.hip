@@ -140,6 +140,9 @@ struct Knobs {
                                // default (-1): fused on the small-grid plan, one launch per pass on the 6-D pair plan
 };
 
+// What the launches of the batched-Gram Anderson form are told about a run (anderson_host.hpp)
+struct AndRun { long long n = 0; int m = 0, mixing_freq = 1; double tol = 0, max_iter = 0, beta = 0, ridge = 0; AndPtrs hp; };
+
 }  // namespace
 
 struct sdfs_handle {
@@ -164,17 +167,6 @@ struct sdfs_handle {
   FastPlan fast;                      // pair plan of the full grid, when the model admits it
   FastPlan sfast[2];                  // sharded handle: the two stages on the pair plan's kernels (build_stage_fast_plans)
   unsigned* sched = nullptr;          // tile tickets of the persistent line passes (SCHED_WORDS per pass, zero between launches)
-  AndState* and_state = nullptr;      // device-resident Anderson loop: state (two buffers: the fused small-grid form alternates), per-chunk record of its passes
-  AndState* and_state_host = nullptr;
-  double* and_gram_partial = nullptr; // large grids: partial sums of the whole Gram matrix (k_and_gram_full)
-  unsigned* and_flag = nullptr;       // fused form: per pass of a chunk, set by a push that met a non-finite residual
-  double* and_err = nullptr; int* and_kind = nullptr; int and_slots = 0;
-  // distributed Anderson (sdfs_anderson_begin / _step): history in caller-owned buffers, control state in and_state
-  struct { bool on = false; long long n = 0; int m = 0, mixing_freq = 1; double tol = 0, max_iter = 0, beta = 0, ridge = 0; AndPtrs hp; } dand;
-  double* and_err_host = nullptr; int* and_kind_host = nullptr;
-  hipGraphExec_t and_graph = nullptr;
-  int and_graph_chunk = 0, and_graph_m = 0, and_graph_freq = 0;
-  double and_graph_key[4] = {0, 0, 0, 0};   // tol, max_iter, beta, ridge: baked into the captured kernel arguments
   double* sa_ring = nullptr;          // small-grid SA: per-workgroup residual maxima of the last two iterations [2][SA_RING]
   std::vector<void*> misc_allocs;     // device index tables of the pair plan
   bool sharded = false;
@@ -225,6 +217,25 @@ struct sdfs_handle {
     std::vector<double> tab_host;                             // its staging (kept alive across the async copy)
   } sim;
 
+  // Anderson acceleration (anderson_host.hpp; `and` itself is an operator name in C++)
+  struct {
+    AndState* state = nullptr;                                // device-resident loops: control state (two buffers: the fused small-grid form alternates)
+    AndState* state_host = nullptr;                           // pinned mirror of the one a chunk ends on
+    double* gram_partial = nullptr;                           // large grids: partial sums of the whole Gram matrix (k_and_gram_full)
+    double* err = nullptr; int* kind = nullptr;               // per pass of a chunk: its error and its step kind (1: the error belongs in the trace)
+    unsigned* flag = nullptr;                                 // fused form, per pass of a chunk: set by a push that met a non-finite residual
+    int slots = 0;                                            // passes that err / kind / flag and the two mirrors hold
+    double* err_host = nullptr; int* kind_host = nullptr;     // pinned mirrors
+    hipGraphExec_t graph = nullptr;                           // one captured chunk, and what it was captured for:
+    int graph_chunk = 0, graph_m = 0, graph_freq = 0;
+    double graph_key[4] = {0, 0, 0, 0};                       // tol, max_iter, beta, ridge: baked into the captured kernel arguments
+    std::vector<double*> X, R;                                // history of the solve loops (and_history), grown on demand
+    double* gram_row = nullptr;                               // host-controlled loop: the Gram row of the pass
+    double* gram_row_host = nullptr;                          // pinned mirror
+    // sharded step API (sdfs_anderson_begin / _step): history in caller-owned buffers, control state in `state`
+    struct : AndRun { bool on = false; } dand;
+  } anderson;
+
   std::vector<double> a3_host;       // host copy of the a3 table (the pair plan looks for its two-table form)
   // sharded handles: the stage settings of sdfs_set_krylov_f32 / sdfs_set_t_f32 (sdfs_apply_stage_gated_dev's requests)
   bool stage_f32 = false;            // J.v and linearising stages with fp32 Krylov storage
@@ -269,9 +280,6 @@ struct sdfs_handle {
   unsigned long long* slots = nullptr;      // residual slots (device)
   unsigned long long* slots_host = nullptr; // pinned mirror
   int nslots = 0;
-  std::vector<double*> andX, andR;
-  double* gram_row = nullptr;
-  double* gram_row_host = nullptr;
 
   double last_resid = std::numeric_limits<double>::quiet_NaN();
   std::vector<double> trace;
@@ -2182,364 +2190,6 @@ int solve_newton(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter,
   return 0;
 }
 
-// dense solve of the (m+1) x (m+1) bordered Anderson system, partial pivoting
-bool solve_dense(std::vector<double>& A, std::vector<double>& b, int n) {
-  for (int c = 0; c < n; ++c) {
-    int piv = c;
-    for (int r = c + 1; r < n; ++r) if (std::fabs(A[r * n + c]) > std::fabs(A[piv * n + c])) piv = r;
-    if (A[piv * n + c] == 0.0) return false;
-    if (piv != c) { for (int k = 0; k < n; ++k) std::swap(A[c * n + k], A[piv * n + k]); std::swap(b[c], b[piv]); }
-    for (int r = c + 1; r < n; ++r) {
-      const double f = A[r * n + c] / A[c * n + c];
-      if (f == 0.0) continue;
-      for (int k = c; k < n; ++k) A[r * n + k] -= f * A[c * n + k];
-      b[r] -= f * b[c];
-    }
-  }
-  for (int r = n - 1; r >= 0; --r) {
-    double s = b[r];
-    for (int k = r + 1; k < n; ++k) s -= A[r * n + k] * b[k];
-    b[r] = s / A[r * n + r];
-  }
-  return true;
-}
-
-// Anderson acceleration with jaxopt's parametrisation (code/solvers.py:98-124).
-int solve_anderson_host(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int64_t* n_apply, double* final_err) {
-  int rc;
-  const int m = o.history;
-  if (m < 1 || m > AND_MAX_M) return fail(h, SDFS_ERR_ARG, "Anderson history must be in 1..%d", AND_MAX_M);
-  if (o.mixing_freq < 1) return fail(h, SDFS_ERR_ARG, "mixing_freq must be >= 1");
-  if ((rc = ensure_buf(h, &h->buf0)) || (rc = ensure_buf(h, &h->buf1)) || (rc = ensure_scalars(h))) return rc;
-  while ((int)h->andX.size() < m) {
-    double *a = nullptr, *b = nullptr;
-    if ((rc = dev_alloc(h, &a, (size_t)h->N)) || (rc = dev_alloc(h, &b, (size_t)h->N))) return rc;
-    h->andX.push_back(a); h->andR.push_back(b);
-  }
-  if (!h->gram_row) {
-    if ((rc = dev_alloc(h, &h->gram_row, AND_MAX_M))) return rc;
-    HIPCHK(h, hipHostMalloc((void**)&h->gram_row_host, sizeof(double) * AND_MAX_M));
-  }
-  AndPtrs hp;
-  memset(&hp, 0, sizeof hp);
-  for (int j = 0; j < m; ++j) { hp.X[j] = h->andX[j]; hp.R[j] = h->andR[j]; }
-  const long long n = h->N;
-  const int g = vec_grid(n);
-  const size_t nb = sizeof(double) * (size_t)n;
-  hipStream_t st = h->stream;
-  double* x = h->buf0;
-  double* fx = h->buf1;
-  HIPCHK(h, hipMemcpyAsync(x, w, nb, hipMemcpyDeviceToDevice, st));
-  for (int j = 0; j < m; ++j) HIPCHK(h, hipMemsetAsync(h->andR[j], 0, nb, st));
-  std::vector<double> G((size_t)m * m, 0.0);
-  h->trace.clear();
-  long long it = 0;
-  double err = std::numeric_limits<double>::infinity();
-  int status = 0;
-  const int cvec = h->profiling ? counter_id(h, "anderson_blas1", 0, 0) : -1;
-  // Safeguard (not in jaxopt): when a mixing step leaves the domain (w <= 0 -> NaN in the next
-  // application; the (m+1)^2 system is badly conditioned once the residual history is nearly
-  // collinear and N r^2 dwarfs the absolute ridge), fall back to the plain step x_prev + r_prev from
-  // the last good iterate, drop the poisoned history slot and pause mixing until the history refills.
-  bool last_mixed = false;
-  int prev_pos = -1, rejected = 0;
-  long long no_mix_until = 0;
-  while (err > o.tol && it < o.max_iter) {
-    if ((rc = apply_T_dev(h, x, fx, nullptr, nullptr, 0.0))) return rc;
-    const int pos = (int)(it % m);
-    { ProfScope ps(h, cvec);
-      hipLaunchKernelGGL(k_and_push, dim3(g), dim3(VEC_BLOCK), 0, st, x, fx, hp, m, pos, n, h->partial);
-      hipLaunchKernelGGL(k_and_push_finish, dim3(1), dim3(VEC_BLOCK), 0, st, h->partial, g, m, h->gram_row); }
-    HIPCHK(h, hipMemcpyAsync(h->gram_row_host, h->gram_row, sizeof(double) * m, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    for (int j = 0; j < m; ++j) { G[(size_t)pos * m + j] = h->gram_row_host[j]; G[(size_t)j * m + pos] = h->gram_row_host[j]; }
-    err = std::sqrt(G[(size_t)pos * m + pos]);
-    if (!std::isfinite(err) && last_mixed && prev_pos >= 0 && rejected < 1000) {
-      for (int j = 0; j < m; ++j) { G[(size_t)pos * m + j] = 0.0; G[(size_t)j * m + pos] = 0.0; }
-      HIPCHK(h, hipMemsetAsync(h->andR[pos], 0, nb, st));
-      AndCoef c;
-      memset(&c, 0, sizeof c);
-      c.a[prev_pos] = 1.0;
-      { ProfScope ps(h, cvec);
-        hipLaunchKernelGGL(k_and_mix, dim3(g), dim3(VEC_BLOCK), 0, st, hp, c, m, 1.0, x, n); }   // x = X_prev + R_prev
-      err = std::sqrt(G[(size_t)prev_pos * m + prev_pos]);
-      last_mixed = false; ++rejected; ++it;
-      no_mix_until = it + m;
-      continue;
-    }
-    if (o.record_errors) h->trace.push_back(err);
-    bool mixed = false;
-    if (it + 1 >= m && it + 1 >= no_mix_until && (it + 1) % o.mixing_freq == 0 && std::isfinite(err)) {
-      const int d = m + 1;
-      std::vector<double> A((size_t)d * d, 0.0), b(d, 0.0);
-      for (int j = 1; j < d; ++j) { A[j] = 1.0; A[(size_t)j * d] = 1.0; }
-      double rg = o.ridge;                     // (< 0: relative to trace(G) / m, as in and_step_wave)
-      if (rg < 0.0) { double tr = 0.0; for (int j = 0; j < m; ++j) tr += G[(size_t)j * m + j]; rg = -rg * tr / m; }
-      for (int i = 0; i < m; ++i)
-        for (int j = 0; j < m; ++j) A[(size_t)(i + 1) * d + j + 1] = G[(size_t)i * m + j] + (i == j ? rg : 0.0);
-      b[0] = 1.0;
-      if (solve_dense(A, b, d)) {
-        AndCoef c;
-        memset(&c, 0, sizeof c);
-        for (int j = 0; j < m; ++j) c.a[j] = b[j + 1];
-        ProfScope ps(h, cvec);
-        hipLaunchKernelGGL(k_and_mix, dim3(g), dim3(VEC_BLOCK), 0, st, hp, c, m, o.beta, x, n);
-        mixed = true;
-      }
-    }
-    if (!mixed) std::swap(x, fx);
-    last_mixed = mixed; prev_pos = pos;
-    ++it;
-    if (!std::isfinite(err)) { status = SDFS_ERR_NUMERIC; break; }
-  }
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(w, x, nb, hipMemcpyDeviceToDevice, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  *n_iter = it; *n_apply = it; *final_err = err;
-  if (status) return fail(h, status, "non-finite Anderson residual at iteration %lld", it);
-  return 0;
-}
-
-// Small-grid plan: can the Anderson loop run its fused form (fast_kernels.hpp, SM_AND_FIRST / SM_AND_LAST) with history m?
-bool anderson_fused_ok(const sdfs_handle* h, int m) {
-  if (!(h->knobs.and_fused && h->fast.ok && h->fast.small && h->fast.passes.size() >= 2 && m <= AND_FUSE_M)) return false;
-  // (pair order reversed: the application ends on the fastest pair, whose tiles are contiguous -- the push's history
-  // streams then cost 4 lines per wave request instead of 64)
-  const FastPass& L = h->fast.passes.front();
-  const FastPass& F = h->fast.passes.back();
-  return (int)small_grid(L.sm, L.wpt) <= AND_FUSE_RING && L.sm.a3 != nullptr && F.sm.a3 != nullptr &&
-         small_and_variant(SM_AND_FIRST, F.r, F.wpt) != nullptr && small_and_variant(SM_AND_LAST, L.r, L.wpt) != nullptr;
-}
-
-// The same loop with its control on the device (vec_kernels.hpp, AndState / k_and_step / k_and_mix_dev): per pass
-// T, push, one single-workgroup step kernel (Gram row, solve, safeguard, stopping test) and the update of x, every
-// launch gated on the loop's own flag; `chunk` passes per host synchronisation, replayed from a hipGraph.
-int solve_anderson(sdfs_handle* h, const sdfs_opts& o, double* w, int64_t* n_iter, int64_t* n_apply, double* final_err) {
-  if (h->knobs.and_host) return solve_anderson_host(h, o, w, n_iter, n_apply, final_err);
-  int rc;
-  const int m = o.history;
-  if (m < 1 || m > AND_MAX_M) return fail(h, SDFS_ERR_ARG, "Anderson history must be in 1..%d", AND_MAX_M);
-  if (o.mixing_freq < 1) return fail(h, SDFS_ERR_ARG, "mixing_freq must be >= 1");
-  if ((rc = ensure_buf(h, &h->buf0)) || (rc = ensure_buf(h, &h->buf1)) || (rc = ensure_scalars(h)) || (rc = ensure_tmp(h))) return rc;
-  while ((int)h->andX.size() < m) {
-    double *a = nullptr, *b = nullptr;
-    if ((rc = dev_alloc(h, &a, (size_t)h->N)) || (rc = dev_alloc(h, &b, (size_t)h->N))) return rc;
-    h->andX.push_back(a); h->andR.push_back(b);
-  }
-  // passes per synchronisation: a multiple of the history length, so that the slot of pass i of a chunk is fixed
-  int chunk = std::max(1, o.check_every);
-  chunk = ((chunk + m - 1) / m) * m;
-  // Small-grid plan: the push rides on T's last pass, the control step and the update of x on the first pass of the next
-  // application (fast_kernels.hpp, SM_AND_LAST / SM_AND_FIRST): D/2 launches per pass instead of D/2 + 3.  The state
-  // alternates between two buffers (even chunks end where they began) and the passes whose step can mix are fixed at
-  // capture time (chunks are multiples of the mixing frequency).
-  bool fusedp = !h->profiling && anderson_fused_ok(h, m);
-  // large grids (the loop is HBM-bound there): the Gram matrix in one sweep where a solve is due (vec_kernels.hpp)
-  const bool lazyp = h->knobs.and_fused && !fusedp && !h->sharded && m <= AND_LAZY_M && h->N >= (1LL << 21);
-  if (lazyp) {
-    const long long unit = lcm(lcm(m, o.mixing_freq), 2);
-    chunk = (int)(((chunk + unit - 1) / unit) * unit);
-    if (!h->and_gram_partial) {
-      HIPCHK(h, hipMalloc((void**)&h->and_gram_partial, sizeof(double) * (size_t)AND_LAZY_PAIRS * AND_LAZY_BLOCKS));
-      h->misc_allocs.push_back(h->and_gram_partial);
-    }
-  }
-  if (fusedp) {
-    const long long unit = lcm(lcm(m, 2), o.mixing_freq);
-    // (a chunk of this form ends with a launch of its own and the passes do not depend on the chunking: the default
-    // polling interval is stretched, an explicit one is honoured)
-    if (h->check_every_default) chunk = 120;
-    if (unit > 4096) fusedp = false;
-    else chunk = (int)(((chunk + unit - 1) / unit) * unit);      // (a chunk ends with one launch of its own: the longer the better)
-  }
-  if (!h->and_state) {
-    HIPCHK(h, hipMalloc((void**)&h->and_state, 2 * sizeof(AndState)));
-    h->misc_allocs.push_back(h->and_state);
-    HIPCHK(h, hipHostMalloc((void**)&h->and_state_host, sizeof(AndState)));
-  }
-  if (h->and_slots < chunk) {
-    if (h->and_graph) { hipGraphExecDestroy(h->and_graph); h->and_graph = nullptr; }
-    if (h->and_err_host) { hipHostFree(h->and_err_host); hipHostFree(h->and_kind_host); }
-    HIPCHK(h, hipMalloc((void**)&h->and_err, sizeof(double) * chunk));
-    h->misc_allocs.push_back(h->and_err);
-    HIPCHK(h, hipMalloc((void**)&h->and_kind, sizeof(int) * chunk));
-    h->misc_allocs.push_back(h->and_kind);
-    HIPCHK(h, hipMalloc((void**)&h->and_flag, sizeof(unsigned) * chunk));
-    h->misc_allocs.push_back(h->and_flag);
-    HIPCHK(h, hipHostMalloc((void**)&h->and_err_host, sizeof(double) * chunk));
-    HIPCHK(h, hipHostMalloc((void**)&h->and_kind_host, sizeof(int) * chunk));
-    h->and_slots = chunk;
-  }
-  AndPtrs hp;
-  memset(&hp, 0, sizeof hp);
-  for (int j = 0; j < m; ++j) { hp.X[j] = h->andX[j]; hp.R[j] = h->andR[j]; }
-  const long long n = h->N;
-  const int g = vec_grid(n);
-  const size_t nb = sizeof(double) * (size_t)n;
-  hipStream_t st = h->stream;
-  double* x = h->buf0;
-  double* fx = h->buf1;
-  HIPCHK(h, hipMemcpyAsync(x, w, nb, hipMemcpyDeviceToDevice, st));
-  for (int j = 0; j < m; ++j) HIPCHK(h, hipMemsetAsync(h->andR[j], 0, nb, st));
-  AndState* S = h->and_state;
-  {
-    AndState& I = *h->and_state_host;
-    memset(&I, 0, sizeof I);
-    I.err = std::numeric_limits<double>::infinity();
-    I.prev_pos = -1.0; I.mix_rel = -1;
-    I.gate = (o.max_iter > 0 && I.err > o.tol) ? ~0ULL : 0ULL;
-    HIPCHK(h, hipMemcpyAsync(S, &I, sizeof I, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(S + 1, &I, sizeof I, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-  }
-  h->trace.clear();
-  const int cvec = h->profiling ? counter_id(h, "anderson_blas1", 0, 0) : -1;
-  // the end of every form of a chunk: the launches' error check, then errors, step kinds and the state go to the host
-  auto read_back = [&](int count, const AndState* state) -> int {
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(h->and_err_host, h->and_err, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(h->and_kind_host, h->and_kind, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(h->and_state_host, state, sizeof(AndState), hipMemcpyDeviceToHost, st));
-    return 0;
-  };
-  auto enqueue = [&](int count) -> int {
-    HIPCHK(h, hipMemsetAsync(h->and_kind, 0, sizeof(int) * (size_t)chunk, st));
-    for (int i = 0; i < count; ++i) {
-      const int pos = i % m;                       // chunks start on multiples of m
-      int r2 = apply_T_dev(h, x, fx, nullptr, &S->gate, 0.0);
-      if (r2) return r2;
-      ProfScope ps(h, cvec);
-      hipLaunchKernelGGL(k_and_push, dim3(g), dim3(VEC_BLOCK), 0, st, (const double*)x, (const double*)fx, hp, m, pos, n, h->partial, (const unsigned long long*)&S->gate);
-      hipLaunchKernelGGL(k_and_step, dim3(1), dim3(VEC_BLOCK), 0, st, (const double*)h->partial, g, m, pos, i, (const AndState*)S, S, h->and_err + i, h->and_kind + i,
-                         o.tol, (double)o.max_iter, (int)o.mixing_freq, o.ridge);
-      hipLaunchKernelGGL(k_and_mix_dev, dim3(g), dim3(VEC_BLOCK), 0, st, hp, (const AndState*)S, m, o.beta, x, (const double*)fx, pos, i, n);
-    }
-    return read_back(count, S);
-  };
-  // the fused form of a chunk: pass 0 starts from x as it stands, pass i > 0 opens with the step of pass i - 1; the step
-  // and the update of the chunk's last pass are the two launches of the unfused form.  State of pass i: S[i & 1].
-  auto enqueue_fused = [&](int count) -> int {
-    HIPCHK(h, hipMemsetAsync(h->and_kind, 0, sizeof(int) * (size_t)chunk, st));
-    HIPCHK(h, hipMemsetAsync(h->and_flag, 0, sizeof(unsigned) * (size_t)chunk, st));
-    const int np = (int)h->fast.passes.size();
-    const FastPass& PF = h->fast.passes[np - 1];
-    const FastPass& PL = h->fast.passes[0];
-    const int nbl = (int)small_grid(PL.sm, PL.wpt);
-    AndStepPar par;
-    par.tol = o.tol; par.max_iter = (double)o.max_iter; par.ridge = o.ridge; par.mixing_freq = (int)o.mixing_freq;
-    for (int i = 0; i < count; ++i) {
-      const int pos = i % m;
-      AndState* Si = S + (i & 1);
-      SmallIO io;
-      AndArgs an;
-      memset(&an, 0, sizeof an);
-      an.h = hp; an.par = par; an.beta = o.beta; an.m = m; an.nb = nbl;
-      // first pass
-      memset(&io, 0, sizeof io);
-      io.out = h->tmp;
-      if (i == 0) {
-        io.in = x; io.gate = &Si->gate;
-        hipLaunchKernelGGL(small_variant(SM_FIRST_T, PF.r, PF.wpt), dim3(small_grid(PF.sm, PF.wpt)), dim3(256), 0, st, PF.sm, io);
-      } else {
-        const int ppos = (i - 1) % m;
-        io.in = fx;
-        an.Sin = S + ((i - 1) & 1); an.Sout = Si; an.partial = h->partial; an.x = x; an.x_pos = hp.X[ppos]; an.r_pos = hp.R[ppos];
-        an.err_slot = h->and_err + (i - 1); an.kind_slot = h->and_kind + (i - 1); an.flag = h->and_flag + (i - 1);
-        an.pos = ppos; an.rel = i - 1;
-        an.step_kind = (i % (int)o.mixing_freq) == 0 ? 2 : (((i - 1) % (int)o.mixing_freq) == 0 ? 1 : 0);
-        // (+ 1: the workgroup that writes the state)
-        hipLaunchKernelGGL(small_and_variant(SM_AND_FIRST, PF.r, PF.wpt), dim3(small_grid(PF.sm, PF.wpt) + 1), dim3(256), 0, st, PF.sm, io, an);
-      }
-      for (int q = np - 2; q >= 1; --q) {
-        const FastPass& PM = h->fast.passes[q];
-        memset(&io, 0, sizeof io);
-        io.in = h->tmp; io.out = h->tmp; io.gate = &Si->gate;
-        hipLaunchKernelGGL(small_variant(SM_MID, PM.r, PM.wpt), dim3(small_grid(PM.sm, PM.wpt)), dim3(256), 0, st, PM.sm, io);
-      }
-      memset(&io, 0, sizeof io);
-      io.in = h->tmp; io.out = fx; io.old = x; io.gate = &Si->gate;
-      an.Sin = nullptr; an.Sout = nullptr; an.partial = nullptr; an.partial_out = h->partial;
-      an.x_pos = hp.X[pos]; an.r_pos = hp.R[pos]; an.pos = pos; an.rel = i; an.step_kind = 0; an.flag = h->and_flag + i;
-      hipLaunchKernelGGL(small_and_variant(SM_AND_LAST, PL.r, PL.wpt), dim3(nbl), dim3(256), 0, st, PL.sm, io, an);
-    }
-    const int lastp = count - 1;
-    {
-      AndArgs an;
-      memset(&an, 0, sizeof an);
-      an.h = hp; an.par = par; an.beta = o.beta; an.m = m; an.nb = nbl;
-      an.Sin = S + (lastp & 1); an.Sout = S + (count & 1); an.partial = h->partial; an.x = x;
-      an.x_pos = hp.X[lastp % m]; an.r_pos = hp.R[lastp % m];
-      an.err_slot = h->and_err + lastp; an.kind_slot = h->and_kind + lastp; an.flag = h->and_flag + lastp;
-      an.pos = lastp % m; an.rel = lastp; an.step_kind = 2;
-      hipLaunchKernelGGL(small_and_finish, dim3((unsigned)std::min<long long>((n + 255) / 256, 512)), dim3(256), 0, st, an, (const double*)fx, n);
-    }
-    return read_back(count, S + (count & 1));
-  };
-  // Large grids: <r, r> per pass, the whole Gram matrix in one sweep where a solve is due, history as Y_j (vec_kernels.hpp)
-  auto enqueue_lazy = [&](int count) -> int {
-    HIPCHK(h, hipMemsetAsync(h->and_kind, 0, sizeof(int) * (size_t)chunk, st));
-    const int gb = (int)std::min<long long>(AND_LAZY_BLOCKS, std::max<long long>(1, (n + 2 * VEC_BLOCK - 1) / (2 * VEC_BLOCK)));
-    for (int i = 0; i < count; ++i) {
-      const int pos = i % m;
-      // the iterate alternates between the two buffers (chunks are even): a plain step x = T x is then no copy at all,
-      // a mixing step writes over T x, which the push has consumed
-      double* const xi = (i & 1) ? fx : x;
-      double* const xo = (i & 1) ? x : fx;
-      // the push rides on T's last pass where that is the streamed form (stream_kernels.hpp, LineIO::and_*): x is read
-      // once, T x is not read back -- 9 grid streams per pass instead of 10, on a pass that is bound by its power, not its bytes
-      long long ptiles = 0;
-      Apply a(MODE_T, xi, xo, xi);
-      a.gate = &S->gate;
-      if (!h->knobs.no_and_push_fusion) {
-        a.push.y = hp.X[pos]; a.push.r = hp.R[pos]; a.push.beta = o.beta; a.push.dot = h->partial; a.push.tiles = &ptiles;
-      }
-      if (int r2 = apply(h, a)) return r2;
-      ProfScope ps(h, cvec);
-      if (ptiles == 0)
-        hipLaunchKernelGGL(k_and_push_lite, dim3(g), dim3(VEC_BLOCK), 0, st, (const double*)xi, (const double*)xo, hp.X[pos], hp.R[pos], o.beta, n, h->partial,
-                           (const unsigned long long*)&S->gate);
-      const int gpush = ptiles ? (int)ptiles : g;
-      const int refresh = ((i + 1) % (int)o.mixing_freq) == 0 ? 1 : 0;
-      if (refresh)
-        hipLaunchKernelGGL(k_and_gram_full, dim3(gb), dim3(VEC_BLOCK), 0, st, hp, m, (int)o.mixing_freq, n, h->and_gram_partial, (const AndState*)S);
-      hipLaunchKernelGGL(k_and_step_lazy, dim3(1), dim3(gpush > 4096 ? 1024 : VEC_BLOCK), 0, st, (const double*)h->partial, gpush, (const double*)h->and_gram_partial, gb, refresh,
-                         m, pos, i, S, h->and_err + i, h->and_kind + i, o.tol, (double)o.max_iter, (int)o.mixing_freq, o.ridge);
-      hipLaunchKernelGGL(k_and_mix_y, dim3(g), dim3(VEC_BLOCK), 0, st, hp, (const AndState*)S, m, o.beta, xo, (const double*)xo, pos, i, n);
-    }
-    return read_back(count, S);
-  };
-  auto enqueue_any = [&](int count) -> int { return fusedp ? enqueue_fused(count) : (lazyp ? enqueue_lazy(count) : enqueue(count)); };
-  const bool graph = o.use_graph && !h->profiling && st != nullptr && chunk > 1;
-  const double key[4] = {o.tol, (double)o.max_iter, o.beta, o.ridge};
-  if (graph && (h->and_graph == nullptr || h->and_graph_chunk != chunk || h->and_graph_m != m || h->and_graph_freq != (int)o.mixing_freq ||
-                memcmp(key, h->and_graph_key, sizeof key) != 0)) {
-    if ((rc = capture_graph(h, &h->and_graph, [&] { return enqueue_any(chunk); }))) return rc;
-    h->and_graph_chunk = chunk; h->and_graph_m = m; h->and_graph_freq = (int)o.mixing_freq;
-    memcpy(h->and_graph_key, key, sizeof key);
-  }
-  long long enq = 0;          // passes enqueued so far (a multiple of chunk while the loop runs)
-  bool running = h->and_state_host->gate != 0ULL;
-  while (running && enq < o.max_iter) {
-    const int count = (int)std::min<long long>(chunk, o.max_iter - enq);
-    if (graph && count == chunk) { HIPCHK(h, hipGraphLaunch(h->and_graph, st)); }
-    else if ((rc = enqueue_any(count))) return rc;
-    HIPCHK(h, hipStreamSynchronize(st));
-    enq += count;
-    if (o.record_errors)
-      for (int i = 0; i < count; ++i) if (h->and_kind_host[i] == 1) h->trace.push_back(h->and_err_host[i]);
-    running = h->and_state_host->gate != 0ULL;
-  }
-  const AndState& F = *h->and_state_host;
-  const long long it = (long long)F.it;
-  const double err = F.err;
-  // (batched-Gram loop: pass i leaves the iterate in buffer (i + 1) & 1)
-  HIPCHK(h, hipMemcpyAsync(w, (lazyp && (it & 1)) ? fx : x, nb, hipMemcpyDeviceToDevice, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  *n_iter = it; *n_apply = it; *final_err = err;
-  if (F.status != 0.0) return fail(h, SDFS_ERR_NUMERIC, "non-finite Anderson residual at iteration %lld", it);
-  return 0;
-}
-
 // ---------------------------------------------------------------------------
 // true when the `count` consecutive blocks of `len` doubles are bit for bit the same
 bool slices_identical(const double* p, long long count, size_t len) {
@@ -2938,6 +2588,8 @@ int stream_grid(const sdfs_handle* h, long long n, int block) {
 }
 }  // namespace
 
+#include "anderson_host.hpp"   // Anderson acceleration: its loops (solve_anderson) and step API (sdfs_anderson_*), built on the definitions above
+
 // ===========================================================================
 extern "C" {
 
@@ -3169,9 +2821,9 @@ void sdfs_destroy(sdfs_handle* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   if (h->sa_graph) hipGraphExecDestroy(h->sa_graph);
-  if (h->and_graph) hipGraphExecDestroy(h->and_graph);
-  if (h->and_state_host) hipHostFree(h->and_state_host);
-  if (h->and_err_host) { hipHostFree(h->and_err_host); hipHostFree(h->and_kind_host); }
+  if (h->anderson.graph) hipGraphExecDestroy(h->anderson.graph);
+  for (void* p : {(void*)h->anderson.state_host, (void*)h->anderson.err_host, (void*)h->anderson.kind_host, (void*)h->anderson.gram_row_host})
+    if (p) hipHostFree(p);
   for (int i = 0; i < 2; ++i) if (h->bicg_graph[i]) hipGraphExecDestroy(h->bicg_graph[i]);
   for (double* p : h->dev_allocs) hipFree(p);
   if (h->price.res) hipFree(h->price.res);
@@ -3179,7 +2831,6 @@ void sdfs_destroy(sdfs_handle* h) {
   if (h->slots) hipFree(h->slots);
   if (h->slots_host) hipHostFree(h->slots_host);
   if (h->sc_host) hipHostFree(h->sc_host);
-  if (h->gram_row_host) hipHostFree(h->gram_row_host);
   if (h->bicg_gate_host) hipHostFree(h->bicg_gate_host);
   for (auto& p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   for (auto e : h->event_pool) hipEventDestroy(e);
@@ -3212,7 +2863,7 @@ int sdfs_set_stream(sdfs_handle* h, void* s, int use_own) {
   int rc = check(h); if (rc) return rc;
   hipStream_t ns = use_own ? h->own_stream : (hipStream_t)s;     // s == NULL is the device's default stream
   if (ns != h->stream && h->sa_graph) { hipGraphExecDestroy(h->sa_graph); h->sa_graph = nullptr; }
-  if (ns != h->stream && h->and_graph) { hipGraphExecDestroy(h->and_graph); h->and_graph = nullptr; }
+  if (ns != h->stream && h->anderson.graph) { hipGraphExecDestroy(h->anderson.graph); h->anderson.graph = nullptr; }
   if (ns != h->stream) for (int i = 0; i < 2; ++i) if (h->bicg_graph[i]) { hipGraphExecDestroy(h->bicg_graph[i]); h->bicg_graph[i] = nullptr; }
   h->stream = ns;
   return 0;
@@ -4063,117 +3714,6 @@ int sdfs_krylov_gate(sdfs_handle* h, const void** gate_dev) {
   if (!gate_dev) return fail(h, SDFS_ERR_ARG, "NULL pointer");
   if ((rc = ensure_bicg_gate(h))) return rc;
   *gate_dev = h->bicg_gate;
-  return 0;
-}
-
-// ---- Anderson acceleration on a sharded grid: the single-GPU loop's batched-Gram kernels on this rank's shard -----------
-constexpr int DAND_SLOTS = 256;       // error ring (one slot per pass, read back by sdfs_anderson_state)
-static_assert(AND_LAZY_PAIRS == SDFS_AND_NPAIRS, "include/sdfs_hip.h states the length of the Gram sums");
-
-int sdfs_anderson_begin(sdfs_handle* h, int64_t n, int history, double* y_hist_dev, double* r_hist_dev, double tol,
-                        int64_t max_iter, double beta, double ridge, int mixing_freq) {
-  int rc = check(h); if (rc) return rc;
-  if (n < 1 || !y_hist_dev || !r_hist_dev) return fail(h, SDFS_ERR_ARG, "bad argument");
-  if (history < 1 || history > AND_LAZY_M) return fail(h, SDFS_ERR_ARG, "Anderson history must be in 1..%d", AND_LAZY_M);
-  if (mixing_freq < 1) return fail(h, SDFS_ERR_ARG, "mixing_freq must be >= 1");
-  if ((n & 1) && history > 0 && ((uintptr_t)r_hist_dev % 16 != 0)) return fail(h, SDFS_ERR_ARG, "history buffers must be 16-byte aligned");
-  if ((rc = ensure_scalars(h))) return rc;
-  if (!h->and_state) {
-    HIPCHK(h, hipMalloc((void**)&h->and_state, 2 * sizeof(AndState)));
-    h->misc_allocs.push_back(h->and_state);
-    HIPCHK(h, hipHostMalloc((void**)&h->and_state_host, sizeof(AndState)));
-  }
-  if (h->and_slots < DAND_SLOTS) {
-    if (h->and_graph) { hipGraphExecDestroy(h->and_graph); h->and_graph = nullptr; }
-    if (h->and_err_host) { hipHostFree(h->and_err_host); hipHostFree(h->and_kind_host); h->and_err_host = nullptr; h->and_kind_host = nullptr; }
-    HIPCHK(h, hipMalloc((void**)&h->and_err, sizeof(double) * DAND_SLOTS));
-    h->misc_allocs.push_back(h->and_err);
-    HIPCHK(h, hipMalloc((void**)&h->and_kind, sizeof(int) * DAND_SLOTS));
-    h->misc_allocs.push_back(h->and_kind);
-    HIPCHK(h, hipMalloc((void**)&h->and_flag, sizeof(unsigned) * DAND_SLOTS));
-    h->misc_allocs.push_back(h->and_flag);
-    HIPCHK(h, hipHostMalloc((void**)&h->and_err_host, sizeof(double) * DAND_SLOTS));
-    HIPCHK(h, hipHostMalloc((void**)&h->and_kind_host, sizeof(int) * DAND_SLOTS));
-    h->and_slots = DAND_SLOTS;
-  }
-  if (!h->and_gram_partial) {
-    HIPCHK(h, hipMalloc((void**)&h->and_gram_partial, sizeof(double) * (size_t)AND_LAZY_PAIRS * AND_LAZY_BLOCKS));
-    h->misc_allocs.push_back(h->and_gram_partial);
-  }
-  auto& D = h->dand;
-  D.on = true; D.n = n; D.m = history; D.mixing_freq = mixing_freq; D.tol = tol; D.max_iter = (double)max_iter; D.beta = beta; D.ridge = ridge;
-  memset(&D.hp, 0, sizeof D.hp);
-  for (int j = 0; j < history; ++j) { D.hp.X[j] = y_hist_dev + (size_t)j * (size_t)n; D.hp.R[j] = r_hist_dev + (size_t)j * (size_t)n; }
-  hipStream_t st = h->stream;
-  HIPCHK(h, hipMemsetAsync(r_hist_dev, 0, sizeof(double) * (size_t)history * (size_t)n, st));
-  HIPCHK(h, hipMemsetAsync(h->and_kind, 0, sizeof(int) * DAND_SLOTS, st));
-  AndState& I = *h->and_state_host;
-  memset(&I, 0, sizeof I);
-  I.err = std::numeric_limits<double>::infinity();
-  I.prev_pos = -1.0; I.mix_rel = -1;
-  I.gate = (max_iter > 0 && I.err > tol) ? ~0ULL : 0ULL;
-  HIPCHK(h, hipMemcpyAsync(h->and_state, &I, sizeof I, hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  return 0;
-}
-
-int sdfs_anderson_gate(sdfs_handle* h, const void** gate_dev) {
-  int rc = check(h); if (rc) return rc;
-  if (!gate_dev || !h->dand.on) return fail(h, SDFS_ERR_ARG, "sdfs_anderson_begin first");
-  *gate_dev = &h->and_state->gate;
-  return 0;
-}
-
-int sdfs_anderson_step(sdfs_handle* h, int step, int64_t pass, const double* x_in, double* x_out, double* sums_dev) {
-  int rc = check(h); if (rc) return rc;
-  const auto& D = h->dand;
-  if (!D.on) return fail(h, SDFS_ERR_ARG, "sdfs_anderson_begin first");
-  if (pass < 0 || !sums_dev) return fail(h, SDFS_ERR_ARG, "bad argument");
-  const long long n = D.n;
-  const int m = D.m, g = vec_grid(n), pos = (int)(pass % m), slot = (int)(pass % DAND_SLOTS), rel = (int)(pass & 0x3fffffff);
-  const int gb = (int)std::min<long long>(AND_LAZY_BLOCKS, std::max<long long>(1, (n + 2 * VEC_BLOCK - 1) / (2 * VEC_BLOCK)));
-  AndState* S = h->and_state;
-  hipStream_t st = h->stream;
-  const unsigned long long* gate = &S->gate;
-  switch (step) {
-    case SDFS_AND_PUSH:       // Y[pos] = x + beta r, R[pos] = r = x_out - x_in, sums[0] = this rank's <r, r>
-      if (!x_in || !x_out) return fail(h, SDFS_ERR_ARG, "NULL iterate");
-      hipLaunchKernelGGL(k_and_push_lite, dim3(g), dim3(VEC_BLOCK), 0, st, x_in, (const double*)x_out, D.hp.X[pos], D.hp.R[pos], D.beta, n, h->partial, gate);
-      hipLaunchKernelGGL(k_presum, dim3(1), dim3(VEC_BLOCK), 0, st, (const double*)h->partial, g, 1, sums_dev, gate);
-      break;
-    case SDFS_AND_GRAM:       // sums[1 ..] = this rank's part of the whole Gram matrix (pairs i <= j in k_and_gram_full's order)
-      hipLaunchKernelGGL(k_and_gram_full, dim3(gb), dim3(VEC_BLOCK), 0, st, D.hp, m, D.mixing_freq, n, h->and_gram_partial, (const AndState*)S);
-      hipLaunchKernelGGL(k_presum, dim3(1), dim3(VEC_BLOCK), 0, st, (const double*)h->and_gram_partial, gb, AND_LAZY_PAIRS, sums_dev + 1, gate);
-      break;
-    case SDFS_AND_STEP: {     // the control step from the all-reduced sums (nb = 0: totals, not partials)
-      const int refresh = ((pass + 1) % D.mixing_freq) == 0 ? 1 : 0;
-      hipLaunchKernelGGL(k_and_step_lazy, dim3(1), dim3(VEC_BLOCK), 0, st, (const double*)sums_dev, 0, (const double*)(sums_dev + 1), 1, refresh,
-                         m, pos, rel, S, h->and_err + slot, h->and_kind + slot, D.tol, D.max_iter, D.mixing_freq, D.ridge);
-      break;
-    }
-    case SDFS_AND_MIX:        // the update of x the step decided on, in place in x_out (= T x_in on entry)
-      if (!x_out) return fail(h, SDFS_ERR_ARG, "NULL iterate");
-      hipLaunchKernelGGL(k_and_mix_y, dim3(g), dim3(VEC_BLOCK), 0, st, D.hp, (const AndState*)S, m, D.beta, x_out, (const double*)x_out, pos, rel, n);
-      break;
-    default:
-      return fail(h, SDFS_ERR_ARG, "unknown Anderson step %d", step);
-  }
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-
-int sdfs_anderson_state(sdfs_handle* h, double* out8_host, double* errs_host, int64_t first_pass, int64_t count) {
-  int rc = check(h); if (rc) return rc;
-  if (!h->dand.on || !out8_host) return fail(h, SDFS_ERR_ARG, "sdfs_anderson_begin first");
-  if (count < 0 || count > DAND_SLOTS || first_pass < 0 || (count > 0 && !errs_host)) return fail(h, SDFS_ERR_ARG, "bad error window");
-  hipStream_t st = h->stream;
-  HIPCHK(h, hipMemcpyAsync(h->and_state_host, h->and_state, sizeof(AndState), hipMemcpyDeviceToHost, st));
-  if (count > 0) HIPCHK(h, hipMemcpyAsync(h->and_err_host, h->and_err, sizeof(double) * DAND_SLOTS, hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  const AndState& F = *h->and_state_host;
-  out8_host[0] = F.it; out8_host[1] = F.err; out8_host[2] = F.gate != 0ULL ? 1.0 : 0.0; out8_host[3] = F.status;
-  out8_host[4] = F.rejected; out8_host[5] = F.no_mix_until; out8_host[6] = F.last_mixed; out8_host[7] = F.prev_pos;
-  for (int64_t i = 0; i < count; ++i) errs_host[i] = h->and_err_host[(first_pass + i) % DAND_SLOTS];
   return 0;
 }
 

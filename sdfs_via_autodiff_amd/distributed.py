@@ -658,8 +658,8 @@ AND_DEVICE_MAX_M = 12
 
 
 def _anderson_sharded_device(op, w_loc, tol, max_iter, m, mixing_frequency, beta, ridge, errors, stats, check_every):
-    """anderson_sharded on the library's own kernels (sdfs_anderson_step: the single-GPU loop's batched-Gram form,
-    csrc/vec_kernels.hpp) with the loop's control in the handle's device state: per pass one sharded application of T
+    """anderson_sharded on the library's own kernels (sdfs_anderson_step, csrc/anderson_host.hpp: the single-GPU loop's
+    batched-Gram form, csrc/vec_kernels.hpp) with the loop's control in the handle's device state: per pass one sharded application of T
     (stage kernels gated on the loop's own word), the push, ONE all-reduce of |r|^2, on every mixing_frequency-th pass the
     Gram sweep and an all-reduce of its 78 sums, the control step (one workgroup: stopping test, solve, safeguard --
     identical on every rank, it only sees all-reduced values) and the update of x.  The iterate alternates between two

@@ -2,14 +2,14 @@
 TEST INFRASTRUCTURE -- numpy restatement of the rule by which the continuous-state operator chooses, per grid
 point, how it reads the iterate.  A restatement of this project's own code, formula by formula:
 
-  host   sdfs_via_autodiff_amd/csrc/sdfs_api.hip   (sdfs_create_continuous)
-           :3024-3028  etamax[d] = max_m |eta[d][m]|
-           :3029-3044  tensor-rule detection: M = tq^D (tq = 2 .. 64) and eta[d][m] = eta[d][((m / tq^d) % tq) tq^d]
-           :3047-3065  mext[d] = the largest box extent any grid point asks for in dimension d, vmax = prod mext,
+  host   sdfs_via_autodiff_amd/csrc/sdfs_api.hip   (sdfs_create_continuous, from its upload of the nodes to its end)
+           cd.etamax   etamax[d] = max_m |eta[d][m]|
+           tq          tensor-rule detection: M = tq^D (tq = 2 .. 64) and eta[d][m] = eta[d][((m / tq^d) % tq) tq^d]
+           mext        mext[d] = the largest box extent any grid point asks for in dimension d, vmax = prod mext,
                        uomax = prod over all but the two fastest dimensions
-           :3066-3068  cap = min(vmax, 4000), rounded up to even
-           :3069-3074  pre-contraction iff tq and vmax <= 4000 and uomax tq^2 + cap <= 4000; then ucap = uomax tq^2
-           :720-723    dynamic LDS = 8 (cap + ucap) bytes for T, twice that for J.v
+           cd.cap      cap = min(vmax, 4000), rounded up to even
+           cd.ucap     pre-contraction iff tq and vmax <= 4000 and uomax tq^2 + cap <= 4000; then ucap = uomax tq^2
+           launch_cont dynamic LDS = 8 (cap + ucap) bytes for T, twice that for J.v
   kernel sdfs_via_autodiff_amd/csrc/cont_kernel.hpp
            :133-143    a[d], k[d]: the affine map node -> next-state coordinate of this block's grid point
            :152-164    blo / bext per dimension from the last dimension down; a block is staged while the running
@@ -24,15 +24,15 @@ The three paths a block can take:
 Classes of a whole launch:  A every block on path 1,  B every block on path 2,  C staged and unstaged blocks mixed,
 D no block staged.
 
-The dynamics table (rho, xcoef / xdim, vol = sconst or phi exp(x[voldim])) restates :2981-3008.
+The dynamics table (rho, xcoef / xdim, vol = sconst or phi exp(x[voldim])) restates the per-model branches of sdfs_create_continuous.
 """
 import numpy as np
 
-CAP_LIMIT = 4000            # sdfs_api.hip:3066
+CAP_LIMIT = 4000            # sdfs_api.hip, sdfs_create_continuous: cap_limit
 
 
 def dynamics(model, params):
-    """Per dimension (rho, sconst, phi, voldim, xcoef, xdim); -1 = absent (sdfs_api.hip:2981-3008)."""
+    """Per dimension (rho, sconst, phi, voldim, xcoef, xdim); -1 = absent (sdfs_create_continuous, the model branches)."""
     q = [float(p) for p in params]
     if model == "ssy":          # dims h_lam, h_c, h_z, z
         return [(q[9], q[12], 0.0, -1, 0.0, -1), (q[8], q[11], 0.0, -1, 0.0, -1),
@@ -45,7 +45,7 @@ def dynamics(model, params):
 
 
 def tensor_order(nodes):
-    """tq of sdfs_api.hip:3029-3044: the 1-D order of a tensor rule in gridmake order, else 0."""
+    """tq of sdfs_create_continuous: the 1-D order of a tensor rule in gridmake order, else 0."""
     D, M = nodes.shape
     tq = next((c for c in range(2, 65) if c ** D == M), 0)
     if not tq:
@@ -60,7 +60,7 @@ def tensor_order(nodes):
 
 def box_extents(model, params, grids, nodes):
     """bext[d] of every grid point (cont_kernel.hpp:133-143, :152-160; the host evaluates the same expressions over
-    (i, ix, iv) at sdfs_api.hip:3051-3061): a list of D integer arrays that broadcast against the grid's shape."""
+    (i, ix, iv) in sdfs_create_continuous's mext loop): a list of D integer arrays that broadcast against the grid's shape."""
     grids = [np.asarray(g, dtype=np.float64) for g in grids]
     nodes = np.asarray(nodes, dtype=np.float64)
     D = len(grids)

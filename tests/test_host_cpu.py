@@ -381,6 +381,21 @@ def test_header_is_plain_c_and_binds_from_c(tmp_path):
     assert r.returncode == 0, r.stderr
 
 
+def test_anderson_host_layer_has_one_home():
+    """The Anderson host code lives in csrc/anderson_host.hpp, which csrc/sdfs_api.hip includes; each of its entry
+    points is defined exactly once across the two files (a definition: the name after its return type at the start
+    of a line)."""
+    csrc = os.path.join(REPO, "sdfs_via_autodiff_amd", "csrc")
+    assert os.path.isfile(os.path.join(csrc, "anderson_host.hpp"))
+    api = open(os.path.join(csrc, "sdfs_api.hip")).read()
+    assert len(re.findall(r'^#include "anderson_host\.hpp"', api, flags=re.M)) == 1
+    both = api + "\n" + open(os.path.join(csrc, "anderson_host.hpp")).read()
+    for name in ("solve_dense", "solve_anderson_host", "anderson_fused_ok", "solve_anderson",
+                 "sdfs_anderson_begin", "sdfs_anderson_gate", "sdfs_anderson_step", "sdfs_anderson_state"):
+        defs = re.findall(r"^(?:int|bool) %s\(" % name, both, flags=re.M)
+        assert len(defs) == 1, f"{name}: {len(defs)} definitions"
+
+
 def test_bench_gpus_flag_never_falls_back_to_one_gpu():
     """`python bench.py --gpus N` without a launcher spawns its own ranks (as a child process) and must exit
     non-zero -- never print an N = 1 line -- when fewer than N devices or ranks come up."""
